@@ -99,6 +99,38 @@ def _cpu_baseline_here(n_cpu):
     return out
 
 
+DUMP_LU_FULL_MAX_BYTES = 32 << 20   # --dump-outputs: the whole LU up to this size (N <= 2048), else a sample of it
+DUMP_LU_SAMPLE = 1 << 22             # entries drawn for that sample (<= 32 MiB of float64 with IPIV and info: under 64 MB in all)
+
+
+def dump_sample_index(n, count=DUMP_LU_SAMPLE, seed=0):
+    """The fixed, seeded sample of an n x n matrix that --dump-outputs writes when the whole LU is too big: sorted distinct
+    column-major positions, returned as (rows, cols)."""
+    import numpy as np
+    flat = np.unique(np.random.default_rng(seed).integers(0, n * n, size=count, dtype=np.int64))
+    return flat % n, flat // n
+
+
+def dump_outputs(out_dir, LU, ipiv, info):
+    """Write what one factorization returned to its caller as out_dir/<name>.npy, float64: ipiv (1-based pivot rows), info,
+    and lu (the whole N x N factors, L below the unit diagonal and U on and above it) or, when that would pass
+    DUMP_LU_FULL_MAX_BYTES, lu_sample (LU at dump_sample_index(N), column-major order).  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    n = LU.shape[0]
+    arrays = {"ipiv": ipiv.cpu().numpy().astype(np.float64), "info": np.array([info], dtype=np.float64)}
+    if n * n * 8 <= DUMP_LU_FULL_MAX_BYTES:
+        arrays["lu"] = LU.cpu().numpy()
+    else:
+        rows, cols = dump_sample_index(n)
+        arrays["lu_sample"] = LU[torch.from_numpy(rows).to(LU.device), torch.from_numpy(cols).to(LU.device)].cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def self_launch(args):
     """`python bench.py --gpus N ...` without a launcher: run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W ...` as a child process, relay its output
@@ -166,7 +198,14 @@ def main():
     ap.add_argument("--legs", default="", help="comma-separated POSITIVE list of the extra legs to run (ir, phases, mxp, config5, ref_style, cpu, configs, check); "
                                                "default: all that no --no-* flag removes.  `--legs none` runs the timed steps only")
     ap.add_argument("--cpu-only", action="store_true", help="print the cpu_baseline object (CPU LAPACK leg alone) and exit: no GPU, no torch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (LU factors or a fixed seeded sample of them, IPIV, "
+                         "info) as DIR/<name>.npy in float64, under 64 MB in all; single-GPU runs only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs needs --gpus 1")
     if args.legs:
         want = {w.strip() for w in args.legs.split(",") if w.strip() and w.strip() != "none"}
         for leg in ("ir", "phases", "mxp", "config5", "ref_style", "cpu", "configs", "check"):
@@ -249,6 +288,8 @@ def main():
     flops = 2.0 / 3.0 * n ** 3
     value = flops / (ms_per_step * 1e-3) / 1e9
     LU = w
+    # (before any later leg reuses the work matrices)
+    dumped = dump_outputs(args.dump_outputs, LU, ipiv, info) if args.dump_outputs else None
     # The timed steps run with the library's default timers: HIP-event pairs around the trailing-update launches only (what the
     # roofline needs).  The other per-phase timers cost ~8 ms per step (an event pair around every small launch of the chain): one
     # extra, untimed step with all of them on (option event_timers = 2) gives the breakdown below.
@@ -677,6 +718,8 @@ def main():
         "phases_sync_timed": phases, "mxp": mxp, "mxp_x3": mxp_x3, "mxp_gmres": mxp_gmres, "config5": config5,
         "roofline": roofline, "peaks": peaks, "reference_style": ref_style, "check": check, "configs": configs,
     }
+    if dumped:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(args.cpu_n)
     print(json.dumps(_finite(line), allow_nan=False))

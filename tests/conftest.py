@@ -44,3 +44,10 @@ def bits16(t):
 
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def matgen_golden(args):
+    """Bytes the reference's matrix_generator.cpp writes for these arguments (tests/golden/make_golden_matgen.py)."""
+    import gzip
+    with gzip.open(os.path.join(GOLDEN_DIR, "matgen", "matgen_" + "_".join(args) + ".txt.gz"), "rb") as f:
+        return f.read()

@@ -2,7 +2,7 @@
 
 The reference ships no golden vectors and its CUDA path cannot be built here, so these vectors pin the
 oracle (and through it the HIP path) against regressions; the generator inputs themselves are pinned
-against the real reference generator binary (oracle/_ref/matgen) by tests/test_oracle.py.
+against the real reference generator's stored output (tests/golden/matgen/) by tests/test_oracle.py.
 Run from the repo root:  python tests/golden/make_golden.py
 """
 import hashlib

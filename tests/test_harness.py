@@ -4,6 +4,8 @@ import subprocess
 
 import pytest
 
+from conftest import matgen_golden
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = os.path.join(ROOT, "harness")
 
@@ -12,15 +14,14 @@ def _build():
     subprocess.run(["make", "-C", H, "-s"], check=True)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "matgen")), reason="oracle/_ref/matgen missing")
 @pytest.mark.parametrize("args", [("64", "2", "exp"), ("40", "7", "lin", "0.3"), ("33", "31", "lin"), ("20", "5", "exp", "0.5")])
 def test_matgen_cli_is_byte_identical_to_the_reference(mpf, tmp_path, args):
+    """The harness generator writes what the reference's matrix_generator.cpp writes (stored under tests/golden/matgen/)."""
     mpf.build()
     _build()
-    a, b = tmp_path / "a.txt", tmp_path / "b.txt"
+    a = tmp_path / "a.txt"
     subprocess.run([os.path.join(H, "mpf_matgen"), str(a), *args], check=True, capture_output=True)
-    subprocess.run([os.path.join(ROOT, "oracle", "_ref", "matgen"), str(b), *args], check=True, capture_output=True)
-    assert a.read_bytes() == b.read_bytes()
+    assert a.read_bytes() == matgen_golden(args)
 
 
 def test_bench_cli_without_gpu_reports_like_the_reference(mpf, tmp_path):

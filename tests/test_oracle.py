@@ -5,12 +5,11 @@ import ctypes
 import hashlib
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN_DIR
+from conftest import GOLDEN_DIR, matgen_golden
 
 
 def test_rand_matches_glibc_and_survey_kat(oracle):
@@ -21,13 +20,12 @@ def test_rand_matches_glibc_and_survey_kat(oracle):
     assert oracle.rand_stream(5000).tolist() == [libc.rand() for _ in range(5000)]
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref", "matgen")),
-                    reason="oracle/_ref/matgen (built from the reference tree) not present")
 @pytest.mark.parametrize("args", [("128", "2", "exp"), ("40", "7", "lin", "0.3"), ("30", "3", "lin")])
 def test_matgen_matches_reference_binary(oracle, tmp_path, args):
-    """The in-memory generator restatement equals the reference's own matrix_generator.cpp output."""
+    """The in-memory generator restatement equals the reference's own matrix_generator.cpp output (stored under
+    tests/golden/matgen/ by tests/golden/make_golden_matgen.py)."""
     f = tmp_path / "m.txt"
-    subprocess.run([oracle.REF_MATGEN, str(f), *args], check=True, capture_output=True)
+    f.write_bytes(matgen_golden(args))
     step = int(args[1]); func = args[2]; sp = float(args[3]) if len(args) > 3 else 0.0
     mats = oracle.read_matgen_file(str(f))
     assert len(mats) >= 3
