@@ -52,33 +52,30 @@ extern "C" int mpf_check_plu_dev(mpf_ctx *c, const double *d_A, int64_t lda, con
     if (!c || !d_A || !d_LU || !d_ipiv) return -1;
     if (N <= 0 || lda < N || ldlu < N) { c->err = "check_plu: bad N / leading dimension"; return -1; }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    double *R = nullptr, *Lm = nullptr, *Um = nullptr, *part = nullptr;
-    const size_t bytes = (size_t)N * (size_t)N * sizeof(double);
+    Buf<double> R, Lm, Um, part;
     const int nred = 1024;
     int rc = 0;
-    auto done = [&](int code) { if (R) hipFree(R); if (Lm) hipFree(Lm); if (Um) hipFree(Um); if (part) hipFree(part); return code; };
-    if (hipMalloc((void **)&R, bytes) != hipSuccess || hipMalloc((void **)&Lm, bytes) != hipSuccess ||
-        hipMalloc((void **)&Um, bytes) != hipSuccess || hipMalloc((void **)&part, 3 * nred * sizeof(double)) != hipSuccess) {
+    if (R.grow(N * N) != hipSuccess || Lm.grow(N * N) != hipSuccess || Um.grow(N * N) != hipSuccess || part.grow(3 * nred) != hipSuccess) {
         c->err = "check_plu: out of device memory (needs 3 N^2 doubles of scratch)";
-        return done(-2);
+        return -2;
     }
-    if (hipMemcpy2DAsync(R, (size_t)N * 8, d_A, (size_t)lda * 8, (size_t)N * 8, (size_t)N, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return done(-2);
+    if (hipMemcpy2DAsync(R, (size_t)N * 8, d_A, (size_t)lda * 8, (size_t)N * 8, (size_t)N, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return -2;
     // P^T A: the swaps in forward order on every column (the inverse of benchmark.cpp:84-95's reverse pass over L U)
     rc = launch_laswp_seq(c, R, N, N, 0, (int)N, d_ipiv, N);
-    if (rc) return done(rc);
+    if (rc) return rc;
     dim3 g((unsigned)((N + 255) / 256), (unsigned)N);
     split_lu_kernel<<<g, 256, 0, c->stream>>>(d_LU, ldlu, Lm, Um, N);
     rc = launch_dgemm_minus(c, N, N, (int)N, Lm, N, Um, N, R, N);   // R -= L U (benchmark.cpp:77-82 on the MFMA GEMM)
-    if (rc) return done(rc);
+    if (rc) return rc;
     check_reduce_kernel<<<nred, 256, 0, c->stream>>>(R, d_A, lda, N, part);
     std::vector<double> h(3 * nred);
     if (hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "check_plu: device error"; return done(-2); }
+        hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "check_plu: device error"; return -2; }
     double mx = 0, s2 = 0, a2 = 0;
     for (int i = 0; i < nred; ++i) { mx = h[3 * i] > mx ? h[3 * i] : mx; s2 += h[3 * i + 1]; a2 += h[3 * i + 2]; }
     if (max_abs_err) *max_abs_err = mx;
     if (fro_rel_err) *fro_rel_err = a2 > 0 ? std::sqrt(s2 / a2) : std::sqrt(s2);
-    return done(0);
+    return 0;
 }
 
 // host-buffer form for the harness (benchmark.cpp:228-233): uploads A, the factors and the pivots, checks on the device
@@ -88,17 +85,15 @@ extern "C" int mpf_check_plu_host(const double *A, const double *LU, const int32
     mpf_ctx *c = nullptr;
     int rc = mpf_create(&c, 0);
     if (rc) return rc;
-    double *dA = nullptr, *dLU = nullptr;
-    int32_t *dP = nullptr;
-    const size_t bytes = (size_t)N * (size_t)N * sizeof(double);
-    if (hipMalloc((void **)&dA, bytes) != hipSuccess || hipMalloc((void **)&dLU, bytes) != hipSuccess ||
-        hipMalloc((void **)&dP, (size_t)N * sizeof(int32_t)) != hipSuccess) rc = -2;
-    if (!rc && (hipMemcpy(dA, A, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dLU, LU, bytes, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(dP, ipiv, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)) rc = -2;
-    if (!rc) rc = mpf_check_plu_dev(c, dA, N, dLU, N, dP, N, max_abs_err, fro_rel_err);
-    if (dA) hipFree(dA);
-    if (dLU) hipFree(dLU);
-    if (dP) hipFree(dP);
+    {
+        Buf<double> dA, dLU;
+        Buf<int32_t> dP;
+        const size_t bytes = (size_t)N * (size_t)N * sizeof(double);
+        if (dA.grow(N * N) != hipSuccess || dLU.grow(N * N) != hipSuccess || dP.grow(N) != hipSuccess) rc = -2;
+        if (!rc && (hipMemcpy(dA, A, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dLU, LU, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(dP, ipiv, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)) rc = -2;
+        if (!rc) rc = mpf_check_plu_dev(c, dA, N, dLU, N, dP, N, max_abs_err, fro_rel_err);
+    }   // (the buffers go before the context)
     mpf_destroy(c);
     return rc;
 }

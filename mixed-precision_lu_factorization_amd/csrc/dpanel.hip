@@ -310,13 +310,7 @@ int launch_dgetf2_npv_piece(mpf_ctx *c, double *P, int64_t ld, int rows, int col
     if (np == 0 || piece < 0 || piece >= np || cols > rows) { c->err = "dgetf2_npv_piece: shape not covered"; return -1; }
     int *info = &c->ws->info;
     const int ntiles = np;
-    if (ntiles > c->dtiles_cap) {
-        if (c->dtiles) (void)hipFree(c->dtiles);
-        c->dtiles = nullptr; c->dtiles_cap = 0;
-        const int cap = ntiles < 8 ? 8 : ntiles;
-        MPF_HIP_TRY(c, hipMalloc((void **)&c->dtiles, (size_t)cap * DP_IB * DP_IB * sizeof(double)));
-        c->dtiles_cap = cap;
-    }
+    MPF_HIP_TRY(c, c->dtiles.grow((int64_t)(ntiles < 8 ? 8 : ntiles) * DP_IB * DP_IB));
     if (piece == 0) {
         const int gb0 = (int)(((long long)rows - DP_IB + 255) / 256);
         if (fused) dpanel_sub_kernel<true, true><<<1 + gb0, 256, 0, c->stream>>>(P, ld, rows, cols, 0, DP_IB, info, info_base, c->dtiles);
@@ -337,7 +331,7 @@ int launch_dgetf2_npv_piece(mpf_ctx *c, double *P, int64_t ld, int rows, int col
 // leading dimension ld).  Until the last piece the matrix itself still holds the UNfactored tile (see dpanel_sub above): whoever
 // copies a finished sub-panel out of the matrix before then (mpf_factor_dist's message instalments) takes the tile from here.
 int launch_dpanel_tile_copy(mpf_ctx *c, double *dst, int64_t ld, int piece) {
-    if (!c->dtiles || piece < 0 || piece >= c->dtiles_cap) { c->err = "dpanel tile copy: no such parked tile"; return -1; }
+    if (!c->dtiles || piece < 0 || piece >= c->dtiles.cap() / (DP_IB * DP_IB)) { c->err = "dpanel tile copy: no such parked tile"; return -1; }
     dpanel_tiles_store_kernel<<<1, 256, 0, c->stream>>>(dst, ld, DP_IB, c->dtiles + (size_t)piece * DP_IB * DP_IB);
     MPF_HIP_TRY(c, hipGetLastError());
     return 0;
@@ -348,13 +342,7 @@ int launch_dgetf2_npv(mpf_ctx *c, double *P, int64_t ld, int rows, int cols, int
     if (cols > rows) { c->err = "dgetf2_npv: cols > rows"; return -1; }
     int *info = &c->ws->info;
     const int ntiles = (cols + DP_IB - 1) / DP_IB;
-    if (ntiles > c->dtiles_cap) {
-        if (c->dtiles) hipFree(c->dtiles);
-        c->dtiles = nullptr; c->dtiles_cap = 0;
-        const int cap = ntiles < 8 ? 8 : ntiles;
-        MPF_HIP_TRY(c, hipMalloc((void **)&c->dtiles, (size_t)cap * DP_IB * DP_IB * sizeof(double)));
-        c->dtiles_cap = cap;
-    }
+    MPF_HIP_TRY(c, c->dtiles.grow((int64_t)(ntiles < 8 ? 8 : ntiles) * DP_IB * DP_IB));
     const int fused_form = c->tune.dpanel_fused_form;
     if (fused_form && cols % DP_IB == 0 && cols >= 2 * DP_IB) {
         // sub-panel 0 as below (its U row-block solve covers all columns right of it), then one fused launch per sub-panel

@@ -1085,7 +1085,7 @@ int launch_hgetf2(mpf_ctx *c, const double *A64, int64_t lda, uint16_t *P16, int
     a.seq = c->hp_seq;
     a.signal = (c->tune.gate_wait_value && c->hp_signal) ? c->hp_signal : nullptr;
     a.moved = moved;
-    const bool own_list = moved && c->lists && moved >= c->lists && moved < c->lists + c->lists_cap;
+    const bool own_list = moved && c->lists && moved >= c->lists && moved < c->lists + c->lists.cap();
     if (moved && !own_list) MPF_HIP_TRY(c, hipMemsetAsync(&moved->n, 0, sizeof(int), c->stream));
     // single-XCD form: the slabs + the waiters' share of one XCD's CUs must fit that XCD
     const int per_xcd = c->num_cus / 8;

@@ -211,24 +211,13 @@ int launch_hgetf2_generic(mpf_ctx *c, const double *A64, int64_t lda, uint16_t *
     if (P16) { W = P16; ldw = ld16; }
     else if (out16) { W = out16; ldw = ldo; }
     else {
-        const size_t need = (size_t)rows * (size_t)cols;
-        if (need > c->g16_cap) {
-            if (c->g16) hipFree(c->g16);
-            c->g16 = nullptr; c->g16_cap = 0;
-            MPF_HIP_TRY(c, hipMalloc((void **)&c->g16, need * sizeof(unsigned short)));
-            c->g16_cap = need;
-        }
+        MPF_HIP_TRY(c, c->g16.grow((int64_t)rows * cols));
         W = c->g16; ldw = rows;
     }
     const int nblk0 = (rows + GP_T - 1) / GP_T;
     // block maxima + the two side rows of the interchange (cols fp16 each) + the pivot row index, in one allocation
     const int need_u64 = nblk0 + (2 * cols + 2) / 4 + 4;
-    if (need_u64 > c->gcand_cap) {
-        if (c->gcand) hipFree(c->gcand);
-        c->gcand = nullptr; c->gcand_cap = 0;
-        MPF_HIP_TRY(c, hipMalloc((void **)&c->gcand, (size_t)need_u64 * sizeof(unsigned long long)));
-        c->gcand_cap = need_u64;
-    }
+    MPF_HIP_TRY(c, c->gcand.grow(need_u64));
     if (A64) {
         dim3 g((unsigned)nblk0, (unsigned)cols);
         gp_convert_kernel<<<g, GP_T, 0, c->stream>>>(A64, lda, W, ldw, rows);

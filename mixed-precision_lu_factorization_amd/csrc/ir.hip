@@ -190,12 +190,7 @@ __global__ void scal_kernel(double alpha, double *x, long long n) {
 int launch_dot(mpf_ctx *c, const double *x, const double *y, int64_t n, double *d_out) {
     int blocks = (int)((n + 255) / 256);
     if (blocks > 1024) blocks = 1024;
-    if (1024 > (int)c->res_part_cap) {
-        if (c->res_part) hipFree(c->res_part);
-        c->res_part = nullptr; c->res_part_cap = 0;
-        MPF_HIP_TRY(c, hipMalloc((void **)&c->res_part, 1024 * sizeof(double)));
-        c->res_part_cap = 1024;
-    }
+    MPF_HIP_TRY(c, c->res_part.grow(1024));
     dot_kernel<<<blocks, 256, 0, c->stream>>>(x, y, n, c->res_part);
     sumsq_final_kernel<<<1, 64, 0, c->stream>>>(c->res_part, blocks, d_out);
     MPF_HIP_TRY(c, hipGetLastError());
@@ -215,13 +210,7 @@ int launch_gather_rows(mpf_ctx *c, const double *in, const int *perm, double *ou
 // r = (b or 0) - A[:, 0:ncols] x[0:ncols], A n x ncols (the distributed residual: a rank's own columns; b on one rank only)
 int launch_residual_rect(mpf_ctx *c, const double *A, int64_t lda, const double *x, const double *b, double *r, int64_t n, int64_t ncols) {
     const int nchunks = (int)((ncols + RS_CCH - 1) / RS_CCH);
-    const size_t need = (size_t)(nchunks > 0 ? nchunks : 1) * (size_t)n;
-    if (need > c->res_part_cap) {
-        if (c->res_part) hipFree(c->res_part);
-        c->res_part = nullptr; c->res_part_cap = 0;
-        MPF_HIP_TRY(c, hipMalloc((void **)&c->res_part, need * sizeof(double)));
-        c->res_part_cap = need;
-    }
+    MPF_HIP_TRY(c, c->res_part.grow((int64_t)(nchunks > 0 ? nchunks : 1) * n));
     if (nchunks > 0) {
         dim3 grid((unsigned)((n + 255) / 256), (unsigned)nchunks);
         residual_kernel<<<grid, 256, 0, c->stream>>>(A, lda, x, c->res_part, n, ncols);
@@ -456,12 +445,7 @@ int launch_axpy(mpf_ctx *c, double alpha, const double *x, double *y, int64_t n)
 int launch_norm2(mpf_ctx *c, const double *x, int64_t n, double *d_out) {
     int blocks = (int)((n + 255) / 256);
     if (blocks > 1024) blocks = 1024;
-    if (1024 > (int)c->res_part_cap) { // the residual's partial-sum buffer doubles as scratch here
-        if (c->res_part) hipFree(c->res_part);
-        c->res_part = nullptr; c->res_part_cap = 0;
-        MPF_HIP_TRY(c, hipMalloc((void **)&c->res_part, 1024 * sizeof(double)));
-        c->res_part_cap = 1024;
-    }
+    MPF_HIP_TRY(c, c->res_part.grow(1024));   // the residual's partial-sum buffer doubles as scratch here
     sumsq_kernel<<<blocks, 256, 0, c->stream>>>(x, n, c->res_part);
     sumsq_final_kernel<<<1, 64, 0, c->stream>>>(c->res_part, blocks, d_out);
     MPF_HIP_TRY(c, hipGetLastError());

@@ -286,10 +286,10 @@ __global__ __launch_bounds__(256) void wt_rows_scatter_kernel(T_ *__restrict__ W
 // W = the copy's element (row 0, first column of the range); scratch = c->perm_tmp (N x nb doubles >= 2 nb rows x N floats)
 int launch_laswp_from_list_f32(mpf_ctx *c, float *W, int64_t ldw, int64_t ncols, const MovedList *ml) {
     if (ncols < 1) return 0;
-    if (!c->perm_tmp || (size_t)c->perm_cap * sizeof(double) < (size_t)LASWP_MAXMOVED * (size_t)ncols * sizeof(float)) {
+    if (!c->perm_tmp || (size_t)c->perm_tmp.cap() * sizeof(double) < (size_t)LASWP_MAXMOVED * (size_t)ncols * sizeof(float)) {
         c->err = "laswp (fp32 copy): scratch too small"; return -1;
     }
-    float *T = (float *)c->perm_tmp;
+    float *T = (float *)c->perm_tmp.get();
     dim3 grid((unsigned)((ncols + 1023) / 1024), LASWP_MAXMOVED);
     wt_rows_gather_kernel<float><<<grid, 256, 0, c->stream>>>(W, ldw, ncols, ml, T);
     wt_rows_scatter_kernel<float><<<grid, 256, 0, c->stream>>>(W, ldw, ncols, ml, T);
@@ -302,7 +302,7 @@ int launch_laswp_from_list_f32(mpf_ctx *c, float *W, int64_t ldw, int64_t ncols,
 // at the same time: each gets its own part of the scratch)
 int launch_laswp_from_list_rm64(mpf_ctx *c, double *R, int64_t ldr, int64_t ncols, const MovedList *ml, int64_t scratch_off) {
     if (ncols < 1) return 0;
-    if (!c->rm_tmp || scratch_off < 0 || c->rm_tmp_cap < scratch_off + (int64_t)LASWP_MAXMOVED * ncols) {
+    if (!c->rm_tmp || scratch_off < 0 || c->rm_tmp.cap() < scratch_off + (int64_t)LASWP_MAXMOVED * ncols) {
         c->err = "laswp (fp64 row-major copy): scratch too small"; return -1;
     }
     double *T = c->rm_tmp + scratch_off;

@@ -107,15 +107,14 @@ extern "C" int mpf_matgen_cols_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t
         poly_mulmod(p, step, tmp);
         memcpy(p, tmp, sizeof tmp);
     }
-    uint32_t *d_states = nullptr;
-    MPF_HIP_TRY(c, hipMalloc((void **)&d_states, states.size() * sizeof(uint32_t)));
+    Buf<uint32_t> d_states;
+    MPF_HIP_TRY(c, d_states.grow((int64_t)states.size()));
     hipError_t e = hipMemcpyAsync(d_states, states.data(), states.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         matgen_cols_kernel<<<(unsigned)((ncols + 63) / 64), 64, 0, c->stream>>>(d_A, lda, N, ncols, d_states);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // `states` (host) and d_states must outlive the copy / kernel
-    hipFree(d_states);
     if (e != hipSuccess) { c->err = std::string("matgen: ") + hipGetErrorString(e); return -2; }
     return 0;
 }

@@ -122,12 +122,9 @@ constexpr int PANEL_PAD = 16;   // doubles = 128 bytes = 32 int32 pivots
 size_t panel_buf_bytes(int64_t N, int nb) { return (size_t)(N + PANEL_PAD) * nb * 8 + sizeof(MovedList); }
 
 int ensure_dist_bufs(mpf_ctx *c, int64_t N, int nb) {
-    const size_t need = panel_buf_bytes(N, nb);
-    if (c->dist_buf[0] && c->dist_buf_cap >= need) return 0;
-    for (auto *&b : c->dist_buf) { if (b) hipFree(b); b = nullptr; }
-    c->dist_buf_cap = 0;
-    for (auto *&b : c->dist_buf) MPF_HIP_TRY(c, hipMalloc((void **)&b, need));
-    c->dist_buf_cap = need;
+    static_assert(sizeof(MovedList) % sizeof(double) == 0, "a panel message is a whole number of doubles");
+    const int64_t need = (int64_t)(panel_buf_bytes(N, nb) / sizeof(double));
+    for (auto &b : c->dist_buf) MPF_HIP_TRY(c, b.grow(need));
     return 0;
 }
 
@@ -243,15 +240,15 @@ int mpf_rccl_selftest(mpf_ctx *c) {
     if (!c) return -1;
     if (!c->rccl_comm) { c->err = "RCCL communicator not initialised (mpf_rccl_init)"; return -5; }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    double *d = nullptr, h[4] = {1.0 + c->rccl_rank, 2.0, 3.0, 4.0}, back[4] = {0, 0, 0, 0};
-    MPF_HIP_TRY(c, hipMalloc((void **)&d, sizeof h));
+    double h[4] = {1.0 + c->rccl_rank, 2.0, 3.0, 4.0}, back[4] = {0, 0, 0, 0};
+    Buf<double> d;
+    MPF_HIP_TRY(c, d.grow(4));
     int rc = 0;
     if (hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = -2;
     if (!rc) rc = rccl_bcast(c, d, sizeof h, 0, c->stream);
     if (!rc) rc = rccl_allreduce(c, d, 4, c->stream);
     if (!rc && hipMemcpyAsync(back, d, sizeof h, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = -2;
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = -2;
-    hipFree(d);
     if (rc) return rc;
     const double w = (double)c->rccl_world;
     if (back[0] != 1.0 * w || back[1] != 2.0 * w || back[3] != 4.0 * w) { c->err = "RCCL self-test: wrong values"; return -5; }
@@ -298,8 +295,8 @@ int mpf_rccl_bcast_probe(mpf_ctx *c, int64_t bytes, int32_t root, int32_t reps, 
     if (!c || !ms_per_bcast || bytes <= 0 || reps <= 0) return -1;
     if (!c->rccl_comm) { c->err = "RCCL communicator not initialised (mpf_rccl_init)"; return -5; }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    void *d = nullptr;
-    MPF_HIP_TRY(c, hipMalloc(&d, (size_t)bytes));
+    Buf<char> d;
+    MPF_HIP_TRY(c, d.grow(bytes));
     hipMemsetAsync(d, 0, (size_t)bytes, c->stream);
     const long long calls0 = c->rccl_bcast_calls, bytes0 = c->rccl_bcast_bytes;
     int rc = rccl_bcast(c, d, bytes, root, c->stream);   // warm-up (connection set-up)
@@ -311,7 +308,6 @@ int mpf_rccl_bcast_probe(mpf_ctx *c, int64_t bytes, int32_t root, int32_t reps, 
     hipEventElapsedTime(&ms, c->ev0, c->ev1);
     *ms_per_bcast = ms / reps;
     c->rccl_bcast_calls = calls0; c->rccl_bcast_bytes = bytes0;   // (the probe is not part of a factorization's traffic)
-    hipFree(d);
     return rc;
 }
 
@@ -401,18 +397,8 @@ int mpf_factor_dist(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_
     }
     if (sb > 1) {
         const int64_t wneed = N * (lcols > 0 ? lcols : 1), sneed = N * sbw;
-        if (c->dist_w32_cap < wneed) {
-            if (c->dist_w32) hipFree(c->dist_w32);
-            c->dist_w32 = nullptr; c->dist_w32_cap = 0;
-            MPF_HIP_TRY(c, hipMalloc((void **)&c->dist_w32, (size_t)wneed * sizeof(float)));
-            c->dist_w32_cap = wneed;
-        }
-        if (c->dist_spl_cap < sneed) {
-            if (c->dist_spl) hipFree(c->dist_spl);
-            c->dist_spl = nullptr; c->dist_spl_cap = 0;
-            MPF_HIP_TRY(c, hipMalloc((void **)&c->dist_spl, (size_t)sneed * sizeof(double)));
-            c->dist_spl_cap = sneed;
-        }
+        MPF_HIP_TRY(c, c->dist_w32.grow(wneed));
+        MPF_HIP_TRY(c, c->dist_spl.grow(sneed));
     }
     if (!c->xstream && dist->world > 1 && c->tune.dist_instalments) {   // exchange stream of the panel's instalments
         int lo = 0, hi = 0;
@@ -435,7 +421,7 @@ int mpf_factor_dist(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_
                              two_ ? 1 : 0, 0, 0};
         for (int i = 0; i < 8; ++i) agreed[i] = mine[i];
         if (dist->world > 1) {
-            long long *dv = (long long *)c->dist_buf[0];   // (free until the first panel message)
+            long long *dv = (long long *)c->dist_buf[0].get();   // (free until the first panel message)
             for (int root = 0; root < dist->world; ++root) {
                 if (root == dist->rank) MPF_HIP_TRY(c, hipMemcpyAsync(dv, mine, sizeof mine, hipMemcpyHostToDevice, c->stream));
                 const int e = bcast_fn(user, dv, (int64_t)sizeof mine, root, (void *)c->stream);
@@ -458,34 +444,8 @@ int mpf_factor_dist(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_
                     mpf_ensure_rowmajor_copy(c, N, lcols, nb) == 0;
     double *Rl = rm ? c->r64 : nullptr;
     const int64_t ldr = lcols > 0 ? lcols : 1;
-    {   // per-panel moved-row lists + scratch of the deferred left-hand interchanges (as mpf_factor_dev)
-        const int npanels = L.nblocks;
-        if (npanels > c->lists_cap) {
-            if (c->lists) hipFree(c->lists);
-            c->lists = nullptr; c->lists_cap = 0;
-            MPF_HIP_TRY(c, hipMalloc((void **)&c->lists, (size_t)npanels * sizeof(MovedList)));
-            c->lists_cap = npanels;
-        }
-        // N x nb doubles for the deferred left-hand interchanges; at least N x 256 so that the scratch also holds the
-        // 2 * HP_MAXCOLS moved rows x local columns (fp32) of an interchange on the row-major working copy
-        const int64_t pneed = N * (int64_t)(nb > HP_MAXCOLS ? nb : HP_MAXCOLS);
-        if (pneed > c->perm_cap) {
-            if (c->perm_tmp) hipFree(c->perm_tmp);
-            c->perm_tmp = nullptr; c->perm_cap = 0;
-            MPF_HIP_TRY(c, hipMalloc((void **)&c->perm_tmp, (size_t)pneed * sizeof(double)));
-            c->perm_cap = pneed;
-        }
-        if (N > c->fmap_cap) {
-            if (c->Fmap) hipFree(c->Fmap);
-            c->Fmap = nullptr; c->fmap_cap = 0;
-            MPF_HIP_TRY(c, hipMalloc((void **)&c->Fmap, (size_t)2 * N * sizeof(int)));   // the map and its inverse
-            c->fmap_cap = N;
-        }
-        MPF_HIP_TRY(c, hipMemsetAsync(c->lists, 0, (size_t)npanels * sizeof(MovedList), c->stream));
-    }
-    const int imax = INT_MAX;
-    MPF_HIP_TRY(c, hipMemcpyAsync(&c->ws->info, &imax, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    MPF_HIP_TRY(c, hipMemsetAsync(&c->ws->hp_timeouts, 0, sizeof(int), c->stream));
+    rc = mpf_factor_setup(c, N, nb, L.nblocks, true);   // per-panel moved-row lists + scratch of the deferred left-hand interchanges
+    if (rc) return rc;
     mpf_stats st{};
     st.n = N; st.nb = nb; st.superpanel = sb;
     hipStream_t S = c->stream, P = (o.no_lookahead || !c->pstream) ? c->stream : c->pstream;
@@ -495,7 +455,7 @@ int mpf_factor_dist(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_
     MPF_HIP_TRY(c, hipEventRecord(c->ev0, S));
     if (two) { hipEvent_t e = ev.get(); hipEventRecord(e, S); hipStreamWaitEvent(P, e, 0); }
 
-    auto buf_of = [&](int b) { return (char *)c->dist_buf[b & 1]; };
+    auto buf_of = [&](int b) { return (char *)c->dist_buf[b & 1].get(); };
     auto rows_of = [&](int b) { return N - (int64_t)b * nb; };
     auto ldp_of = [&](int b) { return rows_of(b) + PANEL_PAD; };
     auto list_off = [&](int b) { return (size_t)ldp_of(b) * L.width(b) * 8; };

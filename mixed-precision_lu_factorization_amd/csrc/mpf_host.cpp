@@ -140,36 +140,9 @@ int mpf_destroy(mpf_ctx *c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->ws) hipFree(c->ws);
     if (c->hp_signal) hipFree(c->hp_signal);
-    if (c->solve_buf) hipFree(c->solve_buf);
-    if (c->perm_buf) hipFree(c->perm_buf);
-    if (c->trsv_inv) hipFree(c->trsv_inv);
-    if (c->trsv_inv256) hipFree(c->trsv_inv256);
-    if (c->trsv_cnt) hipFree(c->trsv_cnt);
-    if (c->res_part) hipFree(c->res_part);
-    if (c->krylov) hipFree(c->krylov);
     mpf_rccl_destroy(c);
-    for (auto *b : c->dist_buf) if (b) hipFree(b);
-    if (c->dist_w32) hipFree(c->dist_w32);
-    if (c->dist_spl) hipFree(c->dist_spl);
-    if (c->dtiles) hipFree(c->dtiles);
-    if (c->w32) hipFree(c->w32);
-    if (c->r64) hipFree(c->r64);
-    if (c->host_A) hipFree(c->host_A);
-    if (c->host_P) hipFree(c->host_P);
-    if (c->host_A0) hipFree(c->host_A0);
     sink_destroy(c);
     feed_destroy(c);
-    if (c->late_flags) hipHostFree(c->late_flags);
-    if (c->rm_tmp) hipFree(c->rm_tmp);
-    if (c->rm_lt) hipFree(c->rm_lt);
-    if (c->g16) hipFree(c->g16);
-    if (c->gcand) hipFree(c->gcand);
-    if (c->lists) hipFree(c->lists);
-    if (c->Fmap) hipFree(c->Fmap);
-    if (c->perm_tmp) hipFree(c->perm_tmp);
-    if (c->h_L) hipFree(c->h_L);
-    if (c->h_U) hipFree(c->h_U);
-    for (auto *b : c->h_Lb) if (b) hipFree(b);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     if (c->pstream) { hipStreamSynchronize(c->pstream); hipStreamDestroy(c->pstream); }
@@ -177,7 +150,7 @@ int mpf_destroy(mpf_ctx *c) {
     if (c->xstream) { hipStreamSynchronize(c->xstream); hipStreamDestroy(c->xstream); }
     for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // (the scratch buffers go with it, every stream synchronised)
     return 0;
 }
 
@@ -332,14 +305,13 @@ int mpf_ensure_h_images(mpf_ctx *c, int64_t rows, int kmax, bool big) {
     if (rows < c->h_rows) rows = c->h_rows;
     if (kmax < c->h_kmax) kmax = c->h_kmax;
     big = big || c->h_Lb[0];
-    if (c->h_L) hipFree(c->h_L);
-    if (c->h_U) hipFree(c->h_U);
-    for (auto *&b : c->h_Lb) { if (b) hipFree(b); b = nullptr; }
-    c->h_L = c->h_U = nullptr; c->h_rows = 0; c->h_kmax = 0;
-    const size_t bytes = 2 * (size_t)rows * kmax * sizeof(unsigned short); // hi image, then lo image (split mode)
-    MPF_HIP_TRY(c, hipMalloc((void **)&c->h_L, bytes));
-    MPF_HIP_TRY(c, hipMalloc((void **)&c->h_U, bytes));
-    if (big) for (auto *&b : c->h_Lb) MPF_HIP_TRY(c, hipMalloc((void **)&b, bytes));
+    c->h_L.release(); c->h_U.release();
+    for (auto &b : c->h_Lb) b.release();
+    c->h_rows = 0; c->h_kmax = 0;
+    const int64_t elems = 2 * rows * kmax; // hi image, then lo image (split mode)
+    MPF_HIP_TRY(c, c->h_L.grow(elems));
+    MPF_HIP_TRY(c, c->h_U.grow(elems));
+    if (big) for (auto &b : c->h_Lb) MPF_HIP_TRY(c, b.grow(elems));
     c->h_rows = rows; c->h_kmax = kmax;
     return 0;
 }
@@ -385,12 +357,9 @@ int mpf_w32_laswp(mpf_ctx *c, float *d_W, int64_t ldw, int64_t ncols, int32_t k,
     if (cols < 1 || cols > HP_MAXCOLS) return fail(c, -1, "w32_laswp: 1 <= cols <= 256");
     if (ldw < ncols) return fail(c, -1, "w32_laswp: ldw < ncols");
     const int64_t need = (int64_t)LASWP_MAXMOVED * ncols / 2 + 1;    // doubles: 2 * HP_MAXCOLS moved rows x ncols floats
-    if (need > c->perm_cap) {
+    if (need > c->perm_tmp.cap()) {
         MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->perm_tmp) hipFree(c->perm_tmp);
-        c->perm_tmp = nullptr; c->perm_cap = 0;
-        MPF_HIP_TRY(c, hipMalloc((void **)&c->perm_tmp, (size_t)need * sizeof(double)));
-        c->perm_cap = need;
+        MPF_HIP_TRY(c, c->perm_tmp.grow(need));
     }
     int rc = launch_laswp_plan(c, d_ipiv, k, cols, &c->ws->list0);
     if (!rc) rc = launch_laswp_from_list_f32(c, d_W, ldw, ncols, &c->ws->list0);
@@ -1034,12 +1003,7 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
     float *W = nullptr;
     const int64_t ldw = N;
     if (use32) {
-        if (c->w32_n < N) {
-            if (c->w32) (void)hipFree(c->w32);
-            c->w32 = nullptr; c->w32_n = 0;
-            MPF_HIP_TRY(c, hipMalloc((void **)&c->w32, (size_t)N * (size_t)N * sizeof(float)));
-            c->w32_n = N;
-        }
+        MPF_HIP_TRY(c, c->w32.grow(N * N));
         W = c->w32;
     }
     if (overlap) {
@@ -1272,25 +1236,28 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
 // panel's row-major L21 (N x nb).  Returns non-zero (and leaves the context usable) when the device has no room: the caller
 // then runs the in-place schedule.
 int mpf_ensure_rowmajor_copy(mpf_ctx *c, int64_t N, int64_t cols, int32_t nb) {   // N rows x cols columns (mpf_factor_dist: the local columns)
-    auto grow = [&](double *&p, int64_t &cap, int64_t need) -> int {
-        if (p && cap >= need) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc((void **)&p, (size_t)need * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return 1; }
-        cap = need;
-        return 0;
-    };
-    const int bad = grow(c->r64, c->r64_cap, N * cols) || grow(c->rm_tmp, c->rm_tmp_cap, (int64_t)LASWP_MAXMOVED * cols) ||
-                    grow(c->rm_lt, c->rm_lt_cap, 3 * N * (int64_t)nb);   // two L21 images: panel k + 1's is written while update k still reads; the third: the replay on late column segments (LatePlan)
+    const bool bad = c->r64.grow(N * cols) || c->rm_tmp.grow((int64_t)LASWP_MAXMOVED * cols) ||
+                     c->rm_lt.grow(3 * N * (int64_t)nb);   // two L21 images: panel k + 1's is written while update k still reads; the third: the replay on late column segments (LatePlan)
     if (bad) {   // no room: the in-place schedule runs, and nothing of this one stays resident
-        if (c->r64) (void)hipFree(c->r64);
-        if (c->rm_tmp) (void)hipFree(c->rm_tmp);
-        if (c->rm_lt) (void)hipFree(c->rm_lt);
-        c->r64 = c->rm_tmp = c->rm_lt = nullptr;
-        c->r64_cap = c->rm_tmp_cap = c->rm_lt_cap = 0; c->r64_n = 0;
+        (void)hipGetLastError();
+        c->r64.release(); c->rm_tmp.release(); c->rm_lt.release();
         return 1;
     }
-    c->r64_n = N;
+    return 0;
+}
+
+int mpf_factor_setup(mpf_ctx *c, int64_t N, int32_t nb, int32_t npanels, bool lists) {
+    if (lists) {
+        MPF_HIP_TRY(c, c->lists.grow(npanels));
+        // N x nb doubles for the deferred left-hand interchanges; at least N x 256 so that the scratch also holds the
+        // 2 * HP_MAXCOLS moved rows x N (or a rank's local) columns (fp32) of an interchange on the row-major working copy
+        MPF_HIP_TRY(c, c->perm_tmp.grow(N * (int64_t)(nb > HP_MAXCOLS ? nb : HP_MAXCOLS)));
+        MPF_HIP_TRY(c, c->Fmap.grow(2 * N));   // the map and its inverse
+        MPF_HIP_TRY(c, hipMemsetAsync(c->lists, 0, (size_t)npanels * sizeof(MovedList), c->stream));
+    }
+    const int imax = INT_MAX;
+    MPF_HIP_TRY(c, hipMemcpyAsync(&c->ws->info, &imax, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    MPF_HIP_TRY(c, hipMemsetAsync(&c->ws->hp_timeouts, 0, sizeof(int), c->stream));
     return 0;
 }
 
@@ -1317,34 +1284,7 @@ int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, 
         const int64_t kimg = (int64_t)sb * nb < 8 * HP_MAXCOLS ? (int64_t)sb * nb : 8 * HP_MAXCOLS; // the generic schedule cuts K to the images
         int e = mpf_ensure_h_images(c, N + HP_MAXCOLS + 64, (int)kimg, sb > 1); if (e) return e;   // + room for the block-row L images
     }
-    if (!generic) {   // per-panel moved-row lists + scratch of the deferred left-hand interchanges
-        const int npanels = (int)((N + nb - 1) / nb);
-        if (npanels > c->lists_cap) {
-            if (c->lists) hipFree(c->lists);
-            c->lists = nullptr; c->lists_cap = 0;
-            MPF_HIP_TRY(c, hipMalloc((void **)&c->lists, (size_t)npanels * sizeof(MovedList)));
-            c->lists_cap = npanels;
-        }
-        // N x nb doubles for the deferred left-hand interchanges; at least N x 256 so that the scratch also holds the
-        // 2 * HP_MAXCOLS moved rows x N columns (fp32) of an interchange on the row-major working copy
-        const int64_t pneed = N * (int64_t)(nb > HP_MAXCOLS ? nb : HP_MAXCOLS);
-        if (pneed > c->perm_cap) {
-            if (c->perm_tmp) hipFree(c->perm_tmp);
-            c->perm_tmp = nullptr; c->perm_cap = 0;
-            MPF_HIP_TRY(c, hipMalloc((void **)&c->perm_tmp, (size_t)pneed * sizeof(double)));
-            c->perm_cap = pneed;
-        }
-        if (N > c->fmap_cap) {
-            if (c->Fmap) hipFree(c->Fmap);
-            c->Fmap = nullptr; c->fmap_cap = 0;
-            MPF_HIP_TRY(c, hipMalloc((void **)&c->Fmap, (size_t)2 * N * sizeof(int)));   // the map and its inverse
-            c->fmap_cap = N;
-        }
-        MPF_HIP_TRY(c, hipMemsetAsync(c->lists, 0, (size_t)npanels * sizeof(MovedList), c->stream));
-    }
-    const int imax = INT_MAX;
-    MPF_HIP_TRY(c, hipMemcpyAsync(&c->ws->info, &imax, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    MPF_HIP_TRY(c, hipMemsetAsync(&c->ws->hp_timeouts, 0, sizeof(int), c->stream));
+    { const int e = mpf_factor_setup(c, N, nb, (int)((N + nb - 1) / nb), !generic); if (e) return e; }
     mpf_stats st{};
     st.n = N; st.nb = nb; st.superpanel = sb;
     const bool lookahead = !o.sync_timing && !o.no_lookahead && !c->tune.no_lookahead && c->pstream != nullptr;
@@ -1393,19 +1333,8 @@ int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, 
 // frees them inside every MPF() call (MPF.cu:80-94,250-255), which at N = 32768 cost 275 ms of a 1037-ms call here;
 // benchmark.cpp:181-266 calls MPF() once per matrix of a file.  mpf_trim() gives the memory back.
 static int ensure_host_copies(mpf_ctx *c, int64_t N) {
-    const int64_t abytes = N * N * (int64_t)sizeof(double), pbytes = N * (int64_t)sizeof(int32_t); // 64-bit: the reference overflows int here (MPF.cu:81)
-    if (c->host_A_cap < abytes) {
-        if (c->host_A) (void)hipFree(c->host_A);
-        c->host_A = nullptr; c->host_A_cap = 0;
-        MPF_HIP_TRY(c, hipMalloc((void **)&c->host_A, (size_t)abytes));
-        c->host_A_cap = abytes;
-    }
-    if (c->host_P_cap < pbytes) {
-        if (c->host_P) (void)hipFree(c->host_P);
-        c->host_P = nullptr; c->host_P_cap = 0;
-        MPF_HIP_TRY(c, hipMalloc((void **)&c->host_P, (size_t)pbytes));
-        c->host_P_cap = pbytes;
-    }
+    MPF_HIP_TRY(c, c->host_A.grow(N * N));   // 64-bit: the reference overflows int here (MPF.cu:81)
+    MPF_HIP_TRY(c, c->host_P.grow(N));
     return 0;
 }
 
@@ -1413,12 +1342,11 @@ int mpf_trim(mpf_ctx *c) {
     if (!c) return -1;
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    auto drop = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
-    drop(c->host_A); drop(c->host_P); drop(c->host_A0); c->host_A_cap = c->host_P_cap = c->host_A0_cap = 0;
+    c->host_A.release(); c->host_P.release(); c->host_A0.release();
     sink_trim(c);
     feed_trim(c);
-    drop(c->r64); drop(c->rm_tmp); drop(c->rm_lt); c->r64_cap = c->rm_tmp_cap = c->rm_lt_cap = 0; c->r64_n = 0;
-    drop(c->w32); c->w32_n = 0;
+    c->r64.release(); c->rm_tmp.release(); c->rm_lt.release();
+    c->w32.release();
     return 0;
 }
 
@@ -1438,12 +1366,8 @@ int mpf_factor_host(mpf_ctx *c, double *A_host, int64_t N, int32_t nb, int32_t *
                            !(opts && opts->trailing != MPF_TRAIL_FP64) && !(opts && opts->pivot_path == 1);
     bool armed = false;
     if (want_sink) {
-        if (c->host_A0_cap < (int64_t)(bytes + pbytes)) {
-            if (c->host_A0) (void)hipFree(c->host_A0);
-            c->host_A0 = nullptr; c->host_A0_cap = 0;
-            if (hipMalloc((void **)&c->host_A0, bytes + pbytes) == hipSuccess) c->host_A0_cap = (int64_t)(bytes + pbytes);
-            else (void)hipGetLastError();   // (no room for the snapshot: the plain way)
-        }
+        if (c->host_A0.grow((int64_t)((bytes + pbytes + sizeof(double) - 1) / sizeof(double))) != hipSuccess)   // A, then P
+            (void)hipGetLastError();   // (no room for the snapshot: the plain way)
         if (c->host_A0) {
             const int e = sink_attach(c, A_host, N, nb);
             if (e < 0) return e;
@@ -1458,7 +1382,10 @@ int mpf_factor_host(mpf_ctx *c, double *A_host, int64_t N, int32_t nb, int32_t *
     int parts = c->tune.host_late_parts;
     if (!want_sink || !c->tune.fp64_rowmajor || N < c->tune.fp64_rowmajor_min_n || N < c->tune.host_late_min_n || npan < 32 || c->tune.no_lookahead || safe_pivots(c) ||
         !hgetf2_lds_eligible(c, (int)N, (int)nb) || c->tune.superpanel_fp64 > 1 || (opts && opts->superpanel > 1)) parts = 0;
-    if (parts > 0 && !c->late_flags && hipHostMalloc((void **)&c->late_flags, 64) != hipSuccess) { (void)hipGetLastError(); parts = 0; }
+    if (parts > 0 && !c->late_flags) {
+        if (c->late_flags.grow(16) != hipSuccess) { (void)hipGetLastError(); parts = 0; }
+        else memset(c->late_flags, 0, 16 * sizeof(unsigned));
+    }
     if (parts > 0 && mpf_ensure_rowmajor_copy(c, N, N, nb) != 0) parts = 0;
     if (parts > 0) {
         // first part: host_first_pct of the columns; the late segments share the rest equally; when a segment is due is decided below,
@@ -1522,7 +1449,7 @@ int mpf_factor_host(mpf_ctx *c, double *A_host, int64_t N, int32_t nb, int32_t *
     }
     if (armed) {
         hipMemcpyAsync(c->host_A0, dA, up_bytes, hipMemcpyDeviceToDevice, c->stream);
-        hipMemcpyAsync((char *)c->host_A0 + bytes, dP, pbytes, hipMemcpyDeviceToDevice, c->stream);
+        hipMemcpyAsync((char *)c->host_A0.get() + bytes, dP, pbytes, hipMemcpyDeviceToDevice, c->stream);
     }
     if (plan.nseg) {
         const int e = feed_start(c, A_host, dA, N, &plan);
@@ -1560,7 +1487,7 @@ int mpf_factor_host(mpf_ctx *c, double *A_host, int64_t N, int32_t nb, int32_t *
         const std::string why = c->err;
         std::cerr << "mpf_factor_host: " << why << " -- " << sent << " block rows had left already; repeating on the generic pivot path from the uploaded matrix" << std::endl;
         hipMemcpyAsync(dA, c->host_A0, bytes, hipMemcpyDeviceToDevice, c->stream);
-        hipMemcpyAsync(dP, (char *)c->host_A0 + bytes, pbytes, hipMemcpyDeviceToDevice, c->stream);
+        hipMemcpyAsync(dP, (char *)c->host_A0.get() + bytes, pbytes, hipMemcpyDeviceToDevice, c->stream);
         mpf_opts o2{};
         if (opts) o2 = *opts;
         o2.pivot_path = 1;
@@ -1606,17 +1533,13 @@ int64_t mpf_hgetf2_capacity_rows(mpf_ctx *c, int32_t waiters, int32_t form) {
 
 int mpf_ensure_solve_buf(mpf_ctx *c, int64_t n) {
     if (c->solve_n >= n && c->solve_buf) return 0;
-    if (c->solve_buf) hipFree(c->solve_buf);
-    if (c->perm_buf) hipFree(c->perm_buf);
-    if (c->trsv_inv) hipFree(c->trsv_inv);
-    if (c->trsv_inv256) hipFree(c->trsv_inv256);
-    if (c->trsv_cnt) hipFree(c->trsv_cnt);
-    c->solve_buf = nullptr; c->perm_buf = nullptr; c->trsv_inv = nullptr; c->trsv_inv256 = nullptr; c->trsv_cnt = nullptr; c->solve_n = 0;
-    MPF_HIP_TRY(c, hipMalloc((void **)&c->solve_buf, (size_t)(4 * n + 8) * sizeof(double)));
-    MPF_HIP_TRY(c, hipMalloc((void **)&c->perm_buf, (size_t)n * sizeof(int32_t)));
-    MPF_HIP_TRY(c, hipMalloc((void **)&c->trsv_inv, (size_t)(2 * ((n + 63) / 64)) * 64 * 64 * sizeof(double)));
-    MPF_HIP_TRY(c, hipMalloc((void **)&c->trsv_inv256, (size_t)(2 * ((n + 255) / 256)) * 256 * 256 * sizeof(double)));
-    MPF_HIP_TRY(c, hipMalloc((void **)&c->trsv_cnt, (size_t)(2 * ((n + 255) / 256) + 2) * sizeof(int)));
+    c->solve_buf.release(); c->perm_buf.release(); c->trsv_inv.release(); c->trsv_inv256.release(); c->trsv_cnt.release();
+    c->solve_n = 0;
+    MPF_HIP_TRY(c, c->solve_buf.grow(4 * n + 8));
+    MPF_HIP_TRY(c, c->perm_buf.grow(n));
+    MPF_HIP_TRY(c, c->trsv_inv.grow(2 * ((n + 63) / 64) * 64 * 64));
+    MPF_HIP_TRY(c, c->trsv_inv256.grow(2 * ((n + 255) / 256) * 256 * 256));
+    MPF_HIP_TRY(c, c->trsv_cnt.grow(2 * ((n + 255) / 256) + 2));
     c->solve_n = n;
     return 0;
 }

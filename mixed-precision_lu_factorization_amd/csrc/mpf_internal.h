@@ -121,6 +121,38 @@ struct MpfTuning {
 #endif
 };
 
+// Grow-only scratch buffer (device memory, or pinned host memory when Pinned) owned by whoever holds it; freed when that is destroyed.
+// grow(n) reallocates only when n elements do not fit, and keeps no contents; on failure the buffer is empty and the error is returned
+// (the caller decides whether that is fatal and whether to clear HIP's sticky error).
+template <class T, bool Pinned = false>
+struct Buf {
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { release(); }
+    hipError_t grow(int64_t n) {
+        if (n <= cap_) return hipSuccess;
+        release();
+        void *q = nullptr;
+        const hipError_t e = Pinned ? hipHostMalloc(&q, (size_t)n * sizeof(T)) : hipMalloc(&q, (size_t)n * sizeof(T));
+        if (e != hipSuccess) return e;
+        p_ = (T *)q;
+        cap_ = n;
+        return hipSuccess;
+    }
+    void release() {
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    int64_t cap() const { return cap_; }   // elements
+private:
+    T *p_ = nullptr;
+    int64_t cap_ = 0;
+};
+
 struct mpf_ctx {
     MpfTuning tune;
     unsigned attr_done = 0;            // hipFuncSetAttribute done for this context's device, one bit per kernel family
@@ -138,73 +170,57 @@ struct mpf_ctx {
     mpf_stats stats{};
     int num_cus = 0;
     // scratch for the solve path (grown on demand)
-    double *solve_buf = nullptr;
+    Buf<double> solve_buf;
     int64_t solve_n = 0;
-    unsigned short *h_L = nullptr, *h_U = nullptr; // fp16 operand images of the fp16 trailing mode
+    Buf<unsigned short> h_L, h_U;      // fp16 operand images of the fp16 trailing mode
     int64_t h_rows = 0;
-    unsigned short *h_Lb[2] = {nullptr, nullptr}; // L images of the deferred K = sb * nb updates (two super-panels in flight)
+    Buf<unsigned short> h_Lb[2];       // L images of the deferred K = sb * nb updates (two super-panels in flight)
     int h_kmax = 0;                     // K capacity (columns) of the fp16 operand images
     unsigned hp_seq = 0;               // launch sequence number of the pivot kernel (row-granule tags)
     unsigned long long *hp_signal = nullptr;   // 8 bytes of signal memory (hipMallocSignalMemory): the progress word for hipStreamWaitValue64
-    int32_t *perm_buf = nullptr;
-    MovedList *lists = nullptr;        // one moved-row list per panel of the running factorization
-    int lists_cap = 0;
-    int *Fmap = nullptr;               // composite row map of the deferred left-hand interchanges
-    double *perm_tmp = nullptr;        // N x nb scratch of the same
-    int64_t perm_cap = 0, fmap_cap = 0;
-    double *trsv_inv = nullptr;        // inverted 64x64 diagonal blocks of L then of U (solve path)
-    double *trsv_inv256 = nullptr;     // full inverses of the 256 x 256 diagonal blocks of L then of U (single-GPU solve)
-    int *trsv_cnt = nullptr;           // per-step counters of the solve's launches (near workgroups done), L steps then U steps
-    double *krylov = nullptr;          // GMRES-IR: (restart + 1) basis vectors
-    size_t krylov_cap = 0;             // doubles
-    double *res_part = nullptr;        // per-column-chunk partial sums of the residual (deterministic reduction)
-    size_t res_part_cap = 0;           // doubles
+    Buf<int32_t> perm_buf;
+    Buf<MovedList> lists;              // one moved-row list per panel of the running factorization
+    Buf<int> Fmap;                     // composite row map of the deferred left-hand interchanges (the map and its inverse)
+    Buf<double> perm_tmp;              // N x nb scratch of the same
+    Buf<double> trsv_inv;              // inverted 64x64 diagonal blocks of L then of U (solve path)
+    Buf<double> trsv_inv256;           // full inverses of the 256 x 256 diagonal blocks of L then of U (single-GPU solve)
+    Buf<int> trsv_cnt;                 // per-step counters of the solve's launches (near workgroups done), L steps then U steps
+    Buf<double> krylov;                // GMRES-IR: (restart + 1) basis vectors
+    Buf<double> res_part;              // per-column-chunk partial sums of the residual (deterministic reduction)
     // factored 32x32 diagonal tiles of the fp64 panel, parked here until every workgroup of the sub-panel launches has
     // read the UNfactored tile from the matrix (dpanel.hip); one tile per 32 panel columns, grown on demand
-    double *dtiles = nullptr;
-    int dtiles_cap = 0;                // tiles
-    float *w32 = nullptr;              // fp32 working copy of the trailing matrix (fp16 trailing modes, two-level schedule)
-    int64_t w32_n = 0;
-    double *r64 = nullptr;             // fp64 ROW-major working copy of the trailing matrix (fp64 mode, factor_lookahead_rm)
-    int64_t r64_n = 0;                 // the size it was last used for
-    int64_t r64_cap = 0;               // its capacity (doubles)
+    Buf<double> dtiles;
+    Buf<float> w32;                    // fp32 working copy of the trailing matrix (fp16 trailing modes, two-level schedule)
+    Buf<double> r64;                   // fp64 ROW-major working copy of the trailing matrix (fp64 mode, factor_lookahead_rm)
     bool hgemm_standalone = false;     // set around the fp16 update of a step operator (no panel chain beside it: the persistent kernel may take every CU)
     mpf_p2p_fn p2p_fn = nullptr;       // point-to-point transport of the distributed solves (mpf_dist_set_p2p); null: RCCL's, or none
     void *p2p_user = nullptr;
     double gmres_budget_ms = 0;        // wall-clock limit of mpf_solve_gmres_ir while mpf_gesv runs it (0: none)
     double fp64_rate_tflops = 0;       // last measured fp64-mode factorization rate of this context (N >= 8192; 0: none yet)
-    double *host_A = nullptr;          // mpf_factor_host's device copy of the caller's matrix, kept between calls (grow-only)
-    int64_t host_A_cap = 0;            // bytes
-    int32_t *host_P = nullptr;         // ... and of the pivot vector
-    int64_t host_P_cap = 0;
-    double *host_A0 = nullptr;         // ... and the matrix as uploaded, while block rows leave during the factorization (rowsink.hip): what a
-    int64_t host_A0_cap = 0;           // repeated call on the generic pivot path starts from when the caller's buffer is already partly results
-    unsigned *late_flags = nullptr;    // 16 pinned host words: LatePlan::flags
+    Buf<double> host_A;                // mpf_factor_host's device copy of the caller's matrix, kept between calls
+    Buf<int32_t> host_P;               // ... and of the pivot vector
+    Buf<double> host_A0;               // ... and the matrix (then the pivot vector) as uploaded, while block rows leave during the factorization
+                                       // (rowsink.hip): what a repeated call on the generic pivot path starts from when the caller's buffer is
+                                       // already partly results
+    Buf<unsigned, true> late_flags;    // 16 pinned host words: LatePlan::flags
     unsigned late_seq = 0;
     struct ColFeed *feed = nullptr;    // mpf_factor_host's upload of late column segments (rowsink.hip)
     struct LatePlan *late = nullptr;   // set by mpf_factor_host around mpf_factor_dev: column segments still on their way up (factor_lookahead_rm takes it)
     struct RowSink *sink = nullptr;    // mpf_factor_host's block-row copies (rowsink.hip); null until the first call that uses it
-    double *rm_tmp = nullptr;          // its scratch: moved rows of an interchange (2 * HP_MAXCOLS x N) / the panel's L21 row-major
-    int64_t rm_tmp_cap = 0;            // doubles
-    double *rm_lt = nullptr;           // L21 of the current panel, row-major [rows][nb]
-    int64_t rm_lt_cap = 0;
+    Buf<double> rm_tmp;                // its scratch: moved rows of an interchange (2 * HP_MAXCOLS x N) / the panel's L21 row-major
+    Buf<double> rm_lt;                 // L21 of the current panel, row-major [rows][nb]
     // generic (global-memory) fp16 pivot path, fp16_panel_generic.hip: packed fp16 panel + per-block candidates
-    unsigned short *g16 = nullptr;
-    size_t g16_cap = 0;                // elements
-    unsigned long long *gcand = nullptr;
-    int gcand_cap = 0;
+    Buf<unsigned short> g16;
+    Buf<unsigned long long> gcand;
     // distributed path (mpf_dist.cpp): RCCL communicator (dlopen'ed), two panel message buffers
     void *rccl_comm = nullptr;
     int rccl_rank = 0, rccl_world = 0;
     long long rccl_bcast_calls = 0, rccl_bcast_bytes = 0, rccl_allreduce_calls = 0, rccl_p2p_calls = 0, rccl_p2p_bytes = 0;   // since mpf_rccl_init
-    double *dist_buf[2] = {nullptr, nullptr};
-    size_t dist_buf_cap = 0;           // bytes
+    Buf<double> dist_buf[2];
     // mpf_factor_dist, two-level schedule of the fp16 modes: this rank's fp32 working copy (N rows x local columns, row-major) and
     // the current super-panel's panels as every rank received them (N x sb * nb doubles, column-major, leading dimension N)
-    float *dist_w32 = nullptr;
-    int64_t dist_w32_cap = 0;          // floats
-    double *dist_spl = nullptr;
-    int64_t dist_spl_cap = 0;          // doubles
+    Buf<float> dist_w32;
+    Buf<double> dist_spl;
     int hp_resident_per_cu = -1;       // occupancy query of the LDS pivot kernel (cached)
     int hp_win_per_cu = 0;             // ... of its column-window form
     int hp_full_beside_waiter = 0;     // pivot workgroups (full-slab / column-window form) that still fit on a CU that holds one workgroup of
@@ -337,6 +353,9 @@ extern "C" {
 int mpf_ensure_h_images(mpf_ctx *c, int64_t rows, int kmax, bool big); // internal (not in mpf_c.h): fp16 operand images
 int mpf_ensure_solve_buf(mpf_ctx *c, int64_t n);                        // internal: solve scratch
 int mpf_ensure_rowmajor_copy(mpf_ctx *c, int64_t rows, int64_t cols, int32_t nb);   // internal: fp64 row-major working copy + its scratch (non-zero: no room)
+// internal: before a factorization (mpf_factor_dev, mpf_factor_dist) -- with `lists`, the per-panel moved-row lists (cleared) and the scratch
+// of the deferred left-hand interchanges; always the first-zero-pivot word (INT_MAX) and the pivot kernel's give-up counter (0)
+int mpf_factor_setup(mpf_ctx *c, int64_t N, int32_t nb, int32_t npanels, bool lists);
 }
 int launch_trsv_prepare(mpf_ctx *c, const double *LU, int64_t ld, int64_t n);
 int launch_trsv_lower_unit(mpf_ctx *c, const double *LU, int64_t ld, double *x, int64_t n);

@@ -147,13 +147,7 @@ int mpf_solve_gmres_ir(mpf_ctx *c, const double *d_A, int64_t lda, const double 
     int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
     if (rc) return rc;
     const int m = restart;
-    const size_t vneed = (size_t)(m + 1) * (size_t)N;
-    if (vneed > c->krylov_cap) {
-        if (c->krylov) hipFree(c->krylov);
-        c->krylov = nullptr; c->krylov_cap = 0;
-        MPF_HIP_TRY(c, hipMalloc((void **)&c->krylov, vneed * sizeof(double)));
-        c->krylov_cap = vneed;
-    }
+    MPF_HIP_TRY(c, c->krylov.grow((int64_t)(m + 1) * N));
     double *V = c->krylov;
     const int64_t S = c->solve_n;
     double *r = c->solve_buf, *w = c->solve_buf + S;

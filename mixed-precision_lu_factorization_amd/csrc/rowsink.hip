@@ -72,12 +72,9 @@ struct RowSink {
     // for the life of the context
     hipStream_t cs = nullptr;          // carries the bounce copies and nothing else
     std::vector<hipEvent_t> events;
-    int *maps = nullptr;               // Id (N) | Pos (N) | Pos_j, j = 0 .. npanels - 1 (N each)
-    int64_t maps_cap = 0;              // ints
-    double *stage = nullptr;           // one staging block per panel
-    int64_t stage_cap = 0;             // doubles
-    double *bounce = nullptr;          // SINK_BOUNCE pinned blocks
-    int64_t bounce_cap = 0;            // doubles
+    Buf<int> maps;                     // Id (N) | Pos (N) | Pos_j, j = 0 .. npanels - 1 (N each)
+    Buf<double> stage;                 // one staging block per panel
+    Buf<double, true> bounce;          // SINK_BOUNCE pinned blocks
 };
 
 namespace {
@@ -200,18 +197,10 @@ int sink_attach(mpf_ctx *c, double *A_host, int64_t N, int nb) {
     const int64_t slot = N * (int64_t)nb + SINK_TAIL;
     const int64_t need_maps = (int64_t)(npanels + 2) * N, need_stage = (int64_t)npanels * slot, need_bounce = SINK_BOUNCE * slot;
     if (need_maps * 4 > (4ll << 30)) return 1;   // (very narrow panels on a very large matrix)
-    auto grow = [&](auto *&ptr, int64_t &cap, int64_t need, size_t elem, bool pinned) -> int {
-        if (cap >= need) return 0;
-        if (ptr) (void)(pinned ? hipHostFree(ptr) : hipFree(ptr));
-        ptr = nullptr; cap = 0;
-        const hipError_t e = pinned ? hipHostMalloc((void **)&ptr, (size_t)need * elem) : hipMalloc((void **)&ptr, (size_t)need * elem);
-        if (e != hipSuccess) { (void)hipGetLastError(); ptr = nullptr; return 1; }   // (no room: the plain copy at the end)
-        cap = need;
-        return 0;
-    };
-    if (grow(s->maps, s->maps_cap, need_maps, sizeof(int), false)) return 1;
-    if (grow(s->stage, s->stage_cap, need_stage, sizeof(double), false)) return 1;
-    if (grow(s->bounce, s->bounce_cap, need_bounce, sizeof(double), true)) return 1;
+    if (s->maps.grow(need_maps) || s->stage.grow(need_stage) || s->bounce.grow(need_bounce)) {
+        (void)hipGetLastError();   // (no room: the plain copy at the end)
+        return 1;
+    }
     while ((int)s->events.size() < npanels + 4) {
         hipEvent_t e;
         MPF_HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -310,17 +299,13 @@ int sink_finish(mpf_ctx *c, int *panels_sent) {
 void sink_trim(mpf_ctx *c) {
     RowSink *s = c->sink;
     if (!s || s->taken) return;
-    if (s->maps) hipFree(s->maps);
-    if (s->stage) hipFree(s->stage);
-    if (s->bounce) hipHostFree(s->bounce);
-    s->maps = nullptr; s->stage = nullptr; s->bounce = nullptr; s->maps_cap = s->stage_cap = s->bounce_cap = 0;
+    s->maps.release(); s->stage.release(); s->bounce.release();
 }
 
 void sink_destroy(mpf_ctx *c) {
     RowSink *s = c->sink;
     if (!s) return;
     if (s->taken) sink_join(s);
-    sink_trim(c);
     if (s->cs) { hipStreamSynchronize(s->cs); hipStreamDestroy(s->cs); }
     for (hipEvent_t e : s->events) hipEventDestroy(e);
     delete s;
@@ -352,8 +337,8 @@ struct ColFeed {
     bool wclosing = false, running = false;
     hipError_t err = hipSuccess;
     hipStream_t fs = nullptr;
-    double *bounce = nullptr;          // two pinned slabs
-    int64_t slab_doubles = 0, bounce_cap = 0;
+    Buf<double, true> bounce;          // two pinned slabs
+    int64_t slab_doubles = 0;
 };
 
 namespace {
@@ -441,12 +426,7 @@ int feed_start(mpf_ctx *c, const double *A_host, double *d_A, int64_t N, LatePla
     int64_t slab_cols = (64ll << 20) / (N * 8);
     if (slab_cols < 1) slab_cols = 1;
     const int64_t need = 2 * slab_cols * N;
-    if (f->bounce_cap < need) {
-        if (f->bounce) (void)hipHostFree(f->bounce);
-        f->bounce = nullptr; f->bounce_cap = 0;
-        MPF_HIP_TRY(c, hipHostMalloc((void **)&f->bounce, (size_t)need * sizeof(double)));
-        f->bounce_cap = need;
-    }
+    MPF_HIP_TRY(c, f->bounce.grow(need));
     f->slab_doubles = slab_cols * N;
     f->host = A_host; f->dA = d_A; f->N = N; f->lp = lp; f->err = hipSuccess; f->wclosing = false;
     f->tasks.clear(); f->pending[0] = f->pending[1] = 0;
@@ -482,15 +462,13 @@ int feed_finish(mpf_ctx *c) {
 void feed_trim(mpf_ctx *c) {
     ColFeed *f = c->feed;
     if (!f || f->running) return;
-    if (f->bounce) hipHostFree(f->bounce);
-    f->bounce = nullptr; f->bounce_cap = 0;
+    f->bounce.release();
 }
 
 void feed_destroy(mpf_ctx *c) {
     ColFeed *f = c->feed;
     if (!f) return;
     (void)feed_finish(c);
-    feed_trim(c);
     if (f->fs) { hipStreamSynchronize(f->fs); hipStreamDestroy(f->fs); }
     delete f;
     c->feed = nullptr;
