@@ -261,6 +261,76 @@ int mpf_gesv(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t N, int32_t nb
                                   GMRES-IR with the caller's own limits: mpf_solve_gmres_ir */,
              mpf_gesv_stats *stats);
 
+/* ---- expert solve driver (build extension; LAPACK dgetrs('T') / dlange / dgeequ / dgecon / dgesvx analogues) ----------------
+ * Every reduction below has one fixed order (no floating-point atomics): a second call on the same data returns the same bits. */
+
+/* mpf_solve_ir_nrhs for A^T X = B: the factors of A (P A = L U, from mpf_factor_dev) give x0 = P^T L^-T U^-T b through
+ * U^T w = b (forward), L^T z = w (backward), x[perm[i]] = z[i]; refinement takes r = b - A^T x in fp64 and stops, stalls and
+ * diverges by the rules of the plain solve.  Same arguments, stats per right-hand side.  Synchronises; -4 as the plain solve. */
+int mpf_solve_ir_trans(mpf_ctx *ctx, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
+                       int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_iter,
+                       double tol, mpf_ir_stats *stats);
+
+/* LAPACK dlange of the M x N matrix d_A: norm '1' / 'O' max column abs sum, 'I' max row abs sum, 'M' max |a_ij|, 'F' Frobenius
+ * (ordered sum of squares, then sqrt: no rescaling, so entries beyond ~1e154 overflow -- out of scope).  *out on the host;
+ * synchronises. */
+int mpf_lange(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t M, int64_t N, char norm, double *out);
+
+/* Equilibration factors of the N x N matrix d_A as LAPACK dgeequb computes them, powers of two so that scaling is exact:
+ *   r_i = 2^-floor(log2 max_j |a_ij|),  c_j = 2^-floor(log2 max_i |a_ij| r_i)   (exponents clamped to [-1022, 1022]);
+ * rowcnd / colcnd / amax as dgeequ: rowcnd = max(min_i m_i, smlnum) / min(max_i m_i, bignum) over the row maxima m_i (colcnd
+ * the same over the scaled column maxima), amax = max |a_ij|; smlnum = DBL_MIN, bignum = 1 / smlnum.  d_r, d_c: N doubles each
+ * on the device.  Returns 0; i + 1 when row i (0-based) is zero (then d_c, colcnd are not set); N + j + 1 when column j is.
+ * Synchronises. */
+int mpf_geequ(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t N, double *d_r, double *d_c, double *rowcnd, double *colcnd,
+              double *amax);
+
+/* Reciprocal condition number of the factored matrix, as LAPACK dgecon: ||(L U)^-1|| is estimated by dlacn2 (Hager / Higham,
+ * ITMAX = 5) on the device's triangular solves (no P, which changes neither norm): norm '1' / 'O': its B-products are L-then-U
+ * solves, its B^T-products U^T-then-L^T solves; 'I': the two swapped.  rcond = 1 / (anorm * ainvnm), anorm = the same norm of
+ * the matrix (mpf_lange).  rcond = 0 without a NaN when anorm == 0, when U has a zero diagonal entry (checked before any solve)
+ * or when the estimate is not finite.  Synchronises; -4 as the solves. */
+typedef struct mpf_gecon_stats {
+    int32_t solves;       /* L-then-U solves (A^-1 products) */
+    int32_t solves_t;     /* U^T-then-L^T solves (A^-T products) */
+    int32_t iterations;   /* dlacn2's iteration count (2 .. 5; 1 for N = 1) */
+    int32_t reserved;
+    double ainvnm;        /* the estimate of ||(L U)^-1|| */
+    double ms_total;
+} mpf_gecon_stats;
+int mpf_gecon(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t N, char norm, double anorm, double *rcond,
+              mpf_gecon_stats *stats);
+
+/* Expert driver (LAPACK dgesvx's shape, one right-hand side): solve A x = b (trans = 0) or A^T x = b (trans = 1).
+ *   1. equilibrate: 0 never; 1 by dlaqge's rule (rows if rowcnd < 0.1 or amax outside [smlnum, bignum], smlnum = DBL_MIN / 2^-52;
+ *      columns if colcnd < 0.1); 2 always; nothing when mpf_geequ reports a zero row or column.  d_work = Dr A Dc (ld = N).
+ *      In the low-precision modes an equilibrated matrix gets one more global power of two, folded into Dr (equed then includes
+ *      rows), so that max |Dr A Dc| lies in [2^13, 2^14): the fp16 operands saturate at 65504 and go subnormal below 2^-14.
+ *   2. factor d_work in the mode try_fp16 asks for (0: fp64, 1: fp16, 2: fp16x3), 3. mpf_gecon on those factors (norm '1',
+ *      'I' for trans = 1), 4. if 1 / rcond > kappa_max (0: 1e4 for fp16, 1e6 for fp16x3) factor again in fp64 at once;
+ *   5. otherwise refine against the ORIGINAL A: r = b - A x (or b - A^T x) in fp64, correction Dc (L U)^-1 P (Dr r) (trans = 1:
+ *      Dr P^T (L U)^-T (Dc r)), with mpf_solve_ir's stop / stall rules; 6. not converged: fp64 factors of the same equilibrated
+ *      matrix, refined the same way.
+ * d_A is preserved; d_work (N x N) holds the factors used on return, d_ipiv (N int32) their pivots; d_r / d_c (N doubles each,
+ * optional) receive the scale factors (valid where equed says they were applied).  Returns 0 when the answer converged, 1 when
+ * not, < 0 on error.  Synchronises. */
+typedef struct mpf_gesvx_stats {
+    int32_t path;             /* 1: low-precision factors + refinement, 2: fp64 factors */
+    int32_t info;             /* first zero pivot of the last factorization (1-based) or 0 */
+    int32_t equed;            /* 0 none, 1 rows, 2 columns, 3 both */
+    int32_t skipped_by_rcond; /* 1: the low-precision factors' rcond sent the solve to fp64 without refining */
+    double rowcnd, colcnd, amax;   /* mpf_geequ's (0 when equilibrate = 0) */
+    double anorm;             /* norm of the equilibrated matrix gecon used */
+    double kappa_max;         /* the threshold applied */
+    double rcond_lowp;        /* rcond of the low-precision factors (0: none) */
+    double rcond;             /* rcond of the factors the answer was refined with */
+    double ms_equilibrate, ms_factor, ms_gecon, ms_ir, ms_total;
+    mpf_ir_stats ir_lowp, ir_final;
+} mpf_gesvx_stats;
+int mpf_gesvx(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t N, int32_t nb, double *d_work, int32_t *d_ipiv,
+              const double *d_b, double *d_x, int32_t trans, int32_t equilibrate, int32_t try_fp16, double kappa_max,
+              int32_t max_iter, double tol, double *d_r, double *d_c, mpf_gesvx_stats *stats);
+
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block
  * b / world; d_Aloc is the rank's N x (local columns) column-major matrix (ldloc >= N), d_ipiv the full pivot vector (N int32,

@@ -31,6 +31,7 @@ C_ABI_SYMBOLS = [
     "mpf_matgen_state", "mpf_rccl_unique_id", "mpf_rccl_init", "mpf_rccl_destroy", "mpf_rccl_version", "mpf_rccl_info", "mpf_rccl_bcast_probe", "mpf_factor_dist",
     "mpf_solve_ir_dist", "mpf_rccl_selftest", "mpf_check_plu_dev", "mpf_check_plu_host", "mpf_solve_ir_nrhs",
     "mpf_solve_gmres_ir", "mpf_trim", "mpf_dist_set_p2p",
+    "mpf_solve_ir_trans", "mpf_lange", "mpf_geequ", "mpf_gecon", "mpf_gesvx",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -75,6 +76,18 @@ class MpfGesvStats(C.Structure):
                 ("ms_factor_fp64", C.c_double), ("ms_ir_fp64", C.c_double), ("ms_total", C.c_double),
                 ("ir_fp16", MpfIrStats), ("ir_final", MpfIrStats), ("gmres_budget_ms", C.c_double), ("gmres_budget_expired", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class MpfGeconStats(C.Structure):
+    _fields_ = [("solves", C.c_int32), ("solves_t", C.c_int32), ("iterations", C.c_int32), ("reserved", C.c_int32),
+                ("ainvnm", C.c_double), ("ms_total", C.c_double)]
+
+
+class MpfGesvxStats(C.Structure):
+    _fields_ = [("path", C.c_int32), ("info", C.c_int32), ("equed", C.c_int32), ("skipped_by_rcond", C.c_int32),
+                ("rowcnd", C.c_double), ("colcnd", C.c_double), ("amax", C.c_double), ("anorm", C.c_double), ("kappa_max", C.c_double),
+                ("rcond_lowp", C.c_double), ("rcond", C.c_double), ("ms_equilibrate", C.c_double), ("ms_factor", C.c_double),
+                ("ms_gecon", C.c_double), ("ms_ir", C.c_double), ("ms_total", C.c_double), ("ir_lowp", MpfIrStats), ("ir_final", MpfIrStats)]
 
 
 BCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)
@@ -149,6 +162,11 @@ def load_library(probe=False):
     L.mpf_solve_ir_nrhs.argtypes = [vp, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, dbl, C.POINTER(MpfIrStats)]
     L.mpf_solve_gmres_ir.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, dbl, C.POINTER(MpfGmresStats)]
     L.mpf_gesv.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, vp, i32, dbl, i32, C.POINTER(MpfGesvStats)]
+    L.mpf_solve_ir_trans.argtypes = [vp, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, dbl, C.POINTER(MpfIrStats)]
+    L.mpf_lange.argtypes = [vp, vp, i64, i64, i64, C.c_char, C.POINTER(dbl)]
+    L.mpf_geequ.argtypes = [vp, vp, i64, i64, vp, vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]
+    L.mpf_gecon.argtypes = [vp, vp, i64, i64, C.c_char, dbl, C.POINTER(dbl), C.POINTER(MpfGeconStats)]
+    L.mpf_gesvx.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, vp, i32, i32, i32, dbl, i32, dbl, vp, vp, C.POINTER(MpfGesvxStats)]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -575,3 +593,77 @@ class MPFContext:
                              int(try_fp16), C.byref(st))  # try_fp16: 0 fp64 only, 1/True fp16, 2 fp16x3
         self._check(rc, "mpf_gesv")
         return x, st, work, ipiv
+
+    # ---- expert driver (include/mpf_c.h: transposed solve, norms, equilibration, condition estimate) ------------------------
+    def solve_ir_trans(self, A, LU, ipiv, B, max_iter=10, tol=1e-12):
+        """mpf_solve_ir_trans: A^T X = B with the factors of A.  B: vector (N) or N x nrhs column-major; returns (X, stats) --
+        stats a list per column when B is a matrix."""
+        self._bind()
+        n = A.shape[0]
+        vec = B.dim() == 1
+        nrhs = 1 if vec else B.shape[1]
+        X = self.torch.empty(n, dtype=self.torch.float64, device=self.device) if vec else self.colmajor(n, nrhs)
+        st = (MpfIrStats * max(nrhs, 1))()
+        ldb = n if vec else _colmajor_ld(B)
+        ldx = n if vec else _colmajor_ld(X)
+        rc = self.L.mpf_solve_ir_trans(self.h, _ptr(A), _colmajor_ld(A), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n, nrhs,
+                                       _ptr(B), ldb, _ptr(X), ldx, max_iter, tol, st)
+        self._check(rc, "mpf_solve_ir_trans")
+        return X, (st[0] if vec else list(st)[:nrhs])
+
+    def lange(self, A, norm="1"):
+        """mpf_lange: '1'/'O', 'I', 'M' or 'F' norm of the column-major matrix A (M x N)."""
+        self._bind()
+        m, n = A.shape
+        out = C.c_double(0)
+        ld = _colmajor_ld(A) if m > 0 and n > 0 else max(m, 1)
+        self._check(self.L.mpf_lange(self.h, _ptr(A), ld, m, n, norm.encode()[:1], C.byref(out)), "mpf_lange")
+        return out.value
+
+    def geequ(self, A):
+        """mpf_geequ: power-of-two row / column scale factors.  Returns (r, c, rowcnd, colcnd, amax, info)."""
+        self._bind()
+        t = self.torch
+        n = A.shape[0]
+        r = t.zeros(n, dtype=t.float64, device=self.device)
+        c = t.zeros(n, dtype=t.float64, device=self.device)
+        rc_, cc_, am = C.c_double(0), C.c_double(0), C.c_double(0)
+        info = self._check(self.L.mpf_geequ(self.h, _ptr(A), _colmajor_ld(A), n, _ptr(r), _ptr(c), C.byref(rc_), C.byref(cc_), C.byref(am)),
+                           "mpf_geequ")
+        return r, c, rc_.value, cc_.value, am.value, info
+
+    def gecon(self, LU, anorm, norm="1"):
+        """mpf_gecon: reciprocal condition number of the factored matrix (LAPACK dgecon).  Returns (rcond, stats)."""
+        self._bind()
+        rcond = C.c_double(0)
+        st = MpfGeconStats()
+        self._check(self.L.mpf_gecon(self.h, _ptr(LU), _colmajor_ld(LU), LU.shape[0], norm.encode()[:1], float(anorm), C.byref(rcond),
+                                     C.byref(st)), "mpf_gecon")
+        return rcond.value, st
+
+    def cond(self, A, LU, ipiv=None, norm="1"):
+        """Estimated condition number of A from its factors: anorm * ||(L U)^-1|| = 1 / rcond (norm '1' or 'I'; ipiv is accepted
+        for symmetry with the solves -- the pivots change neither norm).  inf where rcond is 0."""
+        anorm = self.lange(A, norm)
+        rcond, _ = self.gecon(LU, anorm, norm)
+        return float("inf") if rcond == 0 else 1.0 / rcond
+
+    def gesvx(self, A, b, nb=256, trans=False, equilibrate=1, try_fp16=1, kappa_max=0.0, max_iter=10, tol=1e-12, work=None,
+              want_scales=False):
+        """mpf_gesvx: equilibrate, factor (try_fp16: 0 fp64, 1 fp16, 2 fp16x3), estimate rcond, refine against A, fall back to
+        fp64.  Returns (x, stats, work, ipiv) and, with want_scales, (r, c) as well."""
+        self._bind()
+        t = self.torch
+        n = A.shape[0]
+        if work is None:
+            work = self.colmajor(n, n)
+        ipiv = t.empty(n, dtype=t.int32, device=self.device)
+        x = t.empty(n, dtype=t.float64, device=self.device)
+        r = t.empty(n, dtype=t.float64, device=self.device) if want_scales else None
+        c = t.empty(n, dtype=t.float64, device=self.device) if want_scales else None
+        st = MpfGesvxStats()
+        rc = self.L.mpf_gesvx(self.h, _ptr(A), _colmajor_ld(A), n, nb, _ptr(work), _ptr(ipiv), _ptr(b), _ptr(x), int(bool(trans)),
+                              int(equilibrate), int(try_fp16), float(kappa_max), max_iter, tol, _ptr(r), _ptr(c), C.byref(st))
+        self._check(rc, "mpf_gesvx")
+        out = (x, st, work, ipiv)
+        return out + (r, c) if want_scales else out

@@ -187,6 +187,8 @@ struct mpf_ctx {
     Buf<int> trsv_cnt;                 // per-step counters of the solve's launches (near workgroups done), L steps then U steps
     Buf<double> krylov;                // GMRES-IR: (restart + 1) basis vectors
     Buf<double> res_part;              // per-column-chunk partial sums of the residual (deterministic reduction)
+    // expert driver (mpf_expert.cpp, solve_ext.hip): partials of the column / row reductions, of the vector reductions, and its vectors
+    Buf<double> ext_part, ext_red, ext_vec;
     // factored 32x32 diagonal tiles of the fp64 panel, parked here until every workgroup of the sub-panel launches has
     // read the UNfactored tile from the matrix (dpanel.hip); one tile per 32 panel columns, grown on demand
     Buf<double> dtiles;
@@ -364,6 +366,30 @@ int launch_axpy(mpf_ctx *c, double alpha, const double *x, double *y, int64_t n)
 int launch_norm2(mpf_ctx *c, const double *x, int64_t n, double *d_out);
 int launch_dot(mpf_ctx *c, const double *x, const double *y, int64_t n, double *d_out);
 int launch_scal(mpf_ctx *c, double alpha, double *x, int64_t n);
+// shared by the solve entry points (mpf_solve.cpp, mpf_expert.cpp): the pivot sequence as a gather index in c->perm_buf and the
+// factors' inverted diagonal blocks (launch_trsv_prepare); after the stream has been synchronised, -4 if a bounded wait gave up
+int solve_setup(mpf_ctx *c, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv, int64_t N);
+int solve_check_waits(mpf_ctx *c);
+// expert driver kernels (solve_ext.hip).  Transposed solves with the packed factors, in place on x (prepared as for the plain ones):
+int launch_trsv_upper_t(mpf_ctx *c, const double *LU, int64_t ld, double *x, int64_t n);        // U^T w = x
+int launch_trsv_lower_unit_t(mpf_ctx *c, const double *LU, int64_t ld, double *x, int64_t n);   // L^T z = x
+int launch_scatter_rows(mpf_ctx *c, const double *in, const int *perm, double *out, int64_t n); // out[perm[i]] = in[i]
+int launch_residual_t(mpf_ctx *c, const double *A, int64_t lda, const double *x, const double *b, double *r, int64_t n);   // r = b - A^T x
+int launch_col_abs_sums(mpf_ctx *c, const double *A, int64_t lda, int64_t m, int64_t n, double *out);
+int launch_col_sumsq(mpf_ctx *c, const double *A, int64_t lda, int64_t m, int64_t n, double *out);
+int launch_col_max_abs(mpf_ctx *c, const double *A, int64_t lda, int64_t m, int64_t n, const double *rs, double *out);   // max_i |a_ij| rs_i
+int launch_row_abs_sums(mpf_ctx *c, const double *A, int64_t lda, int64_t m, int64_t n, double *out);
+int launch_row_max_abs(mpf_ctx *c, const double *A, int64_t lda, int64_t m, int64_t n, double *out);
+int launch_vec_sum(mpf_ctx *c, const double *x, int64_t n, double *d_out);
+int launch_vec_max(mpf_ctx *c, const double *x, int64_t n, double *d_out);
+int launch_dasum(mpf_ctx *c, const double *x, int64_t n, double *d_out);
+int launch_lacn2_sign(mpf_ctx *c, const double *x, const double *isgn, int64_t n, double *xs, double *d_out);
+int launch_idamax(mpf_ctx *c, const double *x, int64_t n, double *d_out);
+int launch_lacn2_fill(mpf_ctx *c, double *x, int64_t n, int kind, int64_t j);
+int launch_diag_zero(mpf_ctx *c, const double *LU, int64_t ld, int64_t n, double *d_out);
+int launch_pow2_scale(mpf_ctx *c, const double *m, int64_t n, double *s, double *d_stats);
+int launch_scaled_copy(mpf_ctx *c, const double *A, int64_t lda, const double *r, const double *cs, double *W, int64_t ldw, int64_t m, int64_t n);
+int launch_vscale(mpf_ctx *c, const double *x, const double *s, double alpha, double *y, int64_t n);
 
 // ---- host-side helpers shared by the schedules (mpf_host.cpp, mpf_dist.cpp) --------------------------------------------
 struct StreamSwap { // launch_* helpers use c->stream: point it at another stream for a scope

@@ -10,7 +10,6 @@
 #include <cmath>
 #include <cstring>
 
-namespace {
 // what every solve on one set of factors shares: the pivot sequence as a gather index and the inverted diagonal blocks
 int solve_setup(mpf_ctx *c, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv, int64_t N) {
     int rc = mpf_ensure_solve_buf(c, N);
@@ -37,6 +36,8 @@ int solve_check_waits(mpf_ctx *c) {
     if (flags) { c->err = "solve: a step's wait for its neighbours timed out (GPU shared with another job?)"; return -4; }
     return 0;
 }
+
+namespace {
 int lu_solve(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t N, const double *rhs, double *out) { // out = U^-1 L^-1 P rhs
     int e = launch_gather_rows(c, rhs, c->perm_buf, out, N);
     if (!e) e = launch_trsv_lower_unit(c, d_LU, ldlu, out, N);
