@@ -331,6 +331,27 @@ int mpf_gesvx(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t N, int32_t n
               const double *d_b, double *d_x, int32_t trans, int32_t equilibrate, int32_t try_fp16, double kappa_max,
               int32_t max_iter, double tol, double *d_r, double *d_c, mpf_gesvx_stats *stats);
 
+/* ---- blocked multi-right-hand-side solve (build extension; LAPACK dgetrs and block refinement) -----------------------------
+ * The right-hand sides go through the device in tiles of 32 columns: every triangular step reads its factor block once per tile
+ * (several tiles in one launch) and every residual reads A once per tile, on fp64 MFMA.  Each column's arithmetic has one fixed
+ * order and reads no other column: X[:, j] (and its stats) has the same bits whatever the other columns, nrhs or j's position,
+ * and two calls return the same bits.  The bits differ from the per-column solves' (another summation order). */
+
+/* LAPACK dgetrs: B := A^-1 B (trans = 0) or A^-T B (trans = 1), in place, with the factors of mpf_factor_dev
+ * (P A = L U).  d_B is N x nrhs column-major, ldb >= N; rows N .. ldb-1 are not touched.  nrhs = 0: returns 0, no work.
+ * Synchronises; -4 when a bounded wait of the step kernel gave up (as the other solves). */
+int mpf_getrs(mpf_ctx *ctx, int32_t trans, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv, int64_t N,
+              int32_t nrhs, double *d_B, int64_t ldb);
+
+/* Refinement of all nrhs columns together: the same per-column rules and stats as mpf_solve_ir_nrhs / _trans.
+ * x0 = getrs(b); r = b - op(A) x in fp64; stop at ||r||/||b|| <= tol, at max_iter, on NaN, or on the stall rule.
+ * The residual, the corrections and the norms are computed for a whole tile of columns per pass over A and over the factors.
+ * A column that has stopped gets no further correction.  stats: nrhs entries (or NULL); ms_total is the wall time of the whole
+ * call and the same for every column.  Synchronises. */
+int mpf_solve_ir_block(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu,
+                       const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X,
+                       int64_t ldx, int32_t max_iter, double tol, mpf_ir_stats *stats);
+
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block
  * b / world; d_Aloc is the rank's N x (local columns) column-major matrix (ldloc >= N), d_ipiv the full pivot vector (N int32,

@@ -32,6 +32,7 @@ C_ABI_SYMBOLS = [
     "mpf_solve_ir_dist", "mpf_rccl_selftest", "mpf_check_plu_dev", "mpf_check_plu_host", "mpf_solve_ir_nrhs",
     "mpf_solve_gmres_ir", "mpf_trim", "mpf_dist_set_p2p",
     "mpf_solve_ir_trans", "mpf_lange", "mpf_geequ", "mpf_gecon", "mpf_gesvx",
+    "mpf_getrs", "mpf_solve_ir_block",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -167,6 +168,8 @@ def load_library(probe=False):
     L.mpf_geequ.argtypes = [vp, vp, i64, i64, vp, vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]
     L.mpf_gecon.argtypes = [vp, vp, i64, i64, C.c_char, dbl, C.POINTER(dbl), C.POINTER(MpfGeconStats)]
     L.mpf_gesvx.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, vp, i32, i32, i32, dbl, i32, dbl, vp, vp, C.POINTER(MpfGesvxStats)]
+    L.mpf_getrs.argtypes = [vp, i32, vp, i64, vp, i64, i32, vp, i64]
+    L.mpf_solve_ir_block.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, dbl, C.POINTER(MpfIrStats)]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -667,3 +670,42 @@ class MPFContext:
         self._check(rc, "mpf_gesvx")
         out = (x, st, work, ipiv)
         return out + (r, c) if want_scales else out
+
+    # ---- blocked multi-right-hand-side solve (include/mpf_c.h: mpf_getrs, mpf_solve_ir_block) -----------------------------------
+    def _rhs(self, B):
+        """(matrix view, nrhs, ld) of a vector (N) or N x nrhs column-major right-hand side."""
+        if B.dim() == 1:
+            return B.view(-1, 1), 1, max(B.shape[0], 1)
+        return B, B.shape[1], _colmajor_ld(B)
+
+    def getrs(self, LU, ipiv, B, trans=False, overwrite=False):
+        """mpf_getrs: X = A^-1 B (or A^-T B) with the factors of A.  Returns a new column-major X and leaves B untouched, unless
+        overwrite=True: then B itself is solved in place and returned."""
+        self._bind()
+        n = LU.shape[0]
+        if overwrite:
+            X = B
+        elif B.dim() == 1:
+            X = B.clone()
+        else:
+            X = self.colmajor(n, B.shape[1])
+            X.copy_(B)
+        _, nrhs, ldx = self._rhs(X)
+        rc = self.L.mpf_getrs(self.h, int(bool(trans)), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n, nrhs, _ptr(X), ldx)
+        self._check(rc, "mpf_getrs")
+        return X
+
+    def solve_ir_block(self, A, LU, ipiv, B, trans=False, max_iter=10, tol=1e-12):
+        """mpf_solve_ir_block: refinement of all columns of B together (per-column rules of solve_ir_nrhs / solve_ir_trans).
+        Returns (X, list of per-column stats); X is a vector when B is."""
+        self._bind()
+        n = A.shape[0]
+        vec = B.dim() == 1
+        _, nrhs, ldb = self._rhs(B)
+        X = self.torch.empty(n, dtype=self.torch.float64, device=self.device) if vec else self.colmajor(n, nrhs)
+        ldx = n if vec else _colmajor_ld(X)
+        st = (MpfIrStats * max(nrhs, 1))()
+        rc = self.L.mpf_solve_ir_block(self.h, int(bool(trans)), _ptr(A), _colmajor_ld(A), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n,
+                                       nrhs, _ptr(B), ldb, _ptr(X), ldx, max_iter, tol, st)
+        self._check(rc, "mpf_solve_ir_block")
+        return X, list(st)[:nrhs]

@@ -1,0 +1,158 @@
+// Blocked multi-right-hand-side solve (no reference counterpart; LAPACK dgetrs and block refinement):
+//   mpf_getrs            B := A^-1 B or A^-T B with the factors of mpf_factor_dev
+//   mpf_solve_ir_block   fp64 refinement of all columns together, per-column rules and stats of mpf_solve_ir_nrhs / _trans
+// The right-hand sides go through the device in groups of at most GROUP_TILES tiles of BLK_T columns (solve_block.hip); every
+// triangular step and every residual is one pass over the factor block / over A for the whole group.
+#include "mpf_internal.h"
+#include <chrono>
+#include <cmath>
+
+namespace {
+constexpr int GROUP_TILES = 16;   // 512 columns per group: five N x 512 tiles of scratch at most
+
+struct Group {
+    int64_t ldt = 0;   // rows of a tile (N rounded up to 256)
+    int ntiles = 0;
+    double *base = nullptr;
+    double *t(int i) const { return base + (int64_t)i * ldt * BLK_T * ntiles; }
+};
+// `count` tile sets of `ntiles` tiles, zeroed (the rows beyond N and the columns beyond nrhs stay zero)
+int group_tiles(mpf_ctx *c, int64_t N, int ntiles, int count, Group &g) {
+    g.ldt = (N + 255) / 256 * 256;
+    g.ntiles = ntiles;
+    const int64_t len = (int64_t)count * g.ldt * BLK_T * ntiles;
+    MPF_HIP_TRY(c, c->blk_tiles.grow(len));
+    g.base = c->blk_tiles;
+    MPF_HIP_TRY(c, hipMemsetAsync(g.base, 0, (size_t)len * sizeof(double), c->stream));
+    return 0;
+}
+// W <- op^-1 W on prepared factors: P^T-free forms, the permutation is applied by the loads and stores around it; Z scratch
+int tile_solve(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t N, bool trans, double *W, double *Z, const Group &g) {
+    int rc = launch_blk_tri(c, LU, ldlu, N, trans ? 2 : 0, W, Z, g.ldt, g.ntiles);
+    return rc ? rc : launch_blk_tri(c, LU, ldlu, N, trans ? 3 : 1, Z, W, g.ldt, g.ntiles);
+}
+// out (tiles) <- op(A)^-1 src (tiles), through W / Z
+int tile_getrs(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t N, bool trans, const double *src, double *out, double *W, double *Z,
+               const Group &g) {
+    const int64_t cols = (int64_t)BLK_T * g.ntiles;
+    int rc = launch_blk_load(c, src, g.ldt, trans ? nullptr : c->perm_buf, N, cols, W, g.ldt, g.ntiles);
+    if (!rc) rc = tile_solve(c, LU, ldlu, N, trans, W, Z, g);
+    if (!rc) rc = launch_blk_store(c, W, g.ldt, trans ? c->perm_buf : nullptr, N, cols, out, g.ldt);
+    return rc;
+}
+int col_norms(mpf_ctx *c, const double *T, const Group &g, int64_t N, int64_t ncols, std::vector<double> &out) {
+    int rc = launch_col_sumsq(c, T, g.ldt, N, ncols, c->blk_part);
+    if (rc) return rc;
+    out.resize((size_t)ncols);
+    MPF_HIP_TRY(c, hipMemcpyAsync(out.data(), c->blk_part, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (auto &v : out) v = std::sqrt(v);
+    return 0;
+}
+int check_args(mpf_ctx *c, const char *who, int32_t trans, int64_t N, int32_t nrhs, int64_t ldlu, int64_t ldb) {
+    if (trans != 0 && trans != 1) c->err = std::string(who) + ": trans must be 0 or 1";
+    else if (N <= 0 || nrhs < 0) c->err = std::string(who) + ": N must be positive, nrhs >= 0";
+    else if (ldlu < N || ldb < N) c->err = std::string(who) + ": leading dimension < N";
+    else return 0;
+    return -1;
+}
+} // namespace
+
+extern "C" {
+
+int mpf_getrs(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv, int64_t N, int32_t nrhs, double *d_B,
+              int64_t ldb) {
+    if (!c) return -1;
+    if (check_args(c, "getrs", trans, N, nrhs, ldlu, ldb)) return -1;
+    if (nrhs == 0) return 0;
+    if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
+    if (rc) return rc;
+    const bool tr = trans == 1;
+    for (int32_t j0 = 0; j0 < nrhs; j0 += GROUP_TILES * BLK_T) {
+        const int64_t ncols = std::min<int64_t>(nrhs - j0, GROUP_TILES * BLK_T);
+        Group g;
+        rc = group_tiles(c, N, (int)((ncols + BLK_T - 1) / BLK_T), 2, g);
+        if (rc) return rc;
+        double *W = g.t(0), *Z = g.t(1), *B = d_B + (int64_t)j0 * ldb;
+        rc = launch_blk_load(c, B, ldb, tr ? nullptr : c->perm_buf, N, ncols, W, g.ldt, g.ntiles);
+        if (!rc) rc = tile_solve(c, d_LU, ldlu, N, tr, W, Z, g);
+        if (!rc) rc = launch_blk_store(c, W, g.ldt, tr ? c->perm_buf : nullptr, N, ncols, B, ldb);
+        if (rc) return rc;
+    }
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return solve_check_waits(c);
+}
+
+int mpf_solve_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
+                       int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_iter, double tol,
+                       mpf_ir_stats *stats) {
+    if (!c) return -1;
+    if (check_args(c, "solve_ir_block", trans, N, nrhs, ldlu, ldb)) return -1;
+    if (lda < N || ldx < N) { c->err = "solve_ir_block: leading dimension < N"; return -1; }
+    if (nrhs == 0) return 0;
+    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X) { c->err = "solve_ir_block: null pointer"; return -1; }
+    if (max_iter > 31) max_iter = 31;
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
+    if (rc) return rc;
+    const bool tr = trans == 1;
+    std::vector<mpf_ir_stats> st((size_t)nrhs);
+    for (int32_t j0 = 0; j0 < nrhs; j0 += GROUP_TILES * BLK_T) {
+        const int64_t ncols = std::min<int64_t>(nrhs - j0, GROUP_TILES * BLK_T);
+        Group g;
+        rc = group_tiles(c, N, (int)((ncols + BLK_T - 1) / BLK_T), 5, g);
+        if (rc) return rc;
+        const int64_t tcols = (int64_t)BLK_T * g.ntiles;
+        double *Bt = g.t(0), *Xt = g.t(1), *R = g.t(2), *W = g.t(3), *Z = g.t(4);
+        MPF_HIP_TRY(c, c->blk_mask.grow(tcols));
+        MPF_HIP_TRY(c, c->blk_part.grow(tcols));   // (also the column norms' output)
+        rc = launch_blk_load(c, d_B + (int64_t)j0 * ldb, ldb, nullptr, N, ncols, Bt, g.ldt, g.ntiles);
+        std::vector<double> nb2, nr;
+        if (!rc) rc = col_norms(c, Bt, g, N, ncols, nb2);
+        if (!rc) rc = tile_getrs(c, d_LU, ldlu, N, tr, Bt, Xt, W, Z, g);   // x0
+        if (rc) return rc;
+        for (auto &v : nb2) if (v == 0) v = 1;
+        std::vector<int> active((size_t)ncols, 1), mask((size_t)tcols, 0);
+        for (int it = 0;; ++it) {
+            rc = launch_blk_residual(c, d_A, lda, N, tr, Xt, Bt, R, g.ldt, g.ntiles);
+            if (!rc) rc = col_norms(c, R, g, N, ncols, nr);
+            if (rc) return rc;
+            bool any = false;
+            for (int64_t j = 0; j < ncols; ++j) {   // ir_core's rules, column by column
+                mask[(size_t)j] = 0;
+                if (!active[(size_t)j]) continue;
+                mpf_ir_stats &s = st[(size_t)(j0 + j)];
+                s.rel_residual = nr[(size_t)j] / nb2[(size_t)j];
+                s.history[it] = s.rel_residual;
+                s.iterations = it;
+                bool stop = false;
+                if (s.rel_residual <= tol) { s.converged = 1; stop = true; }
+                else if (it >= max_iter || !(s.rel_residual == s.rel_residual)) stop = true;
+                else if (it >= 2 && s.history[it] > 0.7 * s.history[it - 1] && s.history[it - 1] > 0.7 * s.history[it - 2]) {
+                    s.stalled = 1;
+                    stop = true;
+                }
+                if (stop) active[(size_t)j] = 0;
+                else { mask[(size_t)j] = 1; any = true; }
+            }
+            if (!any) break;
+            MPF_HIP_TRY(c, hipMemcpyAsync(c->blk_mask, mask.data(), (size_t)tcols * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            rc = tile_getrs(c, d_LU, ldlu, N, tr, R, R, W, Z, g);   // correction d = op^-1 r (into R: r is consumed)
+            if (!rc) rc = launch_blk_masked_axpy(c, R, c->blk_mask, Xt, g.ldt, g.ntiles);
+            if (rc) return rc;
+            MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));   // `mask` is a host vector reused by the next step
+        }
+        rc = launch_blk_store(c, Xt, g.ldt, nullptr, N, ncols, d_X + (int64_t)j0 * ldx, ldx);
+        if (rc) return rc;
+    }
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (auto &s : st) s.ms_total = ms;
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    return solve_check_waits(c);
+}
+
+} // extern "C"

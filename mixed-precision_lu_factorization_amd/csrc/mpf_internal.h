@@ -189,6 +189,10 @@ struct mpf_ctx {
     Buf<double> res_part;              // per-column-chunk partial sums of the residual (deterministic reduction)
     // expert driver (mpf_expert.cpp, solve_ext.hip): partials of the column / row reductions, of the vector reductions, and its vectors
     Buf<double> ext_part, ext_red, ext_vec;
+    // blocked multi-right-hand-side solve (mpf_block.cpp, solve_block.hip): right-hand-side tiles, the residual's partial products, the
+    // per-column refinement mask
+    Buf<double> blk_tiles, blk_part;
+    Buf<int> blk_mask;
     // factored 32x32 diagonal tiles of the fp64 panel, parked here until every workgroup of the sub-panel launches has
     // read the UNfactored tile from the matrix (dpanel.hip); one tile per 32 panel columns, grown on demand
     Buf<double> dtiles;
@@ -390,6 +394,15 @@ int launch_diag_zero(mpf_ctx *c, const double *LU, int64_t ld, int64_t n, double
 int launch_pow2_scale(mpf_ctx *c, const double *m, int64_t n, double *s, double *d_stats);
 int launch_scaled_copy(mpf_ctx *c, const double *A, int64_t lda, const double *r, const double *cs, double *W, int64_t ldw, int64_t m, int64_t n);
 int launch_vscale(mpf_ctx *c, const double *x, const double *s, double alpha, double *y, int64_t n);
+// blocked multi-right-hand-side solve (solve_block.hip).  Tiles: BLK_T columns each, column-major with ld = N rounded up to 256, rows
+// beyond N zero.  launch_blk_tri: which 0 = L, 1 = U, 2 = U^T, 3 = L^T on x (consumed) -> y, factors prepared by launch_trsv_prepare
+constexpr int BLK_T = 32;
+int launch_blk_tri(mpf_ctx *c, const double *LU, int64_t ld, int64_t n, int which, double *x, double *y, int64_t ldt, int ntiles);
+int launch_blk_residual(mpf_ctx *c, const double *A, int64_t lda, int64_t n, bool trans, const double *X, const double *B, double *R,
+                        int64_t ldt, int ntiles);   // R = B - op(A) X
+int launch_blk_load(mpf_ctx *c, const double *src, int64_t lds, const int *perm, int64_t n, int64_t ncols, double *t, int64_t ldt, int ntiles);
+int launch_blk_store(mpf_ctx *c, const double *t, int64_t ldt, const int *perm, int64_t n, int64_t ncols, double *dst, int64_t ldd);
+int launch_blk_masked_axpy(mpf_ctx *c, const double *d, const int *mask, double *x, int64_t ldt, int ntiles);
 
 // ---- host-side helpers shared by the schedules (mpf_host.cpp, mpf_dist.cpp) --------------------------------------------
 struct StreamSwap { // launch_* helpers use c->stream: point it at another stream for a scope
