@@ -53,6 +53,8 @@ const OptDesc kOpts[] = {
     OPT_I(trsm_laswp_fused, "MPF_TRSM_LASWP_FUSED", 0, 1),
     OPT_I(fp64_two_lanes, "MPF_FP64_TWO_LANES", 0, 1 << 30),
     OPT_I(fp64_lane_a_pct, "MPF_FP64_LANE_A_PCT", 20, 90),
+    OPT_I(fp64_pair, "MPF_FP64_PAIR", 0, 1),
+    OPT_L(fp64_pair_min_n, "MPF_FP64_PAIR_MIN_N", 0, 1ll << 40),
     OPT_I(event_timers, "MPF_EVENT_TIMERS", 0, 2),
     OPT_I(dist_world1_loop, "MPF_DIST_WORLD1_LOOP", 0, 1),
     OPT_I(gesv_fp64_tflops, "MPF_GESV_FP64_TFLOPS", 0, 1000),
@@ -645,6 +647,214 @@ static int factor_lookahead(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int
     return rc;
 }
 
+// Hand-over between the paired bulk phase and the one-level loop of factor_lookahead_rm: the first panel the loop runs and the events
+// its first turn waits for (the state of R at a pair boundary is the state the loop expects after a panel's update).
+struct PairHandover {
+    int64_t k0 = 0;                                  // first panel of the one-level loop (its chain is queued: `chain`)
+    hipEvent_t chain = nullptr;                      // chain of panel k0 complete (pivot stream)
+    hipEvent_t doneL = nullptr, doneR = nullptr;     // the last pair's lane updates on the main stream
+    int64_t cm = -1;                                 // the lanes' split column
+};
+
+// Paired bulk phase of the row-major schedule (fp64 mode, while the update is the longer side): the panels run in pairs (k, k1 = k + nb),
+// and everything right of the pair's INNER REGION [k1, k3 = k + 3 nb) is passed over ONCE per pair, by an update with K = 2 nb over
+// [L(k) | L(k1)] and the 512 U rows, instead of once per panel -- per element the same chain c = fma(-a_kk, b_kk, c), kk ascending across
+// the two panels (contract C5): identical bits.  The update kernel pays a fixed time per C tile per pass (load, store, hand-over:
+// 65-67 TFLOP/s at K = 256 against 71 at K = 512 on these operands, profiles/pair_dgemm_probe.log), and a pair halves the passes.
+//   inner region, panel by panel at full height with K = nb as in the one-level loop (helper stream T):
+//     i1(k):  interchange k, TRSM, update on [k1, k2) -> chain k1 may start;  the same on [k2, k3);
+//     i2(k1): interchange k1, TRSM, update on [k2, k3) -> chain k2 may start;
+//   far columns, per column range (X = [k3, k5) that joins the next pair's inner region, lane A = [k5, cm), lane B = [cm, N)), after
+//   chain k1 (helper stream T, under the other lane's update):
+//     interchanges k AND k1 (both before any arithmetic on block row k1: a row of [k1, k2) that has received panel k's update must
+//     not change places with one that has not);  U[k:k1] = L11(k)^-1 R[k:k1];  R[k1:k2] -= L(k)[k1:k2] U[k:k1] (K = nb, 256 rows);
+//     U[k1:k2] = L11(k1)^-1 R[k1:k2];  both U block rows back to A;
+//   main stream: nothing but  X(p) | A(p) | B(p) | X(p + 1) | ...  with K = 2 nb, rows k2 .. N.
+// One row-major image per pair holds both panels' L21, rows k1 .. N, leading dimension 2 nb: L(k) goes in right behind chain k and
+// serves the inner region as it is; the left-hand interchanges are deferred in this schedule, so after chain k1 its rows receive panel
+// k1's interchange (contiguous rows of nb doubles) before the far columns use it, and L(k1) goes in beside it.  Two images alive: the
+// next pair's is written while this pair's lane B still reads.
+// The pivot kernels keep starting at a seam (the first of a pair at B(p - 1) | X(p), the second at A(p) | B(p)), as in the two-lane loop.
+static int factor_rm_pairs(mpf_ctx *c, EvPool &ev, mpf_stats &st, const mpf_opts &o, double *d_A, int64_t lda, int64_t N, int32_t nb,
+                           int32_t *d_ipiv, hipEvent_t init_done, PairHandover &h) {
+    hipStream_t S = c->stream, P = c->pstream, T = c->tstream;
+    double *R = c->r64;
+    const int64_t ldr = N, ldp = 2 * (int64_t)nb;
+    const int pref_win = HP_FP64_WINDOW_ROWS;
+    int rc = 0;
+    hipEvent_t doneX = nullptr, doneA = nullptr, doneB = nullptr;   // the last X, A and B on the main stream
+    int64_t cm = -1;
+    int64_t k = h.k0;
+    // Lane B of a pair is launched one turn late, when the chain that starts at the seam in front of it (the next pair's second panel)
+    // has been queued: the main stream waits for an event the pivot stream records right before its pivot kernel (`ps`), so the pivot
+    // kernel is dispatched first.  Both wait for the same update to end, and a pivot kernel that comes second finds every CU taken
+    // by update workgroups (it needs a CU's whole LDS): measured 2.6 ms instead of 0.7 per kernel of <= 20000 rows.
+    struct { bool valid = false; int64_t k = 0, c_lo = 0, w = 0; double *PI2 = nullptr; hipEvent_t ready = nullptr; } pendB;
+    auto far_update = [&](int64_t kk, double *pi2, int64_t c_lo, int64_t w) -> int {   // rows kk + 2 nb .. N, K = 2 nb
+        const int64_t r0 = kk + 2 * (int64_t)nb;
+        const int e = ev.timed(st.ms_gemm, S, [&] { return launch_dgemm_minus(c, w, N - r0, 2 * nb, R + kk * ldr + c_lo, ldr, pi2, ldp, R + r0 * ldr + c_lo, ldr); });
+        count_gemm(st, o, N - r0, w, 2 * nb);
+        return e;
+    };
+    auto flush_B = [&](hipEvent_t ps) -> int {
+        if (!pendB.valid) return 0;
+        hipStreamWaitEvent(S, pendB.ready, 0);
+        if (ps) hipStreamWaitEvent(S, ps, 0);
+        const int e = far_update(pendB.k, pendB.PI2, pendB.c_lo, pendB.w);
+        doneB = ev.get();
+        hipEventRecord(doneB, S);
+        pendB.valid = false;
+        return e;
+    };
+    for (; rc == 0; k += 2 * (int64_t)nb) {
+        const int64_t k1 = k + nb, k2 = k1 + nb, k3 = k2 + nb, k5 = k3 + 2 * (int64_t)nb;
+        // four full panels and two lanes of at least one tile right of them; the update the longer side; the pivot kernels fit
+        // beside an update (factor_lookahead_rm's two-lane condition)
+        if (k5 + 256 > N || (N - k1) <= c->tune.fp64_pair_min_n) break;
+        if (c->num_cus > 0 && (N - k1 + HP_R - 1) / HP_R > (int64_t)c->num_cus * 4 / 5) break;
+        const int64_t cw = N - k5;
+        bool resplit = false;
+        if (cm < 0 || (cm - k5) * 100 < cw * (c->tune.fp64_lane_a_pct - 10)) {
+            cm = k5 + ((cw * c->tune.fp64_lane_a_pct / 100 + 127) / 128) * 128;
+            if (cm > N - 128) cm = N - 128;
+            resplit = true;
+        }
+        double *Ak = d_A + k * lda + k, *Ak1 = d_A + k1 * lda + k1;
+        double *PI = c->rm_pair + ((k / (2 * nb)) & 1) * N * ldp;      // row r of the image = row k1 + r of the matrix
+        double *PI2 = PI + (int64_t)nb * ldp;                           // its row k2
+        const MovedList *lk = c->lists + (k / nb), *lk1 = c->lists + (k1 / nb);
+        hipEvent_t lt_ready = ev.get(), e1 = ev.get(), inner_done = ev.get(), chain1 = ev.get(), pi_ready = ev.get(), e2 = ev.get(),
+                   chain2 = ev.get(), evX = ev.get(), evA = ev.get(), evB = ev.get(), ps1 = ev.get(), ps2 = ev.get();
+        {   // L(k) into the pair's image, on the pivot stream right behind chain k; lane B of the pair before the last read this image
+            // (the last lane B launched so far: the one of the pair before is still pending)
+            if (doneB) hipStreamWaitEvent(P, doneB, 0);
+            StreamSwap sw(c, P);
+            rc = ev.timed(st.ms_cvt, P, [&] { return launch_transpose64(c, Ak + nb, lda, PI, ldp, N - k1, nb, true); });
+            hipEventRecord(lt_ready, P);
+        }
+        if (rc) break;
+        {   // ---- i1(k): panel k on the inner region [k1, k3), the strip [k1, k2) first ------------------------------------------
+            hipStreamWaitEvent(T, h.chain, 0);
+            hipStreamWaitEvent(T, doneX ? doneX : init_done, 0);
+            StreamSwap sw(c, T);
+            rc = ev.timed(st.ms_laswp, T, [&] { return launch_laswp_from_list_rm64(c, R + k1, ldr, k3 - k1, lk, (int64_t)LASWP_MAXMOVED * k1); });
+            if (!rc) rc = ev.timed(st.ms_trsm, T, [&] { return launch_dtrsm_llnu_strided(c, nb, nb, Ak, lda, R + k * ldr + k1, ldr, 1); });
+            hipStreamWaitEvent(T, lt_ready, 0);
+            if (!rc) rc = ev.timed(st.ms_gemm, T, [&] { return launch_dgemm_minus(c, nb, N - k1, nb, R + k * ldr + k1, ldr, PI, ldp, R + k1 * ldr + k1, ldr); });
+            count_gemm(st, o, N - k1, nb, nb);
+            if (!rc) rc = ev.timed(st.ms_cvt, T, [&] { return launch_transpose64(c, Ak1, lda, R + k1 * ldr + k1, ldr, N - k1, nb, false); });
+            hipEventRecord(e1, T);
+            if (!rc) rc = ev.timed(st.ms_trsm, T, [&] { return launch_dtrsm_llnu_strided(c, nb, nb, Ak, lda, R + k * ldr + k2, ldr, 1); });
+            if (!rc) rc = ev.timed(st.ms_gemm, T, [&] { return launch_dgemm_minus(c, nb, N - k1, nb, R + k * ldr + k2, ldr, PI, ldp, R + k1 * ldr + k2, ldr); });
+            count_gemm(st, o, N - k1, nb, nb);
+            if (!rc) rc = ev.timed(st.ms_cvt, T, [&] { return launch_transpose64(c, d_A + k1 * lda + k, lda, R + k * ldr + k1, ldr, nb, k3 - k1, false); });
+            hipEventRecord(inner_done, T);
+        }
+        if (rc) break;
+        {   // ---- chain k1 on P, from the seam A(p - 1) | B(p - 1); then the image: panel k1's interchange on L(k), L(k1) beside it ----
+            hipStreamWaitEvent(P, e1, 0);
+            if (doneA) hipStreamWaitEvent(P, doneA, 0);
+            hipEventRecord(ps1, P);
+            StreamSwap sw(c, P);
+            rc = ev.timed(st.ms_hpanel, P, [&] {
+                return launch_hgetf2(c, Ak1, lda, nullptr, 0, (int)(N - k1), nb, (int)k1, d_ipiv + k1, nullptr, 0, c->lists + (k1 / nb), 0, pref_win); });
+            if (!rc) rc = ev.timed(st.ms_dpanel, P, [&] {
+                int e = launch_laswp_from_list(c, d_A + k1 * lda, lda, nb, lk1);
+                if (!e) e = launch_dgetf2_npv(c, Ak1, lda, (int)(N - k1), nb, o.fused_panel, (int)k1);
+                return e; });
+            hipEventRecord(chain1, P);
+            st.panels++;
+            hipStreamWaitEvent(P, inner_done, 0);   // the inner region has read L(k) in panel k's row order
+            // (the list holds matrix rows, all of them >= k1: the base is the image's virtual row 0; the scratch of the columns [0, nb) is
+            //  free -- every interchange on R in this phase uses the scratch of its own columns, all right of k1)
+            if (!rc) rc = ev.timed(st.ms_laswp, P, [&] { return launch_laswp_from_list_rm64(c, PI - k1 * ldp, ldp, nb, lk1, 0); });
+            if (!rc) rc = ev.timed(st.ms_cvt, P, [&] { return launch_transpose64(c, Ak1 + nb, lda, PI2 + nb, ldp, N - k2, nb, true); });
+            hipEventRecord(pi_ready, P);
+        }
+        if (!rc) rc = flush_B(ps1);   // B(p - 1), behind chain k1's pivot kernel
+        if (rc) break;
+        {   // ---- i2(k1): panel k1 on [k2, k3) -------------------------------------------------------------------------------------
+            hipStreamWaitEvent(T, chain1, 0);
+            StreamSwap sw(c, T);
+            rc = ev.timed(st.ms_laswp, T, [&] { return launch_laswp_from_list_rm64(c, R + k2, ldr, nb, lk1, (int64_t)LASWP_MAXMOVED * k2); });
+            if (!rc) rc = ev.timed(st.ms_trsm, T, [&] { return launch_dtrsm_llnu_strided(c, nb, nb, Ak1, lda, R + k1 * ldr + k2, ldr, 1); });
+            hipStreamWaitEvent(T, pi_ready, 0);
+            if (!rc) rc = ev.timed(st.ms_gemm, T, [&] { return launch_dgemm_minus(c, nb, N - k2, nb, R + k1 * ldr + k2, ldr, PI2 + nb, ldp, R + k2 * ldr + k2, ldr); });
+            count_gemm(st, o, N - k2, nb, nb);
+            if (!rc) rc = ev.timed(st.ms_cvt, T, [&] { return launch_transpose64(c, d_A + k2 * lda + k2, lda, R + k2 * ldr + k2, ldr, N - k2, nb, false); });
+            hipEventRecord(e2, T);
+            if (!rc) rc = ev.timed(st.ms_cvt, T, [&] { return launch_transpose64(c, d_A + k2 * lda + k1, lda, R + k1 * ldr + k2, ldr, nb, nb, false); });
+        }
+        if (rc) break;
+        {   // ---- chain k2 on P, from the seam B(p - 1) | X(p) --------------------------------------------------------------------------
+            hipStreamWaitEvent(P, e2, 0);
+            if (doneB) hipStreamWaitEvent(P, doneB, 0);
+            hipEventRecord(ps2, P);
+            StreamSwap sw(c, P);
+            double *Ak2 = d_A + k2 * lda + k2;
+            MovedList *ml = c->lists + (k2 / nb);
+            rc = ev.timed(st.ms_hpanel, P, [&] {
+                return launch_hgetf2(c, Ak2, lda, nullptr, 0, (int)(N - k2), nb, (int)k2, d_ipiv + k2, nullptr, 0, ml, 0, pref_win); });
+            if (!rc) rc = ev.timed(st.ms_dpanel, P, [&] {
+                int e = launch_laswp_from_list(c, d_A + k2 * lda, lda, nb, ml);
+                if (!e) e = launch_dgetf2_npv(c, Ak2, lda, (int)(N - k2), nb, o.fused_panel, (int)k2);
+                return e; });
+            hipEventRecord(chain2, P);
+            st.panels++;
+        }
+        if (rc) break;
+        // the small launches of the far columns [c_lo, c_lo + w) on T (behind chain k1 and the image: i2 has waited for both)
+        auto far_prep = [&](int64_t c_lo, int64_t w) -> int {
+            const int64_t off = (int64_t)LASWP_MAXMOVED * c_lo;
+            int e = ev.timed(st.ms_laswp, T, [&] {
+                int e2_ = launch_laswp_from_list_rm64(c, R + c_lo, ldr, w, lk, off);
+                if (!e2_) e2_ = launch_laswp_from_list_rm64(c, R + c_lo, ldr, w, lk1, off);
+                return e2_; });
+            if (!e) e = ev.timed(st.ms_trsm, T, [&] { return launch_dtrsm_llnu_strided(c, nb, w, Ak, lda, R + k * ldr + c_lo, ldr, 1); });
+            if (!e) e = ev.timed(st.ms_gemm, T, [&] { return launch_dgemm_minus(c, w, nb, nb, R + k * ldr + c_lo, ldr, PI, ldp, R + k1 * ldr + c_lo, ldr); });
+            count_gemm(st, o, nb, w, nb);
+            if (!e) e = ev.timed(st.ms_trsm, T, [&] { return launch_dtrsm_llnu_strided(c, nb, w, Ak1, lda, R + k1 * ldr + c_lo, ldr, 1); });
+            if (!e) e = ev.timed(st.ms_cvt, T, [&] { return launch_transpose64(c, d_A + c_lo * lda + k, lda, R + k * ldr + c_lo, ldr, 2 * nb, w, false); });
+            return e;
+        };
+        {   // ---- X and lane A: their columns were in lane A of the pair before (at a re-split: in either lane) -----------------------
+            if (doneA) hipStreamWaitEvent(T, doneA, 0); else hipStreamWaitEvent(T, init_done, 0);
+            if (resplit && doneB) hipStreamWaitEvent(T, doneB, 0);
+            StreamSwap sw(c, T);
+            rc = far_prep(k3, k5 - k3);
+            hipEventRecord(evX, T);
+            if (!rc) rc = far_prep(k5, cm - k5);
+            hipEventRecord(evA, T);
+        }
+        if (rc) break;
+        hipStreamWaitEvent(S, evX, 0);
+        hipStreamWaitEvent(S, ps2, 0);   // X(p) behind chain k2's pivot kernel
+        rc = far_update(k, PI2, k3, k5 - k3);
+        if (rc) break;
+        doneX = ev.get();
+        hipEventRecord(doneX, S);
+        hipStreamWaitEvent(S, evA, 0);
+        rc = far_update(k, PI2, k5, cm - k5);
+        if (rc) break;
+        doneA = ev.get();
+        hipEventRecord(doneA, S);
+        {   // ---- lane B (behind B(p - 1)), under A(p) -----------------------------------------------------------------------------
+            if (doneB) hipStreamWaitEvent(T, doneB, 0);
+            StreamSwap sw(c, T);
+            rc = far_prep(cm, N - cm);
+            hipEventRecord(evB, T);
+        }
+        if (rc) break;
+        pendB.valid = true; pendB.k = k; pendB.PI2 = PI2; pendB.c_lo = cm; pendB.w = N - cm; pendB.ready = evB;
+        h.chain = chain2;
+        if (o.verbose) printf("panels k=%lld, %lld rows=%lld (row-major copy, paired: far update K = %d, lanes split at %lld)\n", (long long)k1, (long long)k2, (long long)(N - k1), 2 * nb, (long long)cm);
+    }
+    if (!rc) rc = flush_B(nullptr);
+    h.k0 = k;
+    h.doneL = doneA; h.doneR = doneB; h.cm = cm;
+    return rc;
+}
+
 // Look-ahead schedule of the fp64 mode on a ROW-MAJOR working copy of the trailing matrix (round 3; default for N >= 8192).
 // In the column-major matrix an interchange costs a 64-byte HBM sector each way for every moved row of every column right of
 // the panel (~36 KB per column per panel, 39 ms of a factorization at N = 32768); the element (i, j) of the copy R lives at
@@ -658,8 +868,9 @@ static int factor_lookahead(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int
 //                 (per element the chain c = fma(-u, l, c), kk ascending: the product of the same two numbers as fma(-l, u, c));
 //                 the next panel's columns go back to A (transpose) before its chain starts.
 // Per element the operations and their order are those of factor_lookahead: bit-identical results (tests).
+// pairs: the panels run through factor_rm_pairs while its conditions hold, this loop takes over at a pair boundary.
 static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, int32_t *d_ipiv,
-                               const mpf_opts &o, mpf_stats &st) {
+                               const mpf_opts &o, mpf_stats &st, bool pairs) {
     hipStream_t S = c->stream, P = c->pstream, T = c->tstream;
     EvPool ev(c);
     ev.keep = &st.ms_gemm;
@@ -708,7 +919,17 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
     hipEvent_t init_done = ev.get();
     hipEventRecord(init_done, S);    // the copy R is complete
     bool was_two = false;
-    for (int64_t k = 0; k < N && rc == 0; k += nb) {
+    int64_t k0 = 0;
+    if (pairs && !rc && !sink && !lp && T && N > 1) {
+        PairHandover h;
+        h.chain = chain_a;
+        rc = factor_rm_pairs(c, ev, st, o, d_A, lda, N, nb, d_ipiv, init_done, h);
+        if (h.k0 > 0) {   // the lanes' last launches are in flight, as after a two-lane turn of the loop below
+            k0 = h.k0; chain_a = h.chain; doneL = h.doneL; doneR = h.doneR; cm = h.cm;
+            was_two = true;
+        }
+    }
+    for (int64_t k = k0; k < N && rc == 0; k += nb) {
         const int pc = (int)((N - k) < nb ? (N - k) : nb);
         if (N - k <= 1 || k + pc >= N) break;
         const int64_t n = N - k - pc;          // trailing size
@@ -1292,6 +1513,11 @@ int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, 
     // of N x N doubles once; ms_total is the factorization)
     const bool use_rm = !generic && sb <= 1 && lookahead && o.trailing == MPF_TRAIL_FP64 && c->tune.fp64_rowmajor &&
                         N >= c->tune.fp64_rowmajor_min_n && N > nb && mpf_ensure_rowmajor_copy(c, N, N, nb) == 0;
+    // the paired bulk phase keeps two row-major images of a pair's L21, [rows][2 nb]; without room for them the one-level loop runs
+    bool use_pairs = use_rm && c->tune.fp64_pair && c->tune.fp64_two_lanes > 0 && c->tstream && nb % 16 == 0 && N > c->tune.fp64_pair_min_n;
+    // (and none while the first pivot kernels need nearly every CU: factor_rm_pairs starts at panel 0 or not at all -- N = 65536 stays one-level)
+    if (use_pairs && c->num_cus > 0 && (N - nb + HP_R - 1) / HP_R > (int64_t)c->num_cus * 4 / 5) use_pairs = false;
+    if (use_pairs && c->rm_pair.grow(4 * N * (int64_t)nb) != hipSuccess) { (void)hipGetLastError(); use_pairs = false; }
     if (c->late && !use_rm) {   // (mpf_factor_host planned on the row-major schedule and it is not the one that runs: everything has to be here first)
         const int e = feed_finish(c);
         c->late = nullptr;
@@ -1301,7 +1527,7 @@ int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, 
     int rc;
     if (generic) rc = factor_generic(c, d_A, lda, N, nb, d_ipiv, o, st, force_generic);
     else if (sb > 1) rc = factor_superpanel(c, d_A, lda, N, nb, d_ipiv, o, st, sb, lookahead);
-    else if (use_rm) rc = factor_lookahead_rm(c, d_A, lda, N, nb, d_ipiv, o, st);
+    else if (use_rm) rc = factor_lookahead_rm(c, d_A, lda, N, nb, d_ipiv, o, st, use_pairs);
     else if (lookahead) rc = factor_lookahead(c, d_A, lda, N, nb, d_ipiv, o, st);
     else {
         mpf_opts o2 = o;
@@ -1345,7 +1571,7 @@ int mpf_trim(mpf_ctx *c) {
     c->host_A.release(); c->host_P.release(); c->host_A0.release();
     sink_trim(c);
     feed_trim(c);
-    c->r64.release(); c->rm_tmp.release(); c->rm_lt.release();
+    c->r64.release(); c->rm_tmp.release(); c->rm_lt.release(); c->rm_pair.release();
     c->w32.release();
     return 0;
 }

@@ -111,6 +111,10 @@ struct MpfTuning {
                                          // trailing updates only (ms_gemm, ms_gemm_big; default), 0 = none; option timeline implies 2
     int fp64_lane_a_pct = 50;            // MPF_FP64_LANE_A_PCT: share of those columns in lane A at a (re-)split; re-split 10 points below.  Lane B's
                                          // update has to cover lane A's small launches of the next panel (measured: 60 % and more lose)
+    int fp64_pair = 1;                   // MPF_FP64_PAIR=0: fp64 row-major schedule passes over the far columns once per panel (K = nb) everywhere; 1: once per
+                                         // panel PAIR (K = 2 nb) while the update is the longer side (factor_rm_pairs; same bits)
+    long long fp64_pair_min_n = 16384;   // MPF_FP64_PAIR_MIN_N: ... that is, while the trailing matrix of the pair's first panel is larger than this (measured at
+                                         // N = 32768: 9216 .. 16384 within 1.5 ms of each other, profiles/pair_ab.log; below, the pair's two chains no longer fit under its update)
 #ifdef MPF_PROBE                         // libmpf_probe.so only (tools/): measured-slower variants and diagnostics
     int hp_stamp = 0;                    // MPF_HP_STAMP=1: cycle-stamped build of the pivot kernel
     int hp_r256_upto = 1 << 30;          // MPF_HP_R256_UPTO: panels above that many rows use 128-row workgroups
@@ -215,6 +219,7 @@ struct mpf_ctx {
     struct RowSink *sink = nullptr;    // mpf_factor_host's block-row copies (rowsink.hip); null until the first call that uses it
     Buf<double> rm_tmp;                // its scratch: moved rows of an interchange (2 * HP_MAXCOLS x N) / the panel's L21 row-major
     Buf<double> rm_lt;                 // L21 of the current panel, row-major [rows][nb]
+    Buf<double> rm_pair;               // paired phase (factor_rm_pairs): two row-major images [rows][2 nb] of a panel pair's [L(k) | L(k + nb)]
     // generic (global-memory) fp16 pivot path, fp16_panel_generic.hip: packed fp16 panel + per-block candidates
     Buf<unsigned short> g16;
     Buf<unsigned long long> gcand;
