@@ -487,7 +487,7 @@ int mpf_factor_dist(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_
         hipEvent_t before_pivots = ev.get();
         hipEventRecord(before_pivots, s);
         const bool lds = !force_generic && hgetf2_lds_eligible(c, pr, pc);
-        // the fp64 panel follows the pivot kernel 32 columns behind on the helper stream (see chain_pipelined in mpf_host.cpp) -- where
+        // the fp64 panel follows the pivot kernel 32 columns behind on the helper stream (see chain_behind in mpf_host.cpp) -- where
         // the panel's workgroups fit beside the gated interchange kernel's, which wait for it while sitting on CUs
         const int waiters = (c->tune.gate_wait_value && c->hp_signal) ? 0 : laswp_gated_grid(pc);
         const bool will_pipe = piped_ok && lds && hgetf2_fits_beside(c, pr, pc, waiters);

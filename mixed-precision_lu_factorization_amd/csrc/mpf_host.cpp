@@ -377,6 +377,23 @@ static int trail_gemm(mpf_ctx *c, const mpf_opts &o, int64_t m, int64_t n, int p
     return launch_dgemm_minus(c, m, n, pc, L21, lda, U12, lda, C, lda);
 }
 
+// ---- pieces the schedules share ----------------------------------------------------------------------------------------
+// what every schedule of one factorization works on (mpf_factor_dev's arguments, the event pool, the statistics)
+struct FactorArgs {
+    mpf_ctx *c; EvPool &ev; mpf_stats &st; const mpf_opts &o;
+    double *d_A; int64_t lda, N; int32_t nb; int32_t *d_ipiv;
+};
+
+// panel rows from which the pivot kernel takes its column-window form (launch_hgetf2's prefer_window_rows): the fp64 schedules only
+static int pref_window_rows(const mpf_opts &o) { return o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0; }
+
+// `into` goes on only behind everything queued on `from` so far
+static void stream_join(EvPool &ev, hipStream_t from, hipStream_t into) {
+    hipEvent_t e = ev.get();
+    hipEventRecord(e, from);
+    hipStreamWaitEvent(into, e, 0);
+}
+
 // Single-stream schedule with a host synchronisation after every phase (per-phase timers).
 static int factor_sync_timed(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, int32_t *d_ipiv,
                              const mpf_opts &o, mpf_stats &st) {
@@ -398,7 +415,7 @@ static int factor_sync_timed(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
         if (pr <= 1) break;                                  // MPF.cu:104 (1x1 tail: nothing to do)
         double *Ap = d_A + k * lda + k;
         MovedList *ml = c->lists + (k / nb);
-        rc = phase(st.ms_hpanel, [&] { return launch_hgetf2(c, Ap, lda, nullptr, 0, pr, pc, (int)k, d_ipiv + k, nullptr, 0, ml, 0, o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0); });
+        rc = phase(st.ms_hpanel, [&] { return launch_hgetf2(c, Ap, lda, nullptr, 0, pr, pc, (int)k, d_ipiv + k, nullptr, 0, ml, 0, pref_window_rows(o)); });
         if (rc) break;
         // MPF.cu:162 on the panel and everything right of it; the columns left of it are deferred (laswp.hip)
         rc = phase(st.ms_laswp, [&] { return launch_laswp_from_list(c, d_A + k * lda, lda, N - k, ml); });
@@ -445,7 +462,7 @@ static int factor_generic(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32
         double *Ap = d_A + k * lda + k;
         rc = ev.timed(st.ms_hpanel, S, [&] {
             if (!force_generic_pivots && hgetf2_lds_eligible(c, pr, pc))
-                return launch_hgetf2(c, Ap, lda, nullptr, 0, pr, pc, (int)k, d_ipiv + k, nullptr, 0, nullptr, 0, o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0);
+                return launch_hgetf2(c, Ap, lda, nullptr, 0, pr, pc, (int)k, d_ipiv + k, nullptr, 0, nullptr, 0, pref_window_rows(o));
             st.pivot_path = 1;
             return launch_hgetf2_generic(c, Ap, lda, nullptr, 0, pr, pc, (int)k, d_ipiv + k, nullptr, 0); });
         if (rc) break;
@@ -480,55 +497,104 @@ static int factor_generic(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32
     return rc;
 }
 
-// The chain of one panel (pivots, interchange of the panel's own columns, fp64 panel) with the fp64 panel FOLLOWING the pivot
-// kernel instead of waiting for it.  The pivot kernel (stream P) publishes its progress every 32 columns; stream T runs, per
-// 32-column sub-panel s: a gate (waits for the pivots of columns < 32 (s + 1)), the reference's sequential interchange of
-// exactly those 32 pivots on the panel's columns (LASWP applied in instalments is LASWP: MPF.cu:47-57), and piece s of the fp64
-// panel -- whose rows below the sub-panel are row-independent, so the swaps still to come only move finished rows around
-// (what LAPACK's blocked dgetf2 does).  Same operations per element as the unpipelined chain: bit-identical.
-// e1: the panel's columns are up to date (recorded on the main stream).  On return *e2p follows the pivot kernel (its moved-row
-// list is complete) and *e2t the last fp64-panel piece.  Falls back to the plain chain (returns 1, nothing launched) when
-// the shape has no pieces or there is no third stream.
-static int chain_pipelined(mpf_ctx *c, EvPool &ev, mpf_stats &st, const mpf_opts &o, double *d_A, int64_t lda, int64_t N, int64_t nx,
-                           int pc2, int32_t *d_ipiv, MovedList *ml, hipEvent_t e1, hipEvent_t *e2p, hipEvent_t *e2t, int *rc_out) {
-    const int np = dgetf2_npv_pieces(c, pc2);
-    if (!c->tune.chain_pipeline || np == 0 || !c->tstream || !c->pstream) return 1;
-    // fp64 mode: while the update is the longer side (large trailing matrix) the chain hides under it anyway, and the extra
-    // launches beside it only cost the update time (measured + 4 ms per factorization): pipeline the chain-bound panels only
-    if (o.trailing == MPF_TRAIL_FP64 && (N - nx) > c->tune.chain_pipeline_below) return 1;
-    // the gated interchange kernel's workgroups wait for the pivot kernel while sitting on CUs: the panel must fit beside them
-    // (else the chain runs unpipelined: nobody waits for a kernel whose workgroups cannot all become resident)
-    const int waiters = (c->tune.gate_wait_value && c->hp_signal) ? 0 : laswp_gated_grid(pc2);   // (a stream that waits holds no CU)
-    if (!hgetf2_fits_beside(c, (int)(N - nx), pc2, waiters)) return 1;
-    const int pref_win = o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0;
-    hipStream_t P = c->pstream, T = c->tstream;
-    double *Anx = d_A + nx * lda + nx;
-    int rc = 0;
-    hipStreamWaitEvent(P, e1, 0);
-    hipStreamWaitEvent(T, e1, 0);
-    {
-        StreamSwap sw(c, P);
-        rc = ev.timed(st.ms_hpanel, P, [&] {
-            return launch_hgetf2(c, Anx, lda, nullptr, 0, (int)(N - nx), pc2, (int)nx, d_ipiv + nx, nullptr, 0, ml, waiters, pref_win); });
-        *e2p = ev.get();
-        hipEventRecord(*e2p, P);
-    }
-    if (!rc) {
-        StreamSwap sw(c, T);
-        rc = ev.timed(st.ms_dpanel, T, [&] {
-            int e = 0;
-            for (int s = 0; s < np && !e; ++s) {
-                e = launch_laswp_block_gated(c, d_A + nx * lda, lda, pc2, (int)nx + 32 * s, 32, d_ipiv + nx + 32 * s, N, 32 * (s + 1));
-                if (!e) e = launch_dgetf2_npv_piece(c, Anx, lda, (int)(N - nx), pc2, o.fused_panel, (int)nx, s);
-            }
-            return e; });
-        *e2t = ev.get();
-        hipEventRecord(*e2t, T);
-    }
-    *rc_out = rc;
-    return 0;
+// The plain chain of the panel at k on stream s: pivot kernel, then the interchange of the panel's own columns and the fp64 panel.
+static int panel_chain(const FactorArgs &f, int64_t k, hipStream_t s) {
+    mpf_ctx *c = f.c;
+    const int pc = (int)((f.N - k) < f.nb ? (f.N - k) : f.nb);
+    const int pr = (int)(f.N - k);
+    if (pr <= 1) return 0;
+    StreamSwap sw(c, s);
+    double *Ak = f.d_A + k * f.lda + k;
+    MovedList *ml = c->lists + (k / f.nb);
+    int e = f.ev.timed(f.st.ms_hpanel, s, [&] {
+        return launch_hgetf2(c, Ak, f.lda, nullptr, 0, pr, pc, (int)k, f.d_ipiv + k, nullptr, 0, ml, 0, pref_window_rows(f.o)); });
+    if (!e) e = f.ev.timed(f.st.ms_dpanel, s, [&] {
+        int e2 = launch_laswp_from_list(c, f.d_A + k * f.lda, f.lda, pc, ml);
+        if (!e2) e2 = launch_dgetf2_npv(c, Ak, f.lda, pr, pc, f.o.fused_panel, (int)k);
+        return e2; });
+    f.st.panels++;
+    return e;
 }
 
+// The chain of the NEXT panel (at nx) on the side streams, behind e1: the panel's columns are up to date (recorded by the caller).
+// What the caller gets back: the launches' error code and the events that mark the chain's end -- `a` alone for the plain chain
+// (on P), `a` and `b` for the pipelined one (`a` follows the pivot kernel on P: its moved-row list is complete; `b` the last
+// fp64-panel piece on T).
+//
+// Pipelined: the fp64 panel FOLLOWS the pivot kernel instead of waiting for it.  The pivot kernel (stream P) publishes its progress
+// every 32 columns; stream T runs, per 32-column sub-panel s: a gate (waits for the pivots of columns < 32 (s + 1)), the reference's
+// sequential interchange of exactly those 32 pivots on the panel's columns (LASWP applied in instalments is LASWP: MPF.cu:47-57),
+// and piece s of the fp64 panel -- whose rows below the sub-panel are row-independent, so the swaps still to come only move finished
+// rows around (what LAPACK's blocked dgetf2 does).  Same operations per element as the plain chain: bit-identical.  The plain
+// chain runs when the shape has no pieces or there is no third stream, and in the two cases below.
+struct ChainEnd { int rc = 0; hipEvent_t a = nullptr, b = nullptr; };
+static ChainEnd chain_behind(const FactorArgs &f, int64_t nx, hipEvent_t e1) {
+    mpf_ctx *c = f.c;
+    EvPool &ev = f.ev;
+    const int64_t N = f.N, lda = f.lda;
+    const int pc2 = (int)((N - nx) < f.nb ? (N - nx) : f.nb);
+    hipStream_t P = c->pstream, T = c->tstream;
+    const int np = dgetf2_npv_pieces(c, pc2);
+    const int waiters = (c->tune.gate_wait_value && c->hp_signal) ? 0 : laswp_gated_grid(pc2);   // (a stream that waits holds no CU)
+    const bool piped = c->tune.chain_pipeline && np != 0 && T && P &&
+        // fp64 mode: while the update is the longer side (large trailing matrix) the chain hides under it anyway, and the extra
+        // launches beside it only cost the update time (measured + 4 ms per factorization): pipeline the chain-bound panels only
+        !(f.o.trailing == MPF_TRAIL_FP64 && (N - nx) > c->tune.chain_pipeline_below) &&
+        // the gated interchange kernel's workgroups wait for the pivot kernel while sitting on CUs: the panel must fit beside them
+        // (else the chain runs unpipelined: nobody waits for a kernel whose workgroups cannot all become resident)
+        hgetf2_fits_beside(c, (int)(N - nx), pc2, waiters);
+    ChainEnd r;
+    hipStreamWaitEvent(P, e1, 0);
+    if (!piped) {
+        r.rc = panel_chain(f, nx, P);
+        r.a = ev.get();
+        hipEventRecord(r.a, P);
+        return r;
+    }
+    hipStreamWaitEvent(T, e1, 0);
+    double *Anx = f.d_A + nx * lda + nx;
+    {
+        StreamSwap sw(c, P);
+        r.rc = ev.timed(f.st.ms_hpanel, P, [&] {
+            return launch_hgetf2(c, Anx, lda, nullptr, 0, (int)(N - nx), pc2, (int)nx, f.d_ipiv + nx, nullptr, 0, c->lists + (nx / f.nb), waiters, pref_window_rows(f.o)); });
+        r.a = ev.get();
+        hipEventRecord(r.a, P);
+    }
+    if (!r.rc) {
+        StreamSwap sw(c, T);
+        r.rc = ev.timed(f.st.ms_dpanel, T, [&] {
+            int e = 0;
+            for (int s = 0; s < np && !e; ++s) {
+                e = launch_laswp_block_gated(c, f.d_A + nx * lda, lda, pc2, (int)nx + 32 * s, 32, f.d_ipiv + nx + 32 * s, N, 32 * (s + 1));
+                if (!e) e = launch_dgetf2_npv_piece(c, Anx, lda, (int)(N - nx), pc2, f.o.fused_panel, (int)nx, s);
+            }
+            return e; });
+        r.b = ev.get();
+        hipEventRecord(r.b, T);
+    }
+    f.st.panels++;
+    return r;
+}
+
+// The end of a look-ahead schedule, once the caller has joined into the main stream whatever its last step there depends on: that
+// step (with a row sink the last block rows leave -- the sink applies the left-hand interchanges on the way out, the device matrix
+// keeps them owed; otherwise the deferred left-hand interchanges run), then the host waits for every stream of the schedule and
+// reports.  rc of a failed launch wins over a stream's error.
+static int factor_epilogue(const FactorArgs &f, int rc, bool sink, int sb, bool side_streams) {
+    mpf_ctx *c = f.c;
+    hipStream_t S = c->stream;
+    const int npanels = (int)((f.N + f.nb - 1) / f.nb);
+    if (sink) sink_notify(c, npanels, S);
+    else if (!rc) rc = f.ev.timed(f.st.ms_laswp, S, [&] { return launch_lazy_left_swaps(c, f.d_A, f.lda, f.N, f.nb, npanels, c->lists, sb); });
+    hipError_t se = sink_stream_wait(c, S);   // (hipStreamSynchronize unless a sink's thread is copying)
+    hipError_t sp = side_streams ? sink_stream_wait(c, c->pstream) : hipSuccess;
+    if (side_streams && c->tstream) { const hipError_t stt = sink_stream_wait(c, c->tstream); if (sp == hipSuccess) sp = stt; }
+    if (!rc && (se != hipSuccess || sp != hipSuccess))
+        return fail(c, -2, std::string("factorization failed: ") + hipGetErrorString(se != hipSuccess ? se : sp));
+    f.ev.collect();
+    f.st.lookahead = side_streams ? 1 : 0;
+    return rc;
+}
 
 // Look-ahead schedule.  Main stream S: trailing updates and the row interchanges of everything outside the
 // next panel.  Side stream P (high priority): the latency-bound chain of the NEXT panel -- fp16 pivots, the
@@ -546,19 +612,16 @@ static int factor_lookahead(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int
     hipStream_t S = c->stream, P = c->pstream;
     EvPool ev(c);
     ev.keep = &st.ms_gemm;
+    const FactorArgs f{c, ev, st, o, d_A, lda, N, nb, d_ipiv};
     int rc = 0;
     const bool sink = sink_take(c, d_A, lda, N, nb);   // (mpf_factor_host: block rows leave as they become final, rowsink.hip)
-    { // P must see everything already queued on S (the input matrix may still be in flight there)
-        hipEvent_t e = ev.get();
-        hipEventRecord(e, S);
-        hipStreamWaitEvent(P, e, 0);
-    }
+    stream_join(ev, S, P);   // P must see everything already queued on S (the input matrix may still be in flight there)
     // panel 0 has nothing to hide under
     {
         const int pc = (int)(N < nb ? N : nb), pr = (int)N;
         if (pr > 1) {
             rc = ev.timed(st.ms_hpanel, S, [&] {
-                int e = launch_hgetf2(c, d_A, lda, nullptr, 0, pr, pc, 0, d_ipiv, nullptr, 0, c->lists, 0, o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0);
+                int e = launch_hgetf2(c, d_A, lda, nullptr, 0, pr, pc, 0, d_ipiv, nullptr, 0, c->lists, 0, pref_window_rows(o));
                 const int64_t first = (int64_t)pc + nb < N ? (int64_t)pc + nb : N; // panel 0 and the strip right of it
                 if (!e) e = launch_laswp_from_list(c, d_A, lda, first, c->lists);
                 if (!e) e = launch_dgetf2_npv(c, d_A, lda, pr, pc, o.fused_panel, 0);
@@ -587,29 +650,12 @@ static int factor_lookahead(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int
         if (rc) break;
         count_gemm(st, o, n, ns, pc);
         if (!has_next) break;
-        hipEvent_t e1 = ev.get(), e2 = ev.get();
+        hipEvent_t e1 = ev.get();
         hipEventRecord(e1, S);
         // ---- side streams: the whole chain of panel k+1 ---------------------------------------------------
-        hipEvent_t e2p = nullptr, e2t = nullptr;
-        int rcp = 0;
-        const bool piped = chain_pipelined(c, ev, st, o, d_A, lda, N, nx, pc2, d_ipiv, c->lists + (nx / nb), e1, &e2p, &e2t, &rcp) == 0;
-        if (piped) rc = rcp;
-        else {
-            hipStreamWaitEvent(P, e1, 0);
-            StreamSwap sw(c, P);
-            double *Anx = d_A + nx * lda + nx;
-            MovedList *ml = c->lists + (nx / nb);
-            rc = ev.timed(st.ms_hpanel, P, [&] {
-                return launch_hgetf2(c, Anx, lda, nullptr, 0, (int)(N - nx), pc2, (int)nx, d_ipiv + nx, nullptr, 0, ml, 0, o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0); });
-            if (!rc) rc = ev.timed(st.ms_dpanel, P, [&] {
-                int e = launch_laswp_from_list(c, d_A + nx * lda, lda, pc2, ml);      // the panel's own columns
-                if (!e) e = launch_dgetf2_npv(c, Anx, lda, (int)(N - nx), pc2, o.fused_panel, (int)nx);
-                return e;
-            });
-        }
+        const ChainEnd next = chain_behind(f, nx, e1);
+        rc = next.rc;
         if (rc) break;
-        if (!piped) hipEventRecord(e2, P);
-        st.panels++;
         // ---- main stream: interchanges of panel k on the columns right of the strip (the strip and the panel had
         //      theirs before the strip update), the rest of update k, then panel k+1's interchanges on the next strip
         if (n > pc2) {
@@ -624,8 +670,8 @@ static int factor_lookahead(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int
             if (rc) break;
             count_gemm(st, o, n, n - pc2, pc);
         }
-        if (piped) { hipStreamWaitEvent(S, e2p, 0); hipStreamWaitEvent(S, e2t, 0); }
-        else hipStreamWaitEvent(S, e2, 0);
+        hipStreamWaitEvent(S, next.a, 0);
+        if (next.b) hipStreamWaitEvent(S, next.b, 0);
         rc = ev.timed(st.ms_laswp, S, [&] { // only the next strip now: it is all the next strip update needs
             const int64_t s0 = nx + pc2;
             const int64_t sw = (N - s0) < nb ? (N - s0) : nb;
@@ -633,18 +679,26 @@ static int factor_lookahead(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int
         });
         if (o.verbose) printf("panel k=%lld rows=%lld cols=%d (look-ahead)\n", (long long)nx, (long long)(N - nx), pc2);
     }
-    if (sink) {   // the last block rows; the sink has applied the left-hand interchanges on the way out, the device matrix keeps them owed
-        hipEvent_t ep = ev.get(); hipEventRecord(ep, P); hipStreamWaitEvent(S, ep, 0);
-        sink_notify(c, (int)((N + nb - 1) / nb), S);
-    } else if (!rc) rc = ev.timed(st.ms_laswp, S, [&] { return launch_lazy_left_swaps(c, d_A, lda, N, nb, (int)((N + nb - 1) / nb), c->lists); });
-    hipError_t se = sink_stream_wait(c, S);
-    hipError_t sp = sink_stream_wait(c, P);
-    if (c->tstream) { const hipError_t stt = sink_stream_wait(c, c->tstream); if (sp == hipSuccess) sp = stt; }
-    if (!rc && (se != hipSuccess || sp != hipSuccess))
-        return fail(c, -2, std::string("factorization failed: ") + hipGetErrorString(se != hipSuccess ? se : sp));
-    ev.collect();
-    st.lookahead = 1;
-    return rc;
+    if (sink) stream_join(ev, P, S);   // the last block rows leave behind the last chain
+    return factor_epilogue(f, rc, sink, 1, true);
+}
+
+// Does the pivot kernel of a panel of `rows` rows fit BESIDE a running update?  It takes one workgroup -- one CU's whole LDS -- per
+// HP_R rows, all resident at once: with (nearly) every CU needed, a small launch or an update workgroup on a few of them would hold
+// all the others spinning until the update has drained (N = 65536 measured 3583 ms with the two lanes from the first panel on
+// against 3336 without).
+static bool pivots_fit_beside_update(const mpf_ctx *c, int64_t rows) {
+    return c->num_cus <= 0 || (rows + HP_R - 1) / HP_R <= (int64_t)c->num_cus * 4 / 5;
+}
+
+// The two column lanes' split of the columns [lo, hi): lane A = [lo, cm) gets option fp64_lane_a_pct of them, in whole 128-column
+// tiles, lane B at least one tile.  A split (cm >= 0) stays until lane A's share has dropped by 10 points.  True at a (re-)split.
+static bool lane_split(const mpf_ctx *c, int64_t lo, int64_t hi, int64_t &cm) {
+    const int64_t cw = hi - lo;
+    if (cm >= 0 && (cm - lo) * 100 >= cw * (c->tune.fp64_lane_a_pct - 10)) return false;
+    cm = lo + ((cw * c->tune.fp64_lane_a_pct / 100 + 127) / 128) * 128;
+    if (cm > hi - 128) cm = hi - 128;
+    return true;
 }
 
 // Hand-over between the paired bulk phase and the one-level loop of factor_lookahead_rm: the first panel the loop runs and the events
@@ -680,7 +734,7 @@ static int factor_rm_pairs(mpf_ctx *c, EvPool &ev, mpf_stats &st, const mpf_opts
     hipStream_t S = c->stream, P = c->pstream, T = c->tstream;
     double *R = c->r64;
     const int64_t ldr = N, ldp = 2 * (int64_t)nb;
-    const int pref_win = HP_FP64_WINDOW_ROWS;
+    const FactorArgs f{c, ev, st, o, d_A, lda, N, nb, d_ipiv};
     int rc = 0;
     hipEvent_t doneX = nullptr, doneA = nullptr, doneB = nullptr;   // the last X, A and B on the main stream
     int64_t cm = -1;
@@ -711,14 +765,8 @@ static int factor_rm_pairs(mpf_ctx *c, EvPool &ev, mpf_stats &st, const mpf_opts
         // four full panels and two lanes of at least one tile right of them; the update the longer side; the pivot kernels fit
         // beside an update (factor_lookahead_rm's two-lane condition)
         if (k5 + 256 > N || (N - k1) <= c->tune.fp64_pair_min_n) break;
-        if (c->num_cus > 0 && (N - k1 + HP_R - 1) / HP_R > (int64_t)c->num_cus * 4 / 5) break;
-        const int64_t cw = N - k5;
-        bool resplit = false;
-        if (cm < 0 || (cm - k5) * 100 < cw * (c->tune.fp64_lane_a_pct - 10)) {
-            cm = k5 + ((cw * c->tune.fp64_lane_a_pct / 100 + 127) / 128) * 128;
-            if (cm > N - 128) cm = N - 128;
-            resplit = true;
-        }
+        if (!pivots_fit_beside_update(c, N - k1)) break;
+        const bool resplit = lane_split(c, k5, N, cm);
         double *Ak = d_A + k * lda + k, *Ak1 = d_A + k1 * lda + k1;
         double *PI = c->rm_pair + ((k / (2 * nb)) & 1) * N * ldp;      // row r of the image = row k1 + r of the matrix
         double *PI2 = PI + (int64_t)nb * ldp;                           // its row k2
@@ -755,15 +803,9 @@ static int factor_rm_pairs(mpf_ctx *c, EvPool &ev, mpf_stats &st, const mpf_opts
             hipStreamWaitEvent(P, e1, 0);
             if (doneA) hipStreamWaitEvent(P, doneA, 0);
             hipEventRecord(ps1, P);
-            StreamSwap sw(c, P);
-            rc = ev.timed(st.ms_hpanel, P, [&] {
-                return launch_hgetf2(c, Ak1, lda, nullptr, 0, (int)(N - k1), nb, (int)k1, d_ipiv + k1, nullptr, 0, c->lists + (k1 / nb), 0, pref_win); });
-            if (!rc) rc = ev.timed(st.ms_dpanel, P, [&] {
-                int e = launch_laswp_from_list(c, d_A + k1 * lda, lda, nb, lk1);
-                if (!e) e = launch_dgetf2_npv(c, Ak1, lda, (int)(N - k1), nb, o.fused_panel, (int)k1);
-                return e; });
+            rc = panel_chain(f, k1, P);
             hipEventRecord(chain1, P);
-            st.panels++;
+            StreamSwap sw(c, P);
             hipStreamWaitEvent(P, inner_done, 0);   // the inner region has read L(k) in panel k's row order
             // (the list holds matrix rows, all of them >= k1: the base is the image's virtual row 0; the scratch of the columns [0, nb) is
             //  free -- every interchange on R in this phase uses the scratch of its own columns, all right of k1)
@@ -790,17 +832,8 @@ static int factor_rm_pairs(mpf_ctx *c, EvPool &ev, mpf_stats &st, const mpf_opts
             hipStreamWaitEvent(P, e2, 0);
             if (doneB) hipStreamWaitEvent(P, doneB, 0);
             hipEventRecord(ps2, P);
-            StreamSwap sw(c, P);
-            double *Ak2 = d_A + k2 * lda + k2;
-            MovedList *ml = c->lists + (k2 / nb);
-            rc = ev.timed(st.ms_hpanel, P, [&] {
-                return launch_hgetf2(c, Ak2, lda, nullptr, 0, (int)(N - k2), nb, (int)k2, d_ipiv + k2, nullptr, 0, ml, 0, pref_win); });
-            if (!rc) rc = ev.timed(st.ms_dpanel, P, [&] {
-                int e = launch_laswp_from_list(c, d_A + k2 * lda, lda, nb, ml);
-                if (!e) e = launch_dgetf2_npv(c, Ak2, lda, (int)(N - k2), nb, o.fused_panel, (int)k2);
-                return e; });
+            rc = panel_chain(f, k2, P);
             hipEventRecord(chain2, P);
-            st.panels++;
         }
         if (rc) break;
         // the small launches of the far columns [c_lo, c_lo + w) on T (behind chain k1 and the image: i2 has waited for both)
@@ -874,6 +907,7 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
     hipStream_t S = c->stream, P = c->pstream, T = c->tstream;
     EvPool ev(c);
     ev.keep = &st.ms_gemm;
+    const FactorArgs f{c, ev, st, o, d_A, lda, N, nb, d_ipiv};
     int rc = 0;
     const bool sink = sink_take(c, d_A, lda, N, nb);   // (mpf_factor_host: block rows leave as they become final, rowsink.hip)
     double *R = c->r64;
@@ -893,7 +927,7 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
         {
             StreamSwap sw(c, P);
             rc = ev.timed(st.ms_hpanel, P, [&] {
-                int e = launch_hgetf2(c, d_A, lda, nullptr, 0, (int)N, pc0, 0, d_ipiv, nullptr, 0, c->lists, 0, o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0);
+                int e = launch_hgetf2(c, d_A, lda, nullptr, 0, (int)N, pc0, 0, d_ipiv, nullptr, 0, c->lists, 0, pref_window_rows(o));
                 if (!e) e = launch_laswp_from_list(c, d_A, lda, pc0, c->lists);
                 if (!e) e = launch_dgetf2_npv(c, d_A, lda, (int)N, pc0, o.fused_panel, 0);
                 return e; });
@@ -940,9 +974,6 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
         double *LT = c->rm_lt + ((k / nb) & 1) * N * (int64_t)nb;
         const int64_t ns = has_next ? pc2 : n; // columns updated before the side stream may start
         MovedList *lk = c->lists + (k / nb);
-        // (not while the next pivot kernel needs (nearly) every CU -- one workgroup, one CU's LDS, per 256 rows: with a small launch or
-        //  an update workgroup on a few of them it would hold all the others spinning until the update has drained: N = 65536 measured
-        //  3583 ms with the lanes from the first panel on against 3336 without)
         // ---- a late column segment is due: it receives the panels [0, k / nb) one after the other on the main stream (behind the updates
         //      queued there), then the loop goes on with the wider matrix ------------------------------------------------------------------
         while (lp && lseg < lp->nseg && (k / nb >= lp->q[lseg] || nx + pc2 > ce || !has_next)) {
@@ -979,16 +1010,10 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
         }
         if (rc) break;
         const int64_t cw = ce - nx - pc2;      // columns right of the strip (that are here)
-        const bool pivots_fit = c->num_cus <= 0 || (N - nx + HP_R - 1) / HP_R <= (int64_t)c->num_cus * 4 / 5;
-        const bool want_two = T && c->tune.fp64_two_lanes > 0 && has_next && pivots_fit && (N - nx) > c->tune.chain_pipeline_below &&
-                              cw >= c->tune.fp64_two_lanes;
-        bool resplit = false;
+        const bool want_two = T && c->tune.fp64_two_lanes > 0 && has_next && pivots_fit_beside_update(c, N - nx) &&
+                              (N - nx) > c->tune.chain_pipeline_below && cw >= c->tune.fp64_two_lanes;
         if (!want_two) cm = -1;
-        else if (cm < 0 || (cm - (nx + pc2)) * 100 < cw * (c->tune.fp64_lane_a_pct - 10)) {   // first split, or lane A's share has dropped
-            cm = nx + pc2 + ((cw * c->tune.fp64_lane_a_pct / 100 + 127) / 128) * 128;
-            if (cm > ce - 128) cm = ce - 128;
-            resplit = true;
-        }
+        const bool resplit = want_two && lane_split(c, nx + pc2, ce, cm);
         if (cm >= 0) {
             // ================================ two lanes ===========================================================================
             const int64_t aw = cm - (nx + pc2);
@@ -1028,18 +1053,8 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
                 // at the seam between R(k - 1) and L(k) instead: the chip is empty, the high-priority kernel takes its CUs first.
                 hipStreamWaitEvent(P, e1, 0);
                 if (doneR) hipStreamWaitEvent(P, doneR, 0);
-                StreamSwap sw(c, P);
-                double *Anx = d_A + nx * lda + nx;
-                MovedList *ml = c->lists + (nx / nb);
-                rc = ev.timed(st.ms_hpanel, P, [&] {
-                    return launch_hgetf2(c, Anx, lda, nullptr, 0, (int)(N - nx), pc2, (int)nx, d_ipiv + nx, nullptr, 0, ml, 0, o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0); });
-                if (!rc) rc = ev.timed(st.ms_dpanel, P, [&] {
-                    int e = launch_laswp_from_list(c, d_A + nx * lda, lda, pc2, ml);      // the panel's own columns
-                    if (!e) e = launch_dgetf2_npv(c, Anx, lda, (int)(N - nx), pc2, o.fused_panel, (int)nx);
-                    return e;
-                });
+                rc = panel_chain(f, nx, P);
                 hipEventRecord(e2, P);
-                st.panels++;
             }
             if (rc) break;
             {
@@ -1077,7 +1092,7 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
         }
         // ==================================== one lane =============================================================================
         if (was_two) {   // the lanes' last small launches and the chain of this panel (the main stream did not wait for either)
-            hipEvent_t et = ev.get(); hipEventRecord(et, T); hipStreamWaitEvent(S, et, 0);
+            stream_join(ev, T, S);
             if (chain_a) hipStreamWaitEvent(S, chain_a, 0);
             if (chain_b) hipStreamWaitEvent(S, chain_b, 0);
             was_two = false;
@@ -1086,9 +1101,7 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
         // (the transposition runs on the pivot stream, idle between two pivot kernels, beside the interchange and the strip's TRSM)
         hipEvent_t lt_ready = ev.get();
         {
-            hipEvent_t eb = ev.get();
-            hipEventRecord(eb, S);                 // chain k is complete (S has waited for it); the update before the last has read this LT image
-            hipStreamWaitEvent(P, eb, 0);
+            stream_join(ev, S, P);                 // chain k is complete (S has waited for it); the update before the last has read this LT image
             StreamSwap sw(c, P);
             rc = ev.timed(st.ms_cvt, P, [&] { return launch_transpose64(c, Ap + pc, lda, LT, pc, n, pc, true); });
             hipEventRecord(lt_ready, P);
@@ -1110,29 +1123,12 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
         // the next panel's columns return to the column-major matrix: rows nx.. (its U rows k..nx follow with the others below)
         rc = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, d_A + nx * lda + nx, lda, R + nx * ldr + nx, ldr, N - nx, pc2, false); });
         if (rc) break;
-        hipEvent_t e1 = ev.get(), e2 = ev.get();
+        hipEvent_t e1 = ev.get();
         hipEventRecord(e1, S);
         // ---- side streams: the whole chain of panel k+1 ---------------------------------------------------------------------
-        hipEvent_t e2p = nullptr, e2t = nullptr;
-        int rcp = 0;
-        const bool piped = chain_pipelined(c, ev, st, o, d_A, lda, N, nx, pc2, d_ipiv, c->lists + (nx / nb), e1, &e2p, &e2t, &rcp) == 0;
-        if (piped) rc = rcp;
-        else {
-            hipStreamWaitEvent(P, e1, 0);
-            StreamSwap sw(c, P);
-            double *Anx = d_A + nx * lda + nx;
-            MovedList *ml = c->lists + (nx / nb);
-            rc = ev.timed(st.ms_hpanel, P, [&] {
-                return launch_hgetf2(c, Anx, lda, nullptr, 0, (int)(N - nx), pc2, (int)nx, d_ipiv + nx, nullptr, 0, ml, 0, o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0); });
-            if (!rc) rc = ev.timed(st.ms_dpanel, P, [&] {
-                int e = launch_laswp_from_list(c, d_A + nx * lda, lda, pc2, ml);      // the panel's own columns
-                if (!e) e = launch_dgetf2_npv(c, Anx, lda, (int)(N - nx), pc2, o.fused_panel, (int)nx);
-                return e;
-            });
-        }
+        const ChainEnd next = chain_behind(f, nx, e1);
+        rc = next.rc;
         if (rc) break;
-        if (!piped) hipEventRecord(e2, P);
-        st.panels++;
         // ---- main stream: the rest of update k; the finished U rows of panel k go back to A -------------------------------------
         if (cw > 0) {
             rc = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu_strided(c, pc, cw, Ap, lda, R + k * ldr + nx + pc2, ldr, 1); });
@@ -1141,9 +1137,7 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
         // (the write-back of the finished U rows runs on the chain's second stream, behind the chain's own launches: nothing
         //  waits for it before the end of the factorization, and the main stream goes straight on to the update)
         if (T) {
-            hipEvent_t eu = ev.get();
-            hipEventRecord(eu, S);
-            hipStreamWaitEvent(T, eu, 0);
+            stream_join(ev, S, T);
             StreamSwap sw(c, T);
             rc = ev.timed(st.ms_cvt, T, [&] { return launch_transpose64(c, d_A + nx * lda + k, lda, R + k * ldr + nx, ldr, pc, ce - nx, false); });
             if (sink && !rc && ce == N) sink_notify(c, (int)(k / nb) + 1, T);
@@ -1157,23 +1151,15 @@ static int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, 
             if (rc) break;
             count_gemm(st, o, n, cw, pc);
         }
-        if (piped) { hipStreamWaitEvent(S, e2p, 0); hipStreamWaitEvent(S, e2t, 0); chain_a = e2p; chain_b = e2t; }
-        else { hipStreamWaitEvent(S, e2, 0); chain_a = e2; chain_b = nullptr; }
+        chain_a = next.a; chain_b = next.b;
+        hipStreamWaitEvent(S, chain_a, 0);
+        if (chain_b) hipStreamWaitEvent(S, chain_b, 0);
         if (o.verbose) printf("panel k=%lld rows=%lld cols=%d (look-ahead, row-major copy)\n", (long long)nx, (long long)(N - nx), pc2);
     }
     if (!rc && lp && lseg < lp->nseg) rc = fail(c, -1, "factor_lookahead_rm: a late column segment was never brought up to date (plan beyond the matrix)");
-    if (T) { hipEvent_t et = ev.get(); hipEventRecord(et, T); hipStreamWaitEvent(S, et, 0); }   // the last U write-backs / lane B
-    { hipEvent_t ep = ev.get(); hipEventRecord(ep, P); hipStreamWaitEvent(S, ep, 0); }
-    if (sink) sink_notify(c, (int)((N + nb - 1) / nb), S);   // the last block rows; the left-hand interchanges stay owed on the device (the sink applies them on the way out)
-    else if (!rc) rc = ev.timed(st.ms_laswp, S, [&] { return launch_lazy_left_swaps(c, d_A, lda, N, nb, (int)((N + nb - 1) / nb), c->lists); });
-    hipError_t se = sink_stream_wait(c, S);
-    hipError_t sp = sink_stream_wait(c, P);
-    if (T) { const hipError_t stt = sink_stream_wait(c, T); if (sp == hipSuccess) sp = stt; }
-    if (!rc && (se != hipSuccess || sp != hipSuccess))
-        return fail(c, -2, std::string("factorization failed: ") + hipGetErrorString(se != hipSuccess ? se : sp));
-    ev.collect();
-    st.lookahead = 1;
-    return rc;
+    if (T) stream_join(ev, T, S);   // the last U write-backs / lane B
+    stream_join(ev, P, S);
+    return factor_epilogue(f, rc, sink, 1, true);
 }
 
 // Two-level schedule (default of the fp16 trailing modes).  The fp16 update streams the trailing matrix through the chip
@@ -1217,6 +1203,7 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
     const bool lanes = Ci != S;
     EvPool ev(c);
     ev.keep = &st.ms_gemm;
+    const FactorArgs f{c, ev, st, o, d_A, lda, N, nb, d_ipiv};
     int rc = 0;
     const bool split = o.trailing == MPF_TRAIL_FP16X3;
     const bool f64 = o.trailing == MPF_TRAIL_FP64;
@@ -1227,48 +1214,23 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
         MPF_HIP_TRY(c, c->w32.grow(N * N));
         W = c->w32;
     }
-    if (overlap) {
-        hipEvent_t e = ev.get();
-        hipEventRecord(e, S);
-        hipStreamWaitEvent(P, e, 0);
-    }
+    if (overlap) stream_join(ev, S, P);
     const int64_t sbw = (int64_t)sb * nb;
     const int kst = (int)((sbw + 63) & ~(int64_t)63);                       // row stride of the far U image (elements)
     const int64_t far_cap = N - (int64_t)(sb + 1) * nb;                     // most far columns any super-panel has
     const int64_t inner_u_off = (!f64 && far_cap > 0) ? far_cap * kst : 0;  // the inner steps' U image lives behind the far image
     const int64_t brow_l_off = (int64_t)N * c->h_kmax;                      // block-row L images: in the rows the image buffers hold beyond N
     auto width = [&](int64_t k) { return (int)((N - k) < nb ? (N - k) : nb); };
-    auto chain = [&](int64_t kx, hipStream_t s) -> int { // pivots, own-column interchanges, fp64 panel of the panel at kx
-        const int pcx = width(kx);
-        const int prx = (int)(N - kx);
-        if (prx <= 1) return 0;
-        StreamSwap sw(c, s);
-        double *Ax = d_A + kx * lda + kx;
-        MovedList *ml = c->lists + (kx / nb);
-        int e = ev.timed(st.ms_hpanel, s, [&] { return launch_hgetf2(c, Ax, lda, nullptr, 0, prx, pcx, (int)kx, d_ipiv + kx, nullptr, 0, ml, 0, o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0); });
-        if (!e) e = ev.timed(st.ms_dpanel, s, [&] {
-            int e2 = launch_laswp_from_list(c, d_A + kx * lda, lda, pcx, ml);
-            if (!e2) e2 = launch_dgetf2_npv(c, Ax, lda, prx, pcx, o.fused_panel, (int)kx);
-            return e2; });
-        st.panels++;
-        return e;
-    };
-    auto side_chain = [&](int64_t kx, hipEvent_t e1, hipEvent_t &e2) -> int { // chain on P (and T) behind E1, E2 behind all of it
-        if (!overlap) return chain(kx, S);
-        e2 = ev.get();
-        if (N - kx > 1) {
-            hipEvent_t e2p = nullptr, e2t = nullptr;
-            int rcp = 0;
-            if (chain_pipelined(c, ev, st, o, d_A, lda, N, kx, width(kx), d_ipiv, c->lists + (kx / nb), e1, &e2p, &e2t, &rcp) == 0) {
-                st.panels++;
-                if (!rcp) { hipStreamWaitEvent(c->tstream, e2p, 0); hipEventRecord(e2, c->tstream); }
-                return rcp;
-            }
+    auto side_chain = [&](int64_t kx, hipEvent_t e1, hipEvent_t &e2) -> int { // chain of the panel at kx (N - kx > 1) behind E1, E2 behind all of it
+        if (!overlap) return panel_chain(f, kx, S);
+        const ChainEnd next = chain_behind(f, kx, e1);
+        e2 = next.a;
+        if (!next.rc && next.b) {   // pipelined: one event behind both of its streams
+            e2 = ev.get();
+            hipStreamWaitEvent(c->tstream, next.a, 0);
+            hipEventRecord(e2, c->tstream);
         }
-        hipStreamWaitEvent(P, e1, 0);
-        int e = chain(kx, P);
-        hipEventRecord(e2, P);
-        return e;
+        return next.rc;
     };
     // one right-looking step of panel k (width pc) on the inner-region columns [col0, col0 + ncols), all in the fp64 matrix, on
     // the inner lane: interchange, TRSM with the panel's L11, K = pc update of the rows below.  need_img: convert the panel's L21
@@ -1280,7 +1242,7 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
         const int64_t mrows = N - k - pc;
         if (mrows <= 0) return 0;
         hipStream_t Is = (lanes && P != S) ? P : Ci;
-        if (Is != Ci) { hipEvent_t e = ev.get(); hipEventRecord(e, Ci); hipStreamWaitEvent(Is, e, 0); }   // the chain of panel k is done (Ci waited for it)
+        if (Is != Ci) stream_join(ev, Ci, Is);   // the chain of panel k is done (Ci waited for it)
         StreamSwap sw(c, Is);
         int e = ev.timed(st.ms_cvt, Is, [&] { return launch_cvt_l21(c, d_A + k * lda + k + pc, lda, mrows, pc, split); });
         if (Is != Ci) { img_ready = ev.get(); hipEventRecord(img_ready, Is); } else img_ready = nullptr;
@@ -1372,7 +1334,7 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
         const int64_t e1 = inner_end(sbw < N ? sbw : N);
         if (use32 && e1 < N) rc = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_f64_f32(c, d_A + e1 * lda, lda, W + e1, ldw, N, N - e1); });
     }
-    if (!rc) rc = chain(0, S);
+    if (!rc) rc = panel_chain(f, 0, S);
     hipEvent_t chain_done = nullptr;       // the chain of the panel the next iteration starts with
     if (lanes) { chain_done = ev.get(); hipEventRecord(chain_done, S); }
     hipEvent_t ni_ready = nullptr;         // the columns that joined the current inner region are back in fp64 and up to date (far lane)
@@ -1440,17 +1402,11 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
         }
         if (stop) break;
     }
-    if (lanes) { hipEvent_t e = ev.get(); hipEventRecord(e, Ci); hipStreamWaitEvent(S, e, 0); if (chain_done) hipStreamWaitEvent(S, chain_done, 0); }
-    if (!rc) rc = ev.timed(st.ms_laswp, S, [&] { return launch_lazy_left_swaps(c, d_A, lda, N, nb, (int)((N + nb - 1) / nb), c->lists, sb); });
-    hipError_t se = hipStreamSynchronize(S);
-    hipError_t sp = overlap ? hipStreamSynchronize(P) : hipSuccess;
-    if (overlap && c->tstream) { const hipError_t stt = hipStreamSynchronize(c->tstream); if (sp == hipSuccess) sp = stt; }
-    if (lanes) { const hipError_t sc = hipStreamSynchronize(Ci); if (sp == hipSuccess) sp = sc; }
-    if (!rc && (se != hipSuccess || sp != hipSuccess))
-        return fail(c, -2, std::string("factorization failed: ") + hipGetErrorString(se != hipSuccess ? se : sp));
-    ev.collect();
-    st.lookahead = overlap ? 1 : 0;
-    return rc;
+    if (lanes) {
+        stream_join(ev, Ci, S);
+        if (chain_done) hipStreamWaitEvent(S, chain_done, 0);
+    }
+    return factor_epilogue(f, rc, false, sb, overlap);   // (the inner lane's stream Ci is S or T: among the streams it waits for)
 }
 
 // buffers of factor_lookahead_rm: the N x N fp64 row-major copy, the interchange scratch (2 * HP_MAXCOLS rows x N) and the
@@ -1516,7 +1472,7 @@ int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, 
     // the paired bulk phase keeps two row-major images of a pair's L21, [rows][2 nb]; without room for them the one-level loop runs
     bool use_pairs = use_rm && c->tune.fp64_pair && c->tune.fp64_two_lanes > 0 && c->tstream && nb % 16 == 0 && N > c->tune.fp64_pair_min_n;
     // (and none while the first pivot kernels need nearly every CU: factor_rm_pairs starts at panel 0 or not at all -- N = 65536 stays one-level)
-    if (use_pairs && c->num_cus > 0 && (N - nb + HP_R - 1) / HP_R > (int64_t)c->num_cus * 4 / 5) use_pairs = false;
+    if (use_pairs && !pivots_fit_beside_update(c, N - nb)) use_pairs = false;
     if (use_pairs && c->rm_pair.grow(4 * N * (int64_t)nb) != hipSuccess) { (void)hipGetLastError(); use_pairs = false; }
     if (c->late && !use_rm) {   // (mpf_factor_host planned on the row-major schedule and it is not the one that runs: everything has to be here first)
         const int e = feed_finish(c);
