@@ -352,6 +352,33 @@ int mpf_solve_ir_block(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t l
                        const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X,
                        int64_t ldx, int32_t max_iter, double tol, mpf_ir_stats *stats);
 
+/* ---- error bounds for solves (build extension; LAPACK dgerfs on the tiles of the blocked solve) -----------------------------------
+ * Refines a solution of op(A) X = B in place and returns, per column, the componentwise backward error berr and a bound ferr on
+ * max_i |x_i - xtrue_i| / max_i |x_i|.  d_X holds a solution on entry (from the blocked solve above, for example); ferr and berr are
+ * HOST arrays of nrhs doubles; stats: nrhs host entries or NULL.  itmax = 0 means LAPACK's 5; larger values are clamped to 31 (fp16
+ * factors can need more than 5 corrections).  The arithmetic is dgerfs's, column by column, with eps = 2^-53, safmin = DBL_MIN,
+ * nz = N + 1, safe1 = nz safmin, safe2 = safe1 / eps:
+ *   r = b - op(A) x, w = |b| + |op(A)| |x| (ONE pass over op(A) for both, on fp64 MFMA);
+ *   berr = max_i (w_i > safe2 ? |r_i| / w_i : (|r_i| + safe1) / (w_i + safe1));
+ *   while berr > eps, 2 berr <= the previous berr (3 at first) and fewer than itmax corrections: x += op(A)^-1 r, again; a NaN berr
+ *   stops the column and is returned;
+ *   w_i <- |r_i| + nz eps w_i (+ safe1 where w_i was <= safe2); est = dlacn2's estimate of || op(A)^-1 diag(w) ||_inf;
+ *   ferr = est / max_i |x_i| (est when that is 0).
+ * All columns of a group run the refinement and dlacn2 in lock-step: every product is one pass over the factors for the group, a
+ * column that has stopped is frozen.  Every sum has one fixed order: X[:, j], ferr[j], berr[j], iterations and lacn2_iterations
+ * have the same bits whatever the other columns, nrhs or j's position, and two calls return the same bits.
+ * nrhs = 0: returns 0, no work.  Rows N .. ld - 1 of d_X are not touched.  Synchronises; -4 as the other solves. */
+typedef struct mpf_gerfs_stats {
+    int32_t iterations;        /* corrections this column received (0 .. itmax) */
+    int32_t lacn2_iterations;  /* dlacn2's count for this column (2 .. 5; 1 for N = 1) */
+    int32_t solves;            /* tile solves (op(A)^-1 or op(A)^-T passes) the column's group went through */
+    int32_t reserved;
+    double ms_total;           /* wall time of the whole call, the same for every column */
+} mpf_gerfs_stats;
+int mpf_gerfs(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu,
+              const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+              int32_t itmax, double *ferr, double *berr, mpf_gerfs_stats *stats);
+
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block
  * b / world; d_Aloc is the rank's N x (local columns) column-major matrix (ldloc >= N), d_ipiv the full pivot vector (N int32,

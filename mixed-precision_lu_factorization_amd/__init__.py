@@ -32,7 +32,7 @@ C_ABI_SYMBOLS = [
     "mpf_solve_ir_dist", "mpf_rccl_selftest", "mpf_check_plu_dev", "mpf_check_plu_host", "mpf_solve_ir_nrhs",
     "mpf_solve_gmres_ir", "mpf_trim", "mpf_dist_set_p2p",
     "mpf_solve_ir_trans", "mpf_lange", "mpf_geequ", "mpf_gecon", "mpf_gesvx",
-    "mpf_getrs", "mpf_solve_ir_block",
+    "mpf_getrs", "mpf_solve_ir_block", "mpf_gerfs",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -89,6 +89,11 @@ class MpfGesvxStats(C.Structure):
                 ("rowcnd", C.c_double), ("colcnd", C.c_double), ("amax", C.c_double), ("anorm", C.c_double), ("kappa_max", C.c_double),
                 ("rcond_lowp", C.c_double), ("rcond", C.c_double), ("ms_equilibrate", C.c_double), ("ms_factor", C.c_double),
                 ("ms_gecon", C.c_double), ("ms_ir", C.c_double), ("ms_total", C.c_double), ("ir_lowp", MpfIrStats), ("ir_final", MpfIrStats)]
+
+
+class MpfGerfsStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("lacn2_iterations", C.c_int32), ("solves", C.c_int32), ("reserved", C.c_int32),
+                ("ms_total", C.c_double)]
 
 
 BCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)
@@ -170,6 +175,8 @@ def load_library(probe=False):
     L.mpf_gesvx.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, vp, i32, i32, i32, dbl, i32, dbl, vp, vp, C.POINTER(MpfGesvxStats)]
     L.mpf_getrs.argtypes = [vp, i32, vp, i64, vp, i64, i32, vp, i64]
     L.mpf_solve_ir_block.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, dbl, C.POINTER(MpfIrStats)]
+    L.mpf_gerfs.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, C.POINTER(dbl), C.POINTER(dbl),
+                            C.POINTER(MpfGerfsStats)]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -709,3 +716,29 @@ class MPFContext:
                                        nrhs, _ptr(B), ldb, _ptr(X), ldx, max_iter, tol, st)
         self._check(rc, "mpf_solve_ir_block")
         return X, list(st)[:nrhs]
+
+    # ---- error bounds for solves (include/mpf_c.h: mpf_gerfs) -------------------------------------------------------------------
+    def gerfs(self, A, LU, ipiv, B, X, trans=False, itmax=0, overwrite=False):
+        """mpf_gerfs (LAPACK dgerfs): refines the solution X of op(A) X = B and returns (X, ferr, berr, stats) -- ferr and berr numpy
+        arrays with one entry per column, stats a list per column.  X is copied first and B, X stay untouched, unless
+        overwrite=True: then X itself is refined in place and returned.  itmax = 0: LAPACK's 5 corrections at most."""
+        import numpy as np
+        self._bind()
+        n = A.shape[0]
+        if overwrite:
+            Xr = X
+        elif X.dim() == 1:
+            Xr = X.clone()
+        else:
+            Xr = self.colmajor(n, X.shape[1])
+            Xr.copy_(X)
+        _, nrhs, ldb = self._rhs(B)
+        _, nx, ldx = self._rhs(Xr)
+        assert nx == nrhs, "gerfs: B and X need the same number of columns"
+        ferr, berr = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+        st = (MpfGerfsStats * max(nrhs, 1))()
+        dp = C.POINTER(C.c_double)
+        rc = self.L.mpf_gerfs(self.h, int(bool(trans)), _ptr(A), _colmajor_ld(A), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n, nrhs,
+                              _ptr(B), ldb, _ptr(Xr), ldx, int(itmax), ferr.ctypes.data_as(dp), berr.ctypes.data_as(dp), st)
+        self._check(rc, "mpf_gerfs")
+        return Xr, ferr[:nrhs], berr[:nrhs], list(st)[:nrhs]

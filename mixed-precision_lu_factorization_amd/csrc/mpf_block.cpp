@@ -1,14 +1,16 @@
 // Blocked multi-right-hand-side solve (no reference counterpart; LAPACK dgetrs and block refinement):
 //   mpf_getrs            B := A^-1 B or A^-T B with the factors of mpf_factor_dev
 //   mpf_solve_ir_block   fp64 refinement of all columns together, per-column rules and stats of mpf_solve_ir_nrhs / _trans
+//   mpf_gerfs            LAPACK dgerfs: refinement by the componentwise backward error, berr and the forward bound ferr per column
 // The right-hand sides go through the device in groups of at most GROUP_TILES tiles of BLK_T columns (solve_block.hip); every
 // triangular step and every residual is one pass over the factor block / over A for the whole group.
 #include "mpf_internal.h"
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 
 namespace {
-constexpr int GROUP_TILES = 16;   // 512 columns per group: five N x 512 tiles of scratch at most
+constexpr int GROUP_TILES = 16;   // 512 columns per group: six N x 512 tile sets of scratch at most (mpf_gerfs; 805 MB at N = 32768)
 
 struct Group {
     int64_t ldt = 0;   // rows of a tile (N rounded up to 256)
@@ -47,6 +49,16 @@ int col_norms(mpf_ctx *c, const double *T, const Group &g, int64_t N, int64_t nc
     MPF_HIP_TRY(c, hipMemcpyAsync(out.data(), c->blk_part, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (auto &v : out) v = std::sqrt(v);
+    return 0;
+}
+// one per-column reduction of a step (launch_blk_col_reduce) back on the host: `nvals` values per column, out[v * ncols + j]
+int col_reduce(mpf_ctx *c, int what, const double *T, const Group &g, int64_t N, int64_t ncols, const double *sg, const int *at, int nvals,
+               std::vector<double> &out) {
+    int rc = launch_blk_col_reduce(c, what, T, g.ldt, N, ncols, sg, at);
+    if (rc) return rc;
+    out.resize((size_t)(nvals * ncols));
+    MPF_HIP_TRY(c, hipMemcpyAsync(out.data(), c->blk_red, out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 int check_args(mpf_ctx *c, const char *who, int32_t trans, int64_t N, int32_t nrhs, int64_t ldlu, int64_t ldb) {
@@ -147,6 +159,169 @@ int mpf_solve_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda
         }
         rc = launch_blk_store(c, Xt, g.ldt, nullptr, N, ncols, d_X + (int64_t)j0 * ldx, ldx);
         if (rc) return rc;
+    }
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (auto &s : st) s.ms_total = ms;
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    return solve_check_waits(c);
+}
+
+int mpf_gerfs(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
+              int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *ferr,
+              double *berr, mpf_gerfs_stats *stats) {
+    if (!c) return -1;
+    if (check_args(c, "gerfs", trans, N, nrhs, ldlu, ldb)) return -1;
+    if (lda < N || ldx < N) { c->err = "gerfs: leading dimension < N"; return -1; }
+    if (nrhs == 0) return 0;
+    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !ferr || !berr) { c->err = "gerfs: null pointer"; return -1; }
+    if (itmax <= 0) itmax = 5;
+    if (itmax > 31) itmax = 31;
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
+    if (rc) return rc;
+    const bool tr = trans == 1;
+    // LAPACK's constants: dlamch('E') is the relative machine epsilon 2^-53, not the spacing DBL_EPSILON
+    const double eps = 0x1p-53, safmin = DBL_MIN, nz = (double)(N + 1), safe1 = nz * safmin, safe2 = safe1 / eps;
+    constexpr int LACN2_ITMAX = 5;
+    std::vector<mpf_gerfs_stats> st((size_t)nrhs);
+    for (int32_t j0 = 0; j0 < nrhs; j0 += GROUP_TILES * BLK_T) {
+        const int64_t ncols = std::min<int64_t>(nrhs - j0, GROUP_TILES * BLK_T);
+        Group g;
+        rc = group_tiles(c, N, (int)((ncols + BLK_T - 1) / BLK_T), 6, g);
+        if (rc) return rc;
+        const int64_t tcols = (int64_t)BLK_T * g.ntiles;
+        // Bt and R are free once the weights of the forward bound stand in Wt: dlacn2's vector and its stored signs take their place
+        double *Bt = g.t(0), *Xt = g.t(1), *R = g.t(2), *Wt = g.t(3), *S1 = g.t(4), *S2 = g.t(5), *V = Bt, *Isgn = R;
+        MPF_HIP_TRY(c, c->blk_mask.grow(tcols));
+        MPF_HIP_TRY(c, c->blk_colarg.grow(2 * tcols));
+        int *d_kind = c->blk_colarg, *d_at = d_kind + tcols;
+        std::vector<int> mask((size_t)tcols, 0), arg((size_t)(2 * tcols), 0);
+        int *kind = arg.data(), *at = kind + tcols;
+        std::vector<double> red;
+        int solves = 0;
+        auto upload = [&](int *dst, const std::vector<int> &src) {   // (the step's read-back synchronises before `src` changes again)
+            MPF_HIP_TRY(c, hipMemcpyAsync(dst, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            return 0;
+        };
+        rc = launch_blk_load(c, d_B + (int64_t)j0 * ldb, ldb, nullptr, N, ncols, Bt, g.ldt, g.ntiles);
+        if (!rc) rc = launch_blk_load(c, d_X + (int64_t)j0 * ldx, ldx, nullptr, N, ncols, Xt, g.ldt, g.ntiles);
+        if (rc) return rc;
+
+        // ---- refinement (dgerfs's loop, every column by its own berr; `count` is the same for all columns still refining) ----
+        std::vector<double> lstres((size_t)ncols, 3.0);
+        std::vector<int> active((size_t)ncols, 1);
+        for (int count = 1;; ++count) {
+            rc = launch_blk_residual_bound(c, d_A, lda, N, tr, Xt, Bt, R, Wt, S1, g.ldt, g.ntiles, safe1, safe2);
+            if (!rc) rc = col_reduce(c, 0, S1, g, N, ncols, nullptr, nullptr, 1, red);
+            if (rc) return rc;
+            bool any = false;
+            for (int64_t j = 0; j < ncols; ++j) {
+                mask[(size_t)j] = 0;
+                if (!active[(size_t)j]) continue;
+                const double be = red[(size_t)j];
+                berr[j0 + j] = be;
+                if (be > eps && 2.0 * be <= lstres[(size_t)j] && count <= itmax) {   // (false for a NaN)
+                    lstres[(size_t)j] = be;
+                    st[(size_t)(j0 + j)].iterations = count;
+                    mask[(size_t)j] = 1;
+                    any = true;
+                } else active[(size_t)j] = 0;
+            }
+            if (!any) break;
+            rc = upload(c->blk_mask, mask);
+            if (!rc) rc = tile_getrs(c, d_LU, ldlu, N, tr, R, R, S1, S2, g);   // d = op(A)^-1 r (into R: the next pass rebuilds r)
+            if (!rc) rc = launch_blk_masked_axpy(c, R, c->blk_mask, Xt, g.ldt, g.ntiles);
+            if (rc) return rc;
+            ++solves;
+        }
+        // a stopped column's x did not change any more, so the last pass left its last r and w (the same bits as when it stopped)
+        rc = launch_blk_store(c, Xt, g.ldt, nullptr, N, ncols, d_X + (int64_t)j0 * ldx, ldx);
+        if (!rc) rc = col_reduce(c, 0, Xt, g, N, ncols, nullptr, nullptr, 1, red);
+        if (rc) return rc;
+        const std::vector<double> xmax(red.begin(), red.begin() + ncols);
+
+        // ---- forward bound: dlacn2 on (op(A)^-1 diag(w))^T, all columns in lock-step ----------------------------------------
+        rc = launch_blk_ferr_weight(c, R, Wt, N, ncols, g.ldt, nz * eps, safe1, safe2);
+        if (rc) return rc;
+        auto kase1 = [&]() {   // v <- w .* (op(A)^-T v)
+            ++solves;
+            int r2 = tile_getrs(c, d_LU, ldlu, N, !tr, V, V, S1, S2, g);
+            return r2 ? r2 : launch_blk_scale(c, V, Wt, g.ldt, g.ntiles);
+        };
+        auto kase2 = [&]() {   // v <- op(A)^-1 (w .* v)
+            ++solves;
+            int r2 = launch_blk_scale(c, V, Wt, g.ldt, g.ntiles);
+            return r2 ? r2 : tile_getrs(c, d_LU, ldlu, N, tr, V, V, S1, S2, g);
+        };
+        auto fill = [&]() {
+            int r2 = upload(d_kind, arg);
+            return r2 ? r2 : launch_blk_lacn2_fill(c, V, N, ncols, g.ldt, d_kind, d_at);
+        };
+        auto sign = [&]() {   // live columns: v = isgn = sign(v); the others: v = 0
+            int r2 = upload(c->blk_mask, mask);
+            return r2 ? r2 : launch_blk_lacn2_sign(c, V, Isgn, N, ncols, g.ldt, c->blk_mask);
+        };
+        std::vector<double> est((size_t)ncols, 0.0);
+        std::vector<int> iter((size_t)ncols, 1);
+        std::fill(mask.begin(), mask.end(), 0);
+        for (int64_t j = 0; j < tcols; ++j) { kind[j] = j < ncols ? 0 : -1; at[j] = 0; }
+        rc = fill();
+        if (!rc) rc = kase1();
+        if (!rc) rc = col_reduce(c, 1, V, g, N, ncols, Isgn, nullptr, 2, red);
+        if (rc) return rc;
+        for (int64_t j = 0; j < ncols; ++j) est[(size_t)j] = red[(size_t)j];
+        if (N > 1) {
+            for (int64_t j = 0; j < ncols; ++j) mask[(size_t)j] = 1;   // (mask = the columns still in dlacn2's loop)
+            rc = sign();
+            if (!rc) rc = kase2();
+            if (!rc) rc = col_reduce(c, 2, V, g, N, ncols, nullptr, d_at, 3, red);
+            if (rc) return rc;
+            for (int64_t j = 0; j < ncols; ++j) { at[j] = (int)red[(size_t)(ncols + j)]; iter[(size_t)j] = 2; }
+            for (;;) {
+                for (int64_t j = 0; j < ncols; ++j) kind[j] = mask[(size_t)j] ? 1 : 3;
+                rc = fill();
+                if (!rc) rc = kase1();
+                if (!rc) rc = col_reduce(c, 1, V, g, N, ncols, Isgn, nullptr, 2, red);
+                if (rc) return rc;
+                bool any = false;
+                for (int64_t j = 0; j < ncols; ++j) {
+                    if (!mask[(size_t)j]) continue;
+                    const double estold = est[(size_t)j];
+                    est[(size_t)j] = red[(size_t)j];
+                    if (red[(size_t)(ncols + j)] == 0 || est[(size_t)j] <= estold) mask[(size_t)j] = 0;   // repeated signs, or no growth
+                    else any = true;
+                }
+                if (!any) break;
+                rc = sign();
+                if (!rc) rc = kase2();
+                if (!rc) rc = col_reduce(c, 2, V, g, N, ncols, nullptr, d_at, 3, red);   // (d_at still holds jlast)
+                if (rc) return rc;
+                any = false;
+                for (int64_t j = 0; j < ncols; ++j) {
+                    if (!mask[(size_t)j]) continue;
+                    at[j] = (int)red[(size_t)(ncols + j)];
+                    if (red[(size_t)(2 * ncols + j)] != red[(size_t)j] && iter[(size_t)j] < LACN2_ITMAX) { ++iter[(size_t)j]; any = true; }
+                    else mask[(size_t)j] = 0;
+                }
+                if (!any) break;
+            }
+            for (int64_t j = 0; j < ncols; ++j) kind[j] = 2;   // final stage: the alternating vector
+            rc = fill();
+            if (!rc) rc = kase1();
+            if (!rc) rc = col_reduce(c, 1, V, g, N, ncols, Isgn, nullptr, 2, red);
+            if (rc) return rc;
+            for (int64_t j = 0; j < ncols; ++j) {
+                const double temp = 2.0 * (red[(size_t)j] / (double)(3 * N));
+                if (temp > est[(size_t)j]) est[(size_t)j] = temp;
+            }
+        }
+        for (int64_t j = 0; j < ncols; ++j) {
+            ferr[j0 + j] = xmax[(size_t)j] != 0 ? est[(size_t)j] / xmax[(size_t)j] : est[(size_t)j];
+            st[(size_t)(j0 + j)].lacn2_iterations = iter[(size_t)j];
+            st[(size_t)(j0 + j)].solves = solves;
+        }
     }
     MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -197,6 +197,9 @@ struct mpf_ctx {
     // per-column refinement mask
     Buf<double> blk_tiles, blk_part;
     Buf<int> blk_mask;
+    // error bounds (mpf_gerfs, solve_bounds.hip): results + partials of the per-column reductions, per-column arguments of the dlacn2 steps
+    Buf<double> blk_red;
+    Buf<int> blk_colarg;
     // factored 32x32 diagonal tiles of the fp64 panel, parked here until every workgroup of the sub-panel launches has
     // read the UNfactored tile from the matrix (dpanel.hip); one tile per 32 panel columns, grown on demand
     Buf<double> dtiles;
@@ -408,6 +411,16 @@ int launch_blk_residual(mpf_ctx *c, const double *A, int64_t lda, int64_t n, boo
 int launch_blk_load(mpf_ctx *c, const double *src, int64_t lds, const int *perm, int64_t n, int64_t ncols, double *t, int64_t ldt, int ntiles);
 int launch_blk_store(mpf_ctx *c, const double *t, int64_t ldt, const int *perm, int64_t n, int64_t ncols, double *dst, int64_t ldd);
 int launch_blk_masked_axpy(mpf_ctx *c, const double *d, const int *mask, double *x, int64_t ldt, int ntiles);
+// error bounds (mpf_gerfs).  R = B - op(A) X, W = |B| + |op(A)| |X|, Q = dgerfs's backward-error ratio per element: one pass over op(A)
+int launch_blk_residual_bound(mpf_ctx *c, const double *A, int64_t lda, int64_t n, bool trans, const double *X, const double *B, double *R,
+                              double *W, double *Q, int64_t ldt, int ntiles, double safe1, double safe2);
+// solve_bounds.hip: per-column reductions into c->blk_red (what: 0 max |t|, 1 sum |t| + sign mismatches against sg, 2 first argmax |t| +
+// T[at[col], col]) and the elementwise steps of the batched dlacn2
+int launch_blk_col_reduce(mpf_ctx *c, int what, const double *T, int64_t ldt, int64_t n, int64_t ncols, const double *sg, const int *at);
+int launch_blk_scale(mpf_ctx *c, double *v, const double *w, int64_t ldt, int ntiles);
+int launch_blk_ferr_weight(mpf_ctx *c, const double *r, double *w, int64_t n, int64_t ncols, int64_t ldt, double nzeps, double safe1, double safe2);
+int launch_blk_lacn2_fill(mpf_ctx *c, double *v, int64_t n, int64_t ncols, int64_t ldt, const int *kind, const int *at);
+int launch_blk_lacn2_sign(mpf_ctx *c, double *v, double *isgn, int64_t n, int64_t ncols, int64_t ldt, const int *live);
 
 // ---- host-side helpers shared by the schedules (mpf_host.cpp, mpf_dist.cpp) --------------------------------------------
 struct StreamSwap { // launch_* helpers use c->stream: point it at another stream for a scope

@@ -22,10 +22,18 @@ static_assert(TW % BK == 0 && BK % 4 == 0, "a diagonal block is a whole number o
 
 // O = (or -=) op(F)[m0 .. m0 + 64, k0 .. k1) Y[k0 .. k1, tile] (k0 = blockIdx.z * kc, k1 = min(kw, k0 + kc)); rows of O from mlim
 // on are neither read nor written, op(F) and Y read as zero from k1 on.  O of chunk z at O + z * ozs.
-template <bool TR, bool SUB>
+// ABS (the fused residual and bound of mpf_gerfs): a second accumulator pair takes |op(F)| |Y| from the same staged operands and goes
+// to Oa (same layout as O).  Its plain product is summed in TWO levels: every staged chunk of BK = 32 k starts from zero and is then
+// added to a running total (chunks ascending).  The componentwise backward error is measured against the residual's own rounding: one
+// chain of 4096 accumulations reads 4 .. 5 x 2^-53 for an x that is correct to working precision, the two-level sum 0.9 (a BLAS
+// product: 2.3), and dgerfs's stop rule and the caller both act on that figure.  So O's bits are NOT those of the kernel without ABS
+// (launch_blk_residual); each form has one fixed order of its own.
+template <bool TR, bool SUB, bool ABS = false>
 __global__ __launch_bounds__(256) void blk_gemm_kernel(const double *__restrict__ F, long long ldf, long long fr0, long long fc0,
                                                        long long kw, long long kc, long long mlim, const double *__restrict__ Y,
-                                                       long long ldy, double *__restrict__ O, long long ldo, long long ozs) {
+                                                       long long ldy, double *__restrict__ O, long long ldo, long long ozs,
+                                                       double *__restrict__ Oa = nullptr) {
+    static_assert(!(ABS && SUB), "the bound is a plain product");
     __shared__ double As[BK][BM + 1], Ys[BK][BT + 1];
     const int tid = threadIdx.x, l = tid & 63, g = tid >> 6;
     const long long m0 = (long long)blockIdx.x * BM;
@@ -50,6 +58,7 @@ __global__ __launch_bounds__(256) void blk_gemm_kernel(const double *__restrict_
         }
     };
     d4_t acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+    d4_t abs0 = {0.0, 0.0, 0.0, 0.0}, abs1 = {0.0, 0.0, 0.0, 0.0}, tot0 = {0.0, 0.0, 0.0, 0.0}, tot1 = {0.0, 0.0, 0.0, 0.0};
     if (k0 < k1) fetch(k0);
     for (long long kk = k0; kk < k1; kk += BK) {
 #pragma unroll
@@ -68,6 +77,14 @@ __global__ __launch_bounds__(256) void blk_gemm_kernel(const double *__restrict_
             const double a = As[kr][16 * g + (l & 15)];
             acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Ys[kr][l & 15], acc0, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Ys[kr][16 + (l & 15)], acc1, 0, 0, 0);
+            if (ABS) {
+                abs0 = __builtin_amdgcn_mfma_f64_16x16x4f64(fabs(a), fabs(Ys[kr][l & 15]), abs0, 0, 0, 0);
+                abs1 = __builtin_amdgcn_mfma_f64_16x16x4f64(fabs(a), fabs(Ys[kr][16 + (l & 15)]), abs1, 0, 0, 0);
+            }
+        }
+        if (ABS) {   // second level of the plain product's sum
+            tot0 += acc0; tot1 += acc1;
+            acc0 = d4_t{0.0, 0.0, 0.0, 0.0}; acc1 = d4_t{0.0, 0.0, 0.0, 0.0};
         }
         __syncthreads();
     }
@@ -79,17 +96,23 @@ __global__ __launch_bounds__(256) void blk_gemm_kernel(const double *__restrict_
         if (row >= mlim) continue;
         double *o0 = Ot + row + (long long)(l & 15) * ldo, *o1 = o0 + 16ll * ldo;
         if (SUB) { *o0 = *o0 - acc0[i]; *o1 = *o1 - acc1[i]; }
+        else if (ABS) { *o0 = tot0[i]; *o1 = tot1[i]; }
         else { *o0 = acc0[i]; *o1 = acc1[i]; }
+        if (ABS) {
+            double *a0 = Oa + (long long)blockIdx.z * ozs + col0 * ldo + row + (long long)(l & 15) * ldo;
+            a0[0] = abs0[i];
+            a0[16ll * ldo] = abs1[i];
+        }
     }
 }
 
-template <bool TR, bool SUB>
+template <bool TR, bool SUB, bool ABS = false>
 static int blk_gemm(mpf_ctx *c, const double *F, int64_t ldf, int64_t fr0, int64_t fc0, int64_t kw, int64_t kc, int64_t mlim,
-                    const double *Y, int64_t ldy, double *O, int64_t ldo, int64_t ozs, int ntiles) {
+                    const double *Y, int64_t ldy, double *O, int64_t ldo, int64_t ozs, int ntiles, double *Oa = nullptr) {
     if (mlim <= 0 || kw <= 0) return 0;
     const int64_t nz = (kw + kc - 1) / kc;
     dim3 grid((unsigned)((mlim + BM - 1) / BM), (unsigned)ntiles, (unsigned)nz);
-    blk_gemm_kernel<TR, SUB><<<grid, 256, 0, c->stream>>>(F, ldf, fr0, fc0, kw, kc, mlim, Y, ldy, O, ldo, ozs);
+    blk_gemm_kernel<TR, SUB, ABS><<<grid, 256, 0, c->stream>>>(F, ldf, fr0, fc0, kw, kc, mlim, Y, ldy, O, ldo, ozs, Oa);
     return 0;
 }
 
@@ -146,6 +169,45 @@ int launch_blk_residual(mpf_ctx *c, const double *A, int64_t lda, int64_t n, boo
         if (rc) return rc;
         dim3 grid((unsigned)((ldt + 255) / 256), (unsigned)(BT * nt));
         blk_res_reduce_kernel<<<grid, 256, 0, c->stream>>>(c->blk_part, nch, zs, B + off, R + off, n, ldt);
+    }
+    MPF_HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+// The reduce step of the fused residual and bound: r = b - sum, w = |b| + sum_abs (both sums over the chunks in ascending order) and
+// q = the componentwise backward error's ratio of the element, LAPACK dgerfs's: |r| / w where w > safe2, else (|r| + safe1) / (w + safe1).
+// Rows n .. ldt - 1 of all three: zero.
+__global__ __launch_bounds__(256) void blk_res_abs_reduce_kernel(const double *__restrict__ part, const double *__restrict__ parta, int nchunks,
+                                                                 long long zs, const double *__restrict__ b, double *__restrict__ r,
+                                                                 double *__restrict__ w, double *__restrict__ q, long long n, long long ldt,
+                                                                 double safe1, double safe2) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= ldt) return;
+    const long long e = i + (long long)blockIdx.y * ldt;
+    double s = 0, sa = 0;
+    if (i < n)
+        for (int ch = 0; ch < nchunks; ++ch) { s += part[ch * zs + e]; sa += parta[ch * zs + e]; }
+    const double rv = i < n ? b[e] - s : 0.0, wv = i < n ? fabs(b[e]) + sa : 0.0;
+    r[e] = rv;
+    w[e] = wv;
+    q[e] = i < n ? (wv > safe2 ? fabs(rv) / wv : (fabs(rv) + safe1) / (wv + safe1)) : 0.0;
+}
+// R = B - op(A) X, W = |B| + |op(A)| |X| and Q = the backward error's ratio per element, in ONE pass over op(A) per tile: the residual's
+// launches and partials with the second accumulator pair and the two-level sum of blk_gemm_kernel's ABS form
+int launch_blk_residual_bound(mpf_ctx *c, const double *A, int64_t lda, int64_t n, bool trans, const double *X, const double *B, double *R,
+                              double *W, double *Q, int64_t ldt, int ntiles, double safe1, double safe2) {
+    const int nch = (int)((n + RKC - 1) / RKC);
+    const int64_t zs = ldt * BT * RES_TILES;
+    MPF_HIP_TRY(c, c->blk_part.grow(2 * (int64_t)nch * zs));
+    double *pa = c->blk_part + (int64_t)nch * zs;
+    for (int t0 = 0; t0 < ntiles; t0 += RES_TILES) {
+        const int nt = ntiles - t0 < RES_TILES ? ntiles - t0 : RES_TILES;
+        const int64_t off = (int64_t)t0 * BT * ldt;
+        int rc = trans ? blk_gemm<true, false, true>(c, A, lda, 0, 0, n, RKC, n, X + off, ldt, c->blk_part, ldt, zs, nt, pa)
+                       : blk_gemm<false, false, true>(c, A, lda, 0, 0, n, RKC, n, X + off, ldt, c->blk_part, ldt, zs, nt, pa);
+        if (rc) return rc;
+        dim3 grid((unsigned)((ldt + 255) / 256), (unsigned)(BT * nt));
+        blk_res_abs_reduce_kernel<<<grid, 256, 0, c->stream>>>(c->blk_part, pa, nch, zs, B + off, R + off, W + off, Q + off, n, ldt, safe1, safe2);
     }
     MPF_HIP_TRY(c, hipGetLastError());
     return 0;
