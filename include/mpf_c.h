@@ -379,6 +379,39 @@ int mpf_gerfs(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, const
               const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
               int32_t itmax, double *ferr, double *berr, mpf_gerfs_stats *stats);
 
+/* ---- expert driver for many right-hand sides (build extension; mpf_gesvx's steps on the tiles of the blocked solve) -----------------
+ * Solves op(A) X = B for nrhs columns with ONE factorization: steps 1 .. 4 are mpf_gesvx's, from the same code (equilibrate, factor
+ * d_work in the mode try_fp16 asks for, rcond of those factors, the kappa_max gate).  They depend on A only: for the same A and
+ * arguments path, equed, rcond, rcond_lowp, skipped_by_rcond, anorm, d_work and d_ipiv are mpf_gesvx's, bit for bit.
+ *   5. All columns are refined together against the ORIGINAL A by mpf_solve_ir_block's per-column rules (max_iter, tol, the stall
+ *      rule, stats), with the equilibrated factors as the preconditioner: op(A)^-1 v ~ Dc (L U)^-1 P (Dr v) (trans = 1:
+ *      Dr P^T (L U)^-T (Dc v)).  The scale vectors ride on the tile loads and stores, so a solve costs what mpf_getrs costs.
+ *   6. If ANY column has not converged on low-precision factors, the whole call goes to fp64 factors of the same equilibrated matrix
+ *      and ALL columns are solved and refined again (path = 2).  A column's bits therefore depend only on A, on its own b and on
+ *      the path the call took, not on which other columns converged; the price is that one hard column costs every column the
+ *      fp64 path.
+ *   7. With ferr and berr given (HOST arrays of nrhs doubles; both NULL: no bounds stage) mpf_gerfs's loop runs on the factors that
+ *      produced the answer: X is refined further in place by dgerfs's rule (itmax as in mpf_gerfs: 0 means 5, clamped to 31) and
+ *      berr, ferr are those of the ORIGINAL system for the returned X: the residual and the weights are taken on A, B, X as given,
+ *      the corrections and dlacn2's products go through the scaled solves (the op(A)^-T product with the two scale vectors
+ *      swapped).  This departs from LAPACK's dgesvx on purpose: LAPACK bounds the equilibrated system and divides ferr by colcnd
+ *      or rowcnd.  Every scale factor here is an exact power of two, so the residual and the weights of the original system are
+ *      the equilibrated ones times Dr^-1 without rounding: berr is the same number, and the direct ferr bounds the error of the X
+ *      the caller gets instead of a bound loosened by a condition number.
+ * d_B (N x nrhs, ldb >= N) is preserved; d_X (ldx >= N) receives the solution, rows N .. ldx - 1 are not touched; d_A, d_work,
+ * d_ipiv, d_r, d_c as mpf_gesvx.  stats: the call (path, equed, rcond, rcond_lowp, times; ir_lowp / ir_final: the column with the
+ * largest final rel_residual of the respective attempt; ms_ir includes the bounds stage, whose own time is rfs[0].ms_total).
+ * ir, rfs: nrhs host entries each of the attempt that produced X, or NULL.  A column has the same bits alone, among others and at
+ * another position, within the same path.  Returns 0 when every column converged, 1 when some column did not (ir says which),
+ * < 0 on error; nrhs = 0 returns 0 and does no work, not even the factorization.  Synchronises. */
+int mpf_gesvx_block(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t N, int32_t nb, double *d_work, int32_t *d_ipiv,
+                    int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                    int32_t trans, int32_t equilibrate, int32_t try_fp16, double kappa_max, int32_t max_iter, double tol,
+                    int32_t itmax, double *d_r, double *d_c,
+                    double *ferr, double *berr,             /* host, nrhs each; both NULL: no bounds stage */
+                    mpf_gesvx_stats *stats,                 /* the call: path, equed, rcond, rcond_lowp, times */
+                    mpf_ir_stats *ir, mpf_gerfs_stats *rfs  /* host, nrhs each, optional */);
+
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block
  * b / world; d_Aloc is the rank's N x (local columns) column-major matrix (ldloc >= N), d_ipiv the full pivot vector (N int32,

@@ -32,7 +32,7 @@ C_ABI_SYMBOLS = [
     "mpf_solve_ir_dist", "mpf_rccl_selftest", "mpf_check_plu_dev", "mpf_check_plu_host", "mpf_solve_ir_nrhs",
     "mpf_solve_gmres_ir", "mpf_trim", "mpf_dist_set_p2p",
     "mpf_solve_ir_trans", "mpf_lange", "mpf_geequ", "mpf_gecon", "mpf_gesvx",
-    "mpf_getrs", "mpf_solve_ir_block", "mpf_gerfs",
+    "mpf_getrs", "mpf_solve_ir_block", "mpf_gerfs", "mpf_gesvx_block",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -177,6 +177,8 @@ def load_library(probe=False):
     L.mpf_solve_ir_block.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, dbl, C.POINTER(MpfIrStats)]
     L.mpf_gerfs.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, C.POINTER(dbl), C.POINTER(dbl),
                             C.POINTER(MpfGerfsStats)]
+    L.mpf_gesvx_block.argtypes = [vp, vp, i64, i64, i32, vp, vp, i32, vp, i64, vp, i64, i32, i32, i32, dbl, i32, dbl, i32, vp, vp,
+                                  C.POINTER(dbl), C.POINTER(dbl), C.POINTER(MpfGesvxStats), C.POINTER(MpfIrStats), C.POINTER(MpfGerfsStats)]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -742,3 +744,38 @@ class MPFContext:
                               _ptr(B), ldb, _ptr(Xr), ldx, int(itmax), ferr.ctypes.data_as(dp), berr.ctypes.data_as(dp), st)
         self._check(rc, "mpf_gerfs")
         return Xr, ferr[:nrhs], berr[:nrhs], list(st)[:nrhs]
+
+    # ---- expert driver for many right-hand sides (include/mpf_c.h: mpf_gesvx_block) ---------------------------------------------
+    def gesvx_block(self, A, B, nb=256, trans=False, equilibrate=1, try_fp16=1, kappa_max=0.0, max_iter=10, tol=1e-12, itmax=0,
+                    bounds=True, work=None, want_scales=False):
+        """mpf_gesvx_block: mpf_gesvx's steps with one factorization for all columns of B (a vector or N x nrhs column-major):
+        blocked refinement against A and, with bounds, dgerfs's berr and ferr of the original system.  Returns
+        (X, ferr, berr, stats, ir_stats, gerfs_stats, work, ipiv) and, with want_scales, (r, c) as well; ferr, berr (numpy arrays)
+        and gerfs_stats (a list per column, like ir_stats) are None with bounds=False.  X is a vector when B is."""
+        import numpy as np
+        self._bind()
+        t = self.torch
+        n = A.shape[0]
+        vec = B.dim() == 1
+        _, nrhs, ldb = self._rhs(B)
+        if work is None:
+            work = self.colmajor(n, n)
+        ipiv = t.empty(n, dtype=t.int32, device=self.device)
+        X = t.empty(n, dtype=t.float64, device=self.device) if vec else self.colmajor(n, nrhs)
+        ldx = n if vec else _colmajor_ld(X)
+        r = t.empty(n, dtype=t.float64, device=self.device) if want_scales else None
+        c = t.empty(n, dtype=t.float64, device=self.device) if want_scales else None
+        st = MpfGesvxStats()
+        ist = (MpfIrStats * max(nrhs, 1))()
+        rst = (MpfGerfsStats * max(nrhs, 1))()
+        dp = C.POINTER(C.c_double)
+        ferr = np.zeros(max(nrhs, 1)) if bounds else None
+        berr = np.zeros(max(nrhs, 1)) if bounds else None
+        rc = self.L.mpf_gesvx_block(self.h, _ptr(A), _colmajor_ld(A), n, nb, _ptr(work), _ptr(ipiv), nrhs, _ptr(B), ldb, _ptr(X), ldx,
+                                    int(bool(trans)), int(equilibrate), int(try_fp16), float(kappa_max), max_iter, tol, int(itmax),
+                                    _ptr(r), _ptr(c), ferr.ctypes.data_as(dp) if bounds else None,
+                                    berr.ctypes.data_as(dp) if bounds else None, C.byref(st), ist, rst)
+        self._check(rc, "mpf_gesvx_block")
+        out = (X, ferr[:nrhs] if bounds else None, berr[:nrhs] if bounds else None, st, list(ist)[:nrhs],
+               list(rst)[:nrhs] if bounds else None, work, ipiv)
+        return out + (r, c) if want_scales else out

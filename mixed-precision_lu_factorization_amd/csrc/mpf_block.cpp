@@ -2,6 +2,8 @@
 //   mpf_getrs            B := A^-1 B or A^-T B with the factors of mpf_factor_dev
 //   mpf_solve_ir_block   fp64 refinement of all columns together, per-column rules and stats of mpf_solve_ir_nrhs / _trans
 //   mpf_gerfs            LAPACK dgerfs: refinement by the componentwise backward error, berr and the forward bound ferr per column
+// The bodies of the last two are cores (blk_refine_core, blk_bounds_core) that take optional scale vectors for the factors of an
+// equilibrated copy Dr A Dc: mpf_gesvx_block (mpf_expert.cpp) calls them with its scales, the public functions with none.
 // The right-hand sides go through the device in groups of at most GROUP_TILES tiles of BLK_T columns (solve_block.hip); every
 // triangular step and every residual is one pass over the factor block / over A for the whole group.
 #include "mpf_internal.h"
@@ -33,13 +35,15 @@ int tile_solve(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t N, bool trans
     int rc = launch_blk_tri(c, LU, ldlu, N, trans ? 2 : 0, W, Z, g.ldt, g.ntiles);
     return rc ? rc : launch_blk_tri(c, LU, ldlu, N, trans ? 3 : 1, Z, W, g.ldt, g.ntiles);
 }
-// out (tiles) <- op(A)^-1 src (tiles), through W / Z
+// out (tiles) <- post .* op(L U, P)^-1 (pre .* src) (tiles), through W / Z: op(A)^-1 src for the factors of A itself (pre = post = null)
+// and for those of Dr A Dc (trans = 0: Dc (L U)^-1 P Dr, pre = Dr, post = Dc; trans = 1: Dr P^T (L U)^-T Dc, pre = Dc, post = Dr).
+// The scales ride on the load and the store, indexed by the matrix row as the permutation is.
 int tile_getrs(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t N, bool trans, const double *src, double *out, double *W, double *Z,
-               const Group &g) {
+               const Group &g, const double *pre = nullptr, const double *post = nullptr) {
     const int64_t cols = (int64_t)BLK_T * g.ntiles;
-    int rc = launch_blk_load(c, src, g.ldt, trans ? nullptr : c->perm_buf, N, cols, W, g.ldt, g.ntiles);
+    int rc = launch_blk_load(c, src, g.ldt, trans ? nullptr : c->perm_buf, N, cols, W, g.ldt, g.ntiles, pre);
     if (!rc) rc = tile_solve(c, LU, ldlu, N, trans, W, Z, g);
-    if (!rc) rc = launch_blk_store(c, W, g.ldt, trans ? c->perm_buf : nullptr, N, cols, out, g.ldt);
+    if (!rc) rc = launch_blk_store(c, W, g.ldt, trans ? c->perm_buf : nullptr, N, cols, out, g.ldt, post);
     return rc;
 }
 int col_norms(mpf_ctx *c, const double *T, const Group &g, int64_t N, int64_t ncols, std::vector<double> &out) {
@@ -70,48 +74,13 @@ int check_args(mpf_ctx *c, const char *who, int32_t trans, int64_t N, int32_t nr
 }
 } // namespace
 
-extern "C" {
-
-int mpf_getrs(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv, int64_t N, int32_t nrhs, double *d_B,
-              int64_t ldb) {
-    if (!c) return -1;
-    if (check_args(c, "getrs", trans, N, nrhs, ldlu, ldb)) return -1;
-    if (nrhs == 0) return 0;
-    if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs: null pointer"; return -1; }
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
-    if (rc) return rc;
-    const bool tr = trans == 1;
-    for (int32_t j0 = 0; j0 < nrhs; j0 += GROUP_TILES * BLK_T) {
-        const int64_t ncols = std::min<int64_t>(nrhs - j0, GROUP_TILES * BLK_T);
-        Group g;
-        rc = group_tiles(c, N, (int)((ncols + BLK_T - 1) / BLK_T), 2, g);
-        if (rc) return rc;
-        double *W = g.t(0), *Z = g.t(1), *B = d_B + (int64_t)j0 * ldb;
-        rc = launch_blk_load(c, B, ldb, tr ? nullptr : c->perm_buf, N, ncols, W, g.ldt, g.ntiles);
-        if (!rc) rc = tile_solve(c, d_LU, ldlu, N, tr, W, Z, g);
-        if (!rc) rc = launch_blk_store(c, W, g.ldt, tr ? c->perm_buf : nullptr, N, ncols, B, ldb);
-        if (rc) return rc;
-    }
-    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return solve_check_waits(c);
-}
-
-int mpf_solve_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
-                       int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_iter, double tol,
-                       mpf_ir_stats *stats) {
-    if (!c) return -1;
-    if (check_args(c, "solve_ir_block", trans, N, nrhs, ldlu, ldb)) return -1;
-    if (lda < N || ldx < N) { c->err = "solve_ir_block: leading dimension < N"; return -1; }
-    if (nrhs == 0) return 0;
-    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X) { c->err = "solve_ir_block: null pointer"; return -1; }
+// The body of mpf_solve_ir_block (mpf_internal.h): x0 and every correction go through the scaled tile_getrs, the residual is taken
+// against the original A; rules, stats and masking per column as documented for mpf_solve_ir_block.
+int blk_refine_core(mpf_ctx *c, bool tr, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
+                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_iter, double tol, const double *pre,
+                    const double *post, mpf_ir_stats *st) {
     if (max_iter > 31) max_iter = 31;
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
-    if (rc) return rc;
-    const bool tr = trans == 1;
-    std::vector<mpf_ir_stats> st((size_t)nrhs);
+    int rc;
     for (int32_t j0 = 0; j0 < nrhs; j0 += GROUP_TILES * BLK_T) {
         const int64_t ncols = std::min<int64_t>(nrhs - j0, GROUP_TILES * BLK_T);
         Group g;
@@ -124,7 +93,7 @@ int mpf_solve_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda
         rc = launch_blk_load(c, d_B + (int64_t)j0 * ldb, ldb, nullptr, N, ncols, Bt, g.ldt, g.ntiles);
         std::vector<double> nb2, nr;
         if (!rc) rc = col_norms(c, Bt, g, N, ncols, nb2);
-        if (!rc) rc = tile_getrs(c, d_LU, ldlu, N, tr, Bt, Xt, W, Z, g);   // x0
+        if (!rc) rc = tile_getrs(c, d_LU, ldlu, N, tr, Bt, Xt, W, Z, g, pre, post);   // x0
         if (rc) return rc;
         for (auto &v : nb2) if (v == 0) v = 1;
         std::vector<int> active((size_t)ncols, 1), mask((size_t)tcols, 0);
@@ -152,7 +121,7 @@ int mpf_solve_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda
             }
             if (!any) break;
             MPF_HIP_TRY(c, hipMemcpyAsync(c->blk_mask, mask.data(), (size_t)tcols * sizeof(int), hipMemcpyHostToDevice, c->stream));
-            rc = tile_getrs(c, d_LU, ldlu, N, tr, R, R, W, Z, g);   // correction d = op^-1 r (into R: r is consumed)
+            rc = tile_getrs(c, d_LU, ldlu, N, tr, R, R, W, Z, g, pre, post);   // correction d = op^-1 r (into R: r is consumed)
             if (!rc) rc = launch_blk_masked_axpy(c, R, c->blk_mask, Xt, g.ldt, g.ntiles);
             if (rc) return rc;
             MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));   // `mask` is a host vector reused by the next step
@@ -160,32 +129,20 @@ int mpf_solve_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda
         rc = launch_blk_store(c, Xt, g.ldt, nullptr, N, ncols, d_X + (int64_t)j0 * ldx, ldx);
         if (rc) return rc;
     }
-    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (auto &s : st) s.ms_total = ms;
-    if (stats) std::copy(st.begin(), st.end(), stats);
-    return solve_check_waits(c);
+    return 0;
 }
 
-int mpf_gerfs(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
-              int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *ferr,
-              double *berr, mpf_gerfs_stats *stats) {
-    if (!c) return -1;
-    if (check_args(c, "gerfs", trans, N, nrhs, ldlu, ldb)) return -1;
-    if (lda < N || ldx < N) { c->err = "gerfs: leading dimension < N"; return -1; }
-    if (nrhs == 0) return 0;
-    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !ferr || !berr) { c->err = "gerfs: null pointer"; return -1; }
+// The body of mpf_gerfs (mpf_internal.h): residual, weights and berr of the ORIGINAL system; corrections and dlacn2's KASE 2 product
+// through the scaled tile_getrs, KASE 1 through the transposed one with pre and post swapped.
+int blk_bounds_core(mpf_ctx *c, bool tr, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
+                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *ferr, double *berr, const double *pre,
+                    const double *post, mpf_gerfs_stats *st) {
     if (itmax <= 0) itmax = 5;
     if (itmax > 31) itmax = 31;
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
-    if (rc) return rc;
-    const bool tr = trans == 1;
+    int rc;
     // LAPACK's constants: dlamch('E') is the relative machine epsilon 2^-53, not the spacing DBL_EPSILON
     const double eps = 0x1p-53, safmin = DBL_MIN, nz = (double)(N + 1), safe1 = nz * safmin, safe2 = safe1 / eps;
     constexpr int LACN2_ITMAX = 5;
-    std::vector<mpf_gerfs_stats> st((size_t)nrhs);
     for (int32_t j0 = 0; j0 < nrhs; j0 += GROUP_TILES * BLK_T) {
         const int64_t ncols = std::min<int64_t>(nrhs - j0, GROUP_TILES * BLK_T);
         Group g;
@@ -231,7 +188,7 @@ int mpf_gerfs(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const d
             }
             if (!any) break;
             rc = upload(c->blk_mask, mask);
-            if (!rc) rc = tile_getrs(c, d_LU, ldlu, N, tr, R, R, S1, S2, g);   // d = op(A)^-1 r (into R: the next pass rebuilds r)
+            if (!rc) rc = tile_getrs(c, d_LU, ldlu, N, tr, R, R, S1, S2, g, pre, post);   // d = op(A)^-1 r (into R: the next pass rebuilds r)
             if (!rc) rc = launch_blk_masked_axpy(c, R, c->blk_mask, Xt, g.ldt, g.ntiles);
             if (rc) return rc;
             ++solves;
@@ -245,15 +202,15 @@ int mpf_gerfs(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const d
         // ---- forward bound: dlacn2 on (op(A)^-1 diag(w))^T, all columns in lock-step ----------------------------------------
         rc = launch_blk_ferr_weight(c, R, Wt, N, ncols, g.ldt, nz * eps, safe1, safe2);
         if (rc) return rc;
-        auto kase1 = [&]() {   // v <- w .* (op(A)^-T v)
+        auto kase1 = [&]() {   // v <- w .* (op(A)^-T v): the transposed solve, its scales swapped
             ++solves;
-            int r2 = tile_getrs(c, d_LU, ldlu, N, !tr, V, V, S1, S2, g);
+            int r2 = tile_getrs(c, d_LU, ldlu, N, !tr, V, V, S1, S2, g, post, pre);
             return r2 ? r2 : launch_blk_scale(c, V, Wt, g.ldt, g.ntiles);
         };
         auto kase2 = [&]() {   // v <- op(A)^-1 (w .* v)
             ++solves;
             int r2 = launch_blk_scale(c, V, Wt, g.ldt, g.ntiles);
-            return r2 ? r2 : tile_getrs(c, d_LU, ldlu, N, tr, V, V, S1, S2, g);
+            return r2 ? r2 : tile_getrs(c, d_LU, ldlu, N, tr, V, V, S1, S2, g, pre, post);
         };
         auto fill = [&]() {
             int r2 = upload(d_kind, arg);
@@ -323,6 +280,73 @@ int mpf_gerfs(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const d
             st[(size_t)(j0 + j)].solves = solves;
         }
     }
+    return 0;
+}
+
+extern "C" {
+
+int mpf_getrs(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv, int64_t N, int32_t nrhs, double *d_B,
+              int64_t ldb) {
+    if (!c) return -1;
+    if (check_args(c, "getrs", trans, N, nrhs, ldlu, ldb)) return -1;
+    if (nrhs == 0) return 0;
+    if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
+    if (rc) return rc;
+    const bool tr = trans == 1;
+    for (int32_t j0 = 0; j0 < nrhs; j0 += GROUP_TILES * BLK_T) {
+        const int64_t ncols = std::min<int64_t>(nrhs - j0, GROUP_TILES * BLK_T);
+        Group g;
+        rc = group_tiles(c, N, (int)((ncols + BLK_T - 1) / BLK_T), 2, g);
+        if (rc) return rc;
+        double *W = g.t(0), *Z = g.t(1), *B = d_B + (int64_t)j0 * ldb;
+        rc = launch_blk_load(c, B, ldb, tr ? nullptr : c->perm_buf, N, ncols, W, g.ldt, g.ntiles);
+        if (!rc) rc = tile_solve(c, d_LU, ldlu, N, tr, W, Z, g);
+        if (!rc) rc = launch_blk_store(c, W, g.ldt, tr ? c->perm_buf : nullptr, N, ncols, B, ldb);
+        if (rc) return rc;
+    }
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return solve_check_waits(c);
+}
+
+int mpf_solve_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
+                       int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_iter, double tol,
+                       mpf_ir_stats *stats) {
+    if (!c) return -1;
+    if (check_args(c, "solve_ir_block", trans, N, nrhs, ldlu, ldb)) return -1;
+    if (lda < N || ldx < N) { c->err = "solve_ir_block: leading dimension < N"; return -1; }
+    if (nrhs == 0) return 0;
+    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X) { c->err = "solve_ir_block: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
+    if (rc) return rc;
+    std::vector<mpf_ir_stats> st((size_t)nrhs);
+    rc = blk_refine_core(c, trans == 1, d_A, lda, d_LU, ldlu, N, nrhs, d_B, ldb, d_X, ldx, max_iter, tol, nullptr, nullptr, st.data());
+    if (rc) return rc;
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (auto &s : st) s.ms_total = ms;
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    return solve_check_waits(c);
+}
+
+int mpf_gerfs(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
+              int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *ferr,
+              double *berr, mpf_gerfs_stats *stats) {
+    if (!c) return -1;
+    if (check_args(c, "gerfs", trans, N, nrhs, ldlu, ldb)) return -1;
+    if (lda < N || ldx < N) { c->err = "gerfs: leading dimension < N"; return -1; }
+    if (nrhs == 0) return 0;
+    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !ferr || !berr) { c->err = "gerfs: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
+    if (rc) return rc;
+    std::vector<mpf_gerfs_stats> st((size_t)nrhs);
+    rc = blk_bounds_core(c, trans == 1, d_A, lda, d_LU, ldlu, N, nrhs, d_B, ldb, d_X, ldx, itmax, ferr, berr, nullptr, nullptr, st.data());
+    if (rc) return rc;
     MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     for (auto &s : st) s.ms_total = ms;

@@ -4,6 +4,7 @@
 //   mpf_geequ            power-of-two equilibration factors
 //   mpf_gecon            reciprocal condition number of the factors (dlacn2 on the device's solves)
 //   mpf_gesvx            equilibrate, factor, estimate rcond, refine against the original matrix, fall back to fp64
+//   mpf_gesvx_block      the same steps for many right-hand sides: blocked refinement and dgerfs's bounds on the scaled factors
 // Kernels in solve_ext.hip; the device only ever hands scalars back to the host.
 #include "mpf_internal.h"
 #include <cfloat>
@@ -221,6 +222,119 @@ int ir_scaled(mpf_ctx *c, const Ext &e, const double *A, int64_t lda, const doub
     }
     return 0;
 }
+
+// Steps 1 .. 6 of the expert drivers (mpf_gesvx, mpf_gesvx_block): equilibrate, factor d_work, rcond, the kappa_max gate, one
+// refinement attempt on the low-precision factors and, where that did not converge, fp64 factors of the same equilibrated matrix
+// and a second attempt.  Everything up to the gate depends on A alone, so both drivers take the same decisions and leave the same
+// factors.  `refine(pre, post, ir)` runs one attempt on the factors in d_work (prepared by solve_setup) and fills `ir`: its
+// `converged` decides whether the attempt stands; its ms_total is set here.  Fills `gs` except ms_total; pre / post are the scale
+// vectors of the preconditioner (null where equed says none), valid while `e`, d_r and d_c are.
+template <class Refine>
+int gesvx_steps(mpf_ctx *c, const Ext &e, const double *d_A, int64_t lda, int64_t N, int32_t nb, double *d_work, int32_t *d_ipiv, bool tr,
+                int32_t equilibrate, int32_t try_fp16, double kappa_max, double *d_r, double *d_c, mpf_gesvx_stats &gs, const double *&pre,
+                const double *&post, Refine refine_attempt) {
+    double *r = d_r ? d_r : e.v(V_R), *cs = d_c ? d_c : e.v(V_C);
+    int rc;
+
+    // ---- 1. equilibration and the scaled copy -------------------------------------------------------------------------
+    auto t0 = std::chrono::steady_clock::now();
+    if (equilibrate) {
+        const int info = geequ_core(c, e, d_A, lda, N, r, cs, gs.rowcnd, gs.colcnd, gs.amax);
+        if (info < 0) return info;
+        if (info == 0) {
+            if (equilibrate == 2) gs.equed = 3;
+            else {   // dlaqge's rule
+                const double small = DBL_MIN / DBL_EPSILON, large = 1.0 / small;
+                const bool rows = gs.rowcnd < 0.1 || gs.amax < small || gs.amax > large;
+                const bool cols = gs.colcnd < 0.1;
+                gs.equed = (rows ? 1 : 0) | (cols ? 2 : 0);
+            }
+        }
+    }
+    auto scaled_copy = [&]() {
+        return launch_scaled_copy(c, d_A, lda, (gs.equed & 1) ? r : nullptr, (gs.equed & 2) ? cs : nullptr, d_work, N, N, N);
+    };
+    rc = scaled_copy();
+    if (rc) return rc;
+    if (try_fp16 && gs.equed) {
+        // headroom of the fp16 operands: max |Dr A Dc| into [2^13, 2^14) by one global power of two, folded into Dr
+        double mx = 0;
+        rc = lange_core(c, e, d_work, N, N, N, 'M', mx);
+        if (rc) return rc;
+        if (mx > 0 && std::isfinite(mx)) {
+            const int ex = std::ilogb(mx);
+            const double s = std::ldexp(1.0, 13 - ex);
+            if (s != 1.0) {
+                if (gs.equed & 1) rc = launch_vscale(c, r, nullptr, s, r, N);
+                else {
+                    std::vector<double> sv((size_t)N, s);
+                    MPF_HIP_TRY(c, hipMemcpyAsync(r, sv.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+                    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));   // `sv` is a host temporary
+                    gs.equed |= 1;
+                }
+                if (!rc) rc = scaled_copy();
+                if (rc) return rc;
+            }
+        }
+    }
+    rc = lange_core(c, e, d_work, N, N, N, tr ? 'I' : '1', gs.anorm);
+    if (rc) return rc;
+    gs.ms_equilibrate = ms_since(t0);
+    pre = tr ? ((gs.equed & 2) ? cs : nullptr) : ((gs.equed & 1) ? r : nullptr);
+    post = tr ? ((gs.equed & 1) ? r : nullptr) : ((gs.equed & 2) ? cs : nullptr);
+
+    std::vector<int32_t> ident((size_t)N);
+    for (int64_t i = 0; i < N; ++i) ident[(size_t)i] = (int32_t)(i + 1);
+    // factor d_work (already the scaled copy) in `mode`, prepare the solves, rcond of the factors
+    auto factor_and_rcond = [&](int mode, double &rcond) -> int {
+        auto t1 = std::chrono::steady_clock::now();
+        MPF_HIP_TRY(c, hipMemcpyAsync(d_ipiv, ident.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        mpf_opts o{};
+        o.trailing = mode;
+        int r2 = mpf_factor_dev(c, d_work, N, N, nb, d_ipiv, &o);
+        if (r2 < 0) return r2;
+        gs.info = r2;
+        gs.ms_factor += ms_since(t1);
+        t1 = std::chrono::steady_clock::now();
+        mpf_gecon_stats gst{};
+        r2 = solve_setup(c, d_work, N, d_ipiv, N);
+        if (!r2) r2 = gecon_full(c, e, d_work, N, N, !tr, gs.anorm, rcond, gst);
+        if (r2) return r2;
+        gs.ms_gecon += ms_since(t1);
+        return 0;
+    };
+    auto refine = [&](mpf_ir_stats &ir) -> int {
+        const auto t1 = std::chrono::steady_clock::now();
+        int r2 = refine_attempt(pre, post, ir);
+        if (!r2) MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        ir.ms_total = ms_since(t1);
+        gs.ms_ir += ir.ms_total;
+        return r2;
+    };
+
+    bool done = false;
+    if (try_fp16) {
+        const int mode = try_fp16 == 2 ? MPF_TRAIL_FP16X3 : MPF_TRAIL_FP16;
+        gs.kappa_max = kappa_max > 0 ? kappa_max : (mode == MPF_TRAIL_FP16 ? 1e4 : 1e6);
+        rc = factor_and_rcond(mode, gs.rcond_lowp);
+        if (rc) return rc;
+        if (!(gs.rcond_lowp > 0) || 1.0 / gs.rcond_lowp > gs.kappa_max) gs.skipped_by_rcond = 1;
+        else {
+            rc = refine(gs.ir_lowp);
+            if (!rc) rc = solve_check_waits(c);   // (the fp64 attempt's set-up clears the give-up flag)
+            if (rc) return rc;
+            if (gs.ir_lowp.converged) { gs.path = 1; gs.rcond = gs.rcond_lowp; gs.ir_final = gs.ir_lowp; done = true; }
+        }
+        if (!done) { rc = scaled_copy(); if (rc) return rc; }   // the low-precision factors overwrote the copy
+    }
+    if (!done) {
+        rc = factor_and_rcond(MPF_TRAIL_FP64, gs.rcond);
+        if (!rc) rc = refine(gs.ir_final);
+        if (rc) return rc;
+        gs.path = 2;
+    }
+    return 0;
+}
 } // namespace
 
 extern "C" {
@@ -322,109 +436,79 @@ int mpf_gesvx(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32_t nb,
     Ext e;
     int rc = ext_vectors(c, N, e);
     if (rc) return rc;
-    double *r = d_r ? d_r : e.v(V_R), *cs = d_c ? d_c : e.v(V_C);
     const bool tr = trans == 1;
-
-    // ---- 1. equilibration and the scaled copy -------------------------------------------------------------------------
-    auto t0 = std::chrono::steady_clock::now();
-    if (equilibrate) {
-        const int info = geequ_core(c, e, d_A, lda, N, r, cs, gs.rowcnd, gs.colcnd, gs.amax);
-        if (info < 0) return info;
-        if (info == 0) {
-            if (equilibrate == 2) gs.equed = 3;
-            else {   // dlaqge's rule
-                const double small = DBL_MIN / DBL_EPSILON, large = 1.0 / small;
-                const bool rows = gs.rowcnd < 0.1 || gs.amax < small || gs.amax > large;
-                const bool cols = gs.colcnd < 0.1;
-                gs.equed = (rows ? 1 : 0) | (cols ? 2 : 0);
-            }
-        }
-    }
-    auto scaled_copy = [&]() {
-        return launch_scaled_copy(c, d_A, lda, (gs.equed & 1) ? r : nullptr, (gs.equed & 2) ? cs : nullptr, d_work, N, N, N);
-    };
-    rc = scaled_copy();
+    const double *pre = nullptr, *post = nullptr;
+    rc = gesvx_steps(c, e, d_A, lda, N, nb, d_work, d_ipiv, tr, equilibrate, try_fp16, kappa_max, d_r, d_c, gs, pre, post,
+                     [&](const double *pr, const double *po, mpf_ir_stats &ir) {
+                         return ir_scaled(c, e, d_A, lda, d_work, N, N, tr, pr, po, d_b, d_x, max_iter, tol, ir);
+                     });
     if (rc) return rc;
-    if (try_fp16 && gs.equed) {
-        // headroom of the fp16 operands: max |Dr A Dc| into [2^13, 2^14) by one global power of two, folded into Dr
-        double mx = 0;
-        rc = lange_core(c, e, d_work, N, N, N, 'M', mx);
-        if (rc) return rc;
-        if (mx > 0 && std::isfinite(mx)) {
-            const int ex = std::ilogb(mx);
-            const double s = std::ldexp(1.0, 13 - ex);
-            if (s != 1.0) {
-                if (gs.equed & 1) rc = launch_vscale(c, r, nullptr, s, r, N);
-                else {
-                    std::vector<double> sv((size_t)N, s);
-                    MPF_HIP_TRY(c, hipMemcpyAsync(r, sv.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-                    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));   // `sv` is a host temporary
-                    gs.equed |= 1;
-                }
-                if (!rc) rc = scaled_copy();
-                if (rc) return rc;
-            }
-        }
-    }
-    rc = lange_core(c, e, d_work, N, N, N, tr ? 'I' : '1', gs.anorm);
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    gs.ms_total = ms_since(t_all);
+    if (stats) *stats = gs;
+    rc = solve_check_waits(c);
     if (rc) return rc;
-    gs.ms_equilibrate = ms_since(t0);
-    const double *pre = tr ? ((gs.equed & 2) ? cs : nullptr) : ((gs.equed & 1) ? r : nullptr);
-    const double *post = tr ? ((gs.equed & 1) ? r : nullptr) : ((gs.equed & 2) ? cs : nullptr);
+    return gs.ir_final.converged ? 0 : 1;
+}
 
-    std::vector<int32_t> ident((size_t)N);
-    for (int64_t i = 0; i < N; ++i) ident[(size_t)i] = (int32_t)(i + 1);
-    // factor d_work (already the scaled copy) in `mode`, prepare the solves, rcond of the factors
-    auto factor_and_rcond = [&](int mode, double &rcond) -> int {
-        auto t1 = std::chrono::steady_clock::now();
-        MPF_HIP_TRY(c, hipMemcpyAsync(d_ipiv, ident.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        mpf_opts o{};
-        o.trailing = mode;
-        int r2 = mpf_factor_dev(c, d_work, N, N, nb, d_ipiv, &o);
-        if (r2 < 0) return r2;
-        gs.info = r2;
-        gs.ms_factor += ms_since(t1);
-        t1 = std::chrono::steady_clock::now();
-        mpf_gecon_stats gst{};
-        r2 = solve_setup(c, d_work, N, d_ipiv, N);
-        if (!r2) r2 = gecon_full(c, e, d_work, N, N, !tr, gs.anorm, rcond, gst);
-        if (r2) return r2;
-        gs.ms_gecon += ms_since(t1);
-        return 0;
-    };
-    auto refine = [&](mpf_ir_stats &ir) -> int {
+int mpf_gesvx_block(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32_t nb, double *d_work, int32_t *d_ipiv, int32_t nrhs,
+                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t trans, int32_t equilibrate, int32_t try_fp16,
+                    double kappa_max, int32_t max_iter, double tol, int32_t itmax, double *d_r, double *d_c, double *ferr, double *berr,
+                    mpf_gesvx_stats *stats, mpf_ir_stats *ir, mpf_gerfs_stats *rfs) {
+    if (!c) return -1;
+    if (N <= 0 || nrhs < 0) { c->err = "gesvx_block: N must be positive, nrhs >= 0"; return -1; }
+    if (lda < N || ldb < N || ldx < N) { c->err = "gesvx_block: leading dimension < N"; return -1; }
+    if (trans < 0 || trans > 1 || equilibrate < 0 || equilibrate > 2 || try_fp16 < 0 || try_fp16 > 2) {
+        c->err = "gesvx_block: trans must be 0 / 1, equilibrate 0 / 1 / 2, try_fp16 0 / 1 / 2";
+        return -1;
+    }
+    if ((ferr == nullptr) != (berr == nullptr)) { c->err = "gesvx_block: ferr and berr go together (both, or both NULL)"; return -1; }
+    if (nrhs == 0) return 0;
+    if (!d_A || !d_work || !d_ipiv || !d_B || !d_X) { c->err = "gesvx_block: null pointer"; return -1; }
+    if (max_iter > 31) max_iter = 31;
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const auto t_all = std::chrono::steady_clock::now();
+    mpf_gesvx_stats gs{};
+    Ext e;
+    int rc = ext_vectors(c, N, e);
+    if (rc) return rc;
+    const bool tr = trans == 1;
+    const double *pre = nullptr, *post = nullptr;
+    std::vector<mpf_ir_stats> cols((size_t)nrhs);
+    // one attempt: all columns on the factors in d_work; the attempt's summary is its column with the largest final rel_residual
+    // (a NaN counts as largest), so its `converged` says whether EVERY column converged
+    rc = gesvx_steps(c, e, d_A, lda, N, nb, d_work, d_ipiv, tr, equilibrate, try_fp16, kappa_max, d_r, d_c, gs, pre, post,
+                     [&](const double *pr, const double *po, mpf_ir_stats &worst) {
+                         std::fill(cols.begin(), cols.end(), mpf_ir_stats{});
+                         int r2 = blk_refine_core(c, tr, d_A, lda, d_work, N, N, nrhs, d_B, ldb, d_X, ldx, max_iter, tol, pr, po, cols.data());
+                         if (r2) return r2;
+                         size_t w = 0;
+                         for (size_t j = 1; j < cols.size(); ++j) {
+                             const double a = cols[j].rel_residual, b = cols[w].rel_residual;
+                             if (b == b && (a != a || a > b)) w = j;
+                         }
+                         worst = cols[w];
+                         return 0;
+                     });
+    if (rc) return rc;
+    const double ms_attempt = gs.ir_final.ms_total;
+    for (auto &s : cols) s.ms_total = ms_attempt;
+    // 7. the bounds of the ORIGINAL system on the factors that produced the answer
+    std::vector<mpf_gerfs_stats> rst((size_t)nrhs);
+    if (ferr) {
         const auto t1 = std::chrono::steady_clock::now();
-        int r2 = ir_scaled(c, e, d_A, lda, d_work, N, N, tr, pre, post, d_b, d_x, max_iter, tol, ir);
-        if (!r2) MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        ir.ms_total = ms_since(t1);
-        gs.ms_ir += ir.ms_total;
-        return r2;
-    };
-
-    bool done = false;
-    if (try_fp16) {
-        const int mode = try_fp16 == 2 ? MPF_TRAIL_FP16X3 : MPF_TRAIL_FP16;
-        gs.kappa_max = kappa_max > 0 ? kappa_max : (mode == MPF_TRAIL_FP16 ? 1e4 : 1e6);
-        rc = factor_and_rcond(mode, gs.rcond_lowp);
+        rc = blk_bounds_core(c, tr, d_A, lda, d_work, N, N, nrhs, d_B, ldb, d_X, ldx, itmax, ferr, berr, pre, post, rst.data());
         if (rc) return rc;
-        if (!(gs.rcond_lowp > 0) || 1.0 / gs.rcond_lowp > gs.kappa_max) gs.skipped_by_rcond = 1;
-        else {
-            rc = refine(gs.ir_lowp);
-            if (!rc) rc = solve_check_waits(c);   // (the fp64 attempt's set-up clears the give-up flag)
-            if (rc) return rc;
-            if (gs.ir_lowp.converged) { gs.path = 1; gs.rcond = gs.rcond_lowp; gs.ir_final = gs.ir_lowp; done = true; }
-        }
-        if (!done) { rc = scaled_copy(); if (rc) return rc; }   // the low-precision factors overwrote the copy
-    }
-    if (!done) {
-        rc = factor_and_rcond(MPF_TRAIL_FP64, gs.rcond);
-        if (!rc) rc = refine(gs.ir_final);
-        if (rc) return rc;
-        gs.path = 2;
+        MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        const double ms = ms_since(t1);
+        for (auto &s : rst) s.ms_total = ms;
+        gs.ms_ir += ms;
     }
     MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
     gs.ms_total = ms_since(t_all);
     if (stats) *stats = gs;
+    if (ir) std::copy(cols.begin(), cols.end(), ir);
+    if (rfs && ferr) std::copy(rst.begin(), rst.end(), rfs);
     rc = solve_check_waits(c);
     if (rc) return rc;
     return gs.ir_final.converged ? 0 : 1;

@@ -408,8 +408,12 @@ constexpr int BLK_T = 32;
 int launch_blk_tri(mpf_ctx *c, const double *LU, int64_t ld, int64_t n, int which, double *x, double *y, int64_t ldt, int ntiles);
 int launch_blk_residual(mpf_ctx *c, const double *A, int64_t lda, int64_t n, bool trans, const double *X, const double *B, double *R,
                         int64_t ldt, int ntiles);   // R = B - op(A) X
-int launch_blk_load(mpf_ctx *c, const double *src, int64_t lds, const int *perm, int64_t n, int64_t ncols, double *t, int64_t ldt, int ntiles);
-int launch_blk_store(mpf_ctx *c, const double *t, int64_t ldt, const int *perm, int64_t n, int64_t ncols, double *dst, int64_t ldd);
+// load / store: `scale` (optional, n doubles, powers of two) multiplies each element by the scale of its MATRIX row, perm[i] or i;
+// null is the unscaled kernel (a template instance of its own)
+int launch_blk_load(mpf_ctx *c, const double *src, int64_t lds, const int *perm, int64_t n, int64_t ncols, double *t, int64_t ldt, int ntiles,
+                    const double *scale = nullptr);
+int launch_blk_store(mpf_ctx *c, const double *t, int64_t ldt, const int *perm, int64_t n, int64_t ncols, double *dst, int64_t ldd,
+                     const double *scale = nullptr);
 int launch_blk_masked_axpy(mpf_ctx *c, const double *d, const int *mask, double *x, int64_t ldt, int ntiles);
 // error bounds (mpf_gerfs).  R = B - op(A) X, W = |B| + |op(A)| |X|, Q = dgerfs's backward-error ratio per element: one pass over op(A)
 int launch_blk_residual_bound(mpf_ctx *c, const double *A, int64_t lda, int64_t n, bool trans, const double *X, const double *B, double *R,
@@ -421,6 +425,16 @@ int launch_blk_scale(mpf_ctx *c, double *v, const double *w, int64_t ldt, int nt
 int launch_blk_ferr_weight(mpf_ctx *c, const double *r, double *w, int64_t n, int64_t ncols, int64_t ldt, double nzeps, double safe1, double safe2);
 int launch_blk_lacn2_fill(mpf_ctx *c, double *v, int64_t n, int64_t ncols, int64_t ldt, const int *kind, const int *at);
 int launch_blk_lacn2_sign(mpf_ctx *c, double *v, double *isgn, int64_t n, int64_t ncols, int64_t ldt, const int *live);
+// mpf_block.cpp: the bodies of mpf_solve_ir_block and mpf_gerfs on the ORIGINAL system (A, B, X) with the preconditioner
+//     op(A)^-1 v ~ post .* op(L U, P)^-1 (pre .* v)        (pre / post: scale vectors of the factored matrix Dr A Dc, or null)
+// trans = 0: pre = Dr, post = Dc; trans = 1: pre = Dc, post = Dr.  The factors are prepared (solve_setup); `st` holds nrhs zeroed
+// entries; neither core synchronises at its end nor sets ms_total.
+int blk_refine_core(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
+                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_iter, double tol, const double *pre,
+                    const double *post, mpf_ir_stats *st);
+int blk_bounds_core(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
+                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *ferr, double *berr, const double *pre,
+                    const double *post, mpf_gerfs_stats *st);
 
 // ---- host-side helpers shared by the schedules (mpf_host.cpp, mpf_dist.cpp) --------------------------------------------
 struct StreamSwap { // launch_* helpers use c->stream: point it at another stream for a scope

@@ -213,30 +213,49 @@ int launch_blk_residual_bound(mpf_ctx *c, const double *A, int64_t lda, int64_t 
     return 0;
 }
 
-// tile <- caller's columns: t[i, j] = src[p(i) + j lds] for i < n, j < ncols (p = perm or identity), zero elsewhere in the tiles
-__global__ __launch_bounds__(256) void blk_load_kernel(const double *__restrict__ src, long long lds, const int *__restrict__ perm, long long n,
-                                                       long long ncols, double *__restrict__ t, long long ldt) {
+// tile <- caller's columns: t[i, j] = src[p(i) + j lds] for i < n, j < ncols (p = perm or identity), zero elsewhere in the tiles.
+// SC: times s[p(i)], the scale of the MATRIX row the element comes from (s: n doubles, exact powers of two; read below n only).
+// Without SC the kernel is the unscaled one, instruction for instruction: the flag is a template argument, not a factor of 1.0.
+template <bool SC>
+__global__ __launch_bounds__(256) void blk_load_kernel(const double *__restrict__ src, long long lds, const int *__restrict__ perm,
+                                                       const double *__restrict__ s, long long n, long long ncols, double *__restrict__ t,
+                                                       long long ldt) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
     if (i >= ldt) return;
-    t[i + j * ldt] = (i < n && j < ncols) ? src[(perm ? (long long)perm[i] : i) + j * lds] : 0.0;
+    double v = 0.0;
+    if (i < n && j < ncols) {
+        const long long row = perm ? (long long)perm[i] : i;
+        v = src[row + j * lds];
+        if (SC) v *= s[row];
+    }
+    t[i + j * ldt] = v;
 }
-int launch_blk_load(mpf_ctx *c, const double *src, int64_t lds, const int *perm, int64_t n, int64_t ncols, double *t, int64_t ldt, int ntiles) {
+int launch_blk_load(mpf_ctx *c, const double *src, int64_t lds, const int *perm, int64_t n, int64_t ncols, double *t, int64_t ldt, int ntiles,
+                    const double *scale) {
     dim3 grid((unsigned)((ldt + 255) / 256), (unsigned)(BT * ntiles));
-    blk_load_kernel<<<grid, 256, 0, c->stream>>>(src, lds, perm, n, ncols, t, ldt);
+    if (scale) blk_load_kernel<true><<<grid, 256, 0, c->stream>>>(src, lds, perm, scale, n, ncols, t, ldt);
+    else blk_load_kernel<false><<<grid, 256, 0, c->stream>>>(src, lds, perm, nullptr, n, ncols, t, ldt);
     MPF_HIP_TRY(c, hipGetLastError());
     return 0;
 }
-// caller's columns <- tile: dst[p(i) + j ldd] = t[i, j] for i < n, j < ncols (p = perm: the scatter of the transposed solve)
-__global__ __launch_bounds__(256) void blk_store_kernel(const double *__restrict__ t, long long ldt, const int *__restrict__ perm, long long n,
-                                                        double *__restrict__ dst, long long ldd) {
+// caller's columns <- tile: dst[p(i) + j ldd] = t[i, j] for i < n, j < ncols (p = perm: the scatter of the transposed solve).
+// SC: times s[p(i)], the scale of the matrix row the element goes to.
+template <bool SC>
+__global__ __launch_bounds__(256) void blk_store_kernel(const double *__restrict__ t, long long ldt, const int *__restrict__ perm,
+                                                        const double *__restrict__ s, long long n, double *__restrict__ dst, long long ldd) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
     if (i >= n) return;
-    dst[(perm ? (long long)perm[i] : i) + j * ldd] = t[i + j * ldt];
+    const long long row = perm ? (long long)perm[i] : i;
+    double v = t[i + j * ldt];
+    if (SC) v *= s[row];
+    dst[row + j * ldd] = v;
 }
-int launch_blk_store(mpf_ctx *c, const double *t, int64_t ldt, const int *perm, int64_t n, int64_t ncols, double *dst, int64_t ldd) {
+int launch_blk_store(mpf_ctx *c, const double *t, int64_t ldt, const int *perm, int64_t n, int64_t ncols, double *dst, int64_t ldd,
+                     const double *scale) {
     if (ncols <= 0) return 0;
     dim3 grid((unsigned)((n + 255) / 256), (unsigned)ncols);
-    blk_store_kernel<<<grid, 256, 0, c->stream>>>(t, ldt, perm, n, dst, ldd);
+    if (scale) blk_store_kernel<true><<<grid, 256, 0, c->stream>>>(t, ldt, perm, scale, n, dst, ldd);
+    else blk_store_kernel<false><<<grid, 256, 0, c->stream>>>(t, ldt, perm, nullptr, n, dst, ldd);
     MPF_HIP_TRY(c, hipGetLastError());
     return 0;
 }
