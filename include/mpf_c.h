@@ -39,7 +39,16 @@ typedef struct mpf_opts {
                               global-memory path otherwise (panels wider than 256 columns or taller than 256 rows x #CUs).
                               1: generic path and generic schedule always -- no kernel ever waits for another workgroup; for GPUs
                               shared with other processes (also option safe_pivots / MPF_SAFE_PIVOTS=1).  Results do not depend on this value. */
-    int32_t reserved;
+    int32_t pivot_search;  /* 0: the reference's rule -- pivots from an fp16 image of the panel (double_to_fp16 clamps at +-65504 and flushes
+                              below 2^-14, so entries outside that range, or within one fp16 ulp of each other, tie).  Default.
+                              1: LAPACK's partial pivoting -- the pivot search runs in fp64 on the numbers being eliminated (see
+                              mpf_dgetf2_piv): |l_ij| <= 1, the pivots do not change when the matrix is scaled by a power of two, fp16's
+                              range plays no part.  Runs the generic schedule's loop in every trailing mode (single stream, no kernel
+                              waits for another workgroup, -4 cannot occur), any nb and lda: per panel mpf_dgetf2_piv, the interchange of
+                              the columns left and right of the panel, then the TRSM and the update as they are.  In the fp64 trailing
+                              mode IPIV and the factors equal, bit for bit, what the same loop gives through the step operators
+                              mpf_dgetf2_piv, mpf_laswp, mpf_dtrsm_llnu, mpf_dgemm_minus.  Also option pivot_fp64 / MPF_PIVOT_FP64=1, which
+                              turns it on for every entry point that factors internally.  Not available in mpf_factor_dist. */
 } mpf_opts;
 
 typedef struct mpf_stats {
@@ -72,7 +81,8 @@ typedef struct mpf_stats {
                                    what was left of the way home after the last kernel) */
     int32_t host_late_segments; /* mpf_factor_host: column segments of the matrix that went UP while the factorization had started on the
                                    first part (0: the whole matrix first, as MPF.cu:82; ms_h2d is then the whole upload, otherwise the first part's) */
-    int32_t reserved;
+    int32_t pivot_search;       /* the pivot rule that ran: 0 fp16 image (the reference's), 1 fp64 partial pivoting -- then lookahead = 0,
+                                   superpanel = 1, ms_hpanel = 0 and ms_dpanel is the pivoting panel (event_timers = 2 for the phase timers) */
 } mpf_stats;
 
 /* ---- lifetime -------------------------------------------------------------------------- */
@@ -89,7 +99,7 @@ int mpf_get_stats(mpf_ctx *ctx, mpf_stats *out);
  * "superpanel_fp16", see csrc/mpf_internal.h MpfTuning for the list); afterwards only these calls change them, so contexts
  * on different host threads are independent.  Names: safe_pivots, chain_pipeline, chain_pipeline_below, fp16_work32,
  * superpanel_fp16, superpanel_fp64, no_lookahead, verbose, timeline, hp_spin_limit, hp_gate_ticks, hp_acq_fence, hgemm_pad,
- * hgemm_split_pad, hgemm_big, hgemm_big_tile, dgemm_dma, generic_fused, fp64_rowmajor, fp64_rowmajor_min_n, dist_instalments, dist_instalment_min_bytes, lazy_gather, dpanel_fused_form, trsm_laswp_fused.  mpf_option_name enumerates them (returns the count). */
+ * hgemm_split_pad, hgemm_big, hgemm_big_tile, dgemm_dma, generic_fused, pivot_fp64, fp64_rowmajor, fp64_rowmajor_min_n, dist_instalments, dist_instalment_min_bytes, lazy_gather, dpanel_fused_form, trsm_laswp_fused.  mpf_option_name enumerates them (returns the count). */
 /* Rows of the tallest panel the LDS-resident pivot kernel takes -- all its workgroups must be resident at once -- beside `waiters`
  * workgroups of kernels that wait for its progress (0: alone; a negative value -w: beside the pipelined chain's gated interchange
  * kernel on a panel of w columns).  Derived from the kernels' LDS / register footprints and the occupancy API (csrc/fp16_panel.hip):
@@ -158,6 +168,20 @@ int mpf_laswp(mpf_ctx *ctx, double *d_A, int64_t lda, int64_t ncols, int32_t k, 
 /* dgetf2_native_npv, dgetf2_native_npv.cu:11-36, in place with leading dimension ld (no packed
  * copy: replaces the extract / write-back memcpy loops MPF.cu:168-200 too). */
 int mpf_dgetf2_npv(mpf_ctx *ctx, double *d_P, int64_t ld, int32_t rows, int32_t cols, int32_t fused);
+/* LAPACK dgetf2 on a panel (build extension; the reference has no fp64 pivot search): partial pivoting in fp64, in place on
+ * d_P[rows x cols] with leading dimension ld; any rows >= 1, 1 <= cols <= 65535.
+ * Pivot rule (idamax): for column j the pivot is the smallest row index p >= j with |a_pj| largest over rows j .. rows-1 of the
+ * column as updated by the columns < j; comparison is a strict >, so the first maximum wins; a NaN never beats a number; a column
+ * whose remaining part is all zero or all NaN keeps p = j.  d_ipiv[j] = p + 1 + ipiv_offset for j < min(rows, cols) (the convention
+ * of mpf_hgetf2_pivots); rows j and p are exchanged in all columns of the panel.
+ * Arithmetic: that of mpf_dgetf2_npv (contract C3), honouring `fused`: the multiplier is a_ij / a_jj, each element is then updated
+ * once per k in ascending order (separate multiply and subtract, or one FMA).  Bit contract: the factored panel equals, bit for bit,
+ * mpf_dgetf2_npv applied to the same panel with its rows pre-permuted by the returned pivots.
+ * info (host, optional): first zero pivot, 1-based, or 0; when given the call synchronises, otherwise it is asynchronous.
+ * One or two ordinary launches per column (csrc/dpivot.hip); the kernel boundary is the only inter-workgroup synchronisation: no
+ * spinning, no bounded waits, no LDS-residency or co-residency requirement. */
+int mpf_dgetf2_piv(mpf_ctx *ctx, double *d_P, int64_t ld, int32_t rows, int32_t cols, int32_t fused,
+                   int32_t ipiv_offset, int32_t *d_ipiv, int32_t *info /* host, optional */);
 /* cublasDtrsm(LEFT, LOWER, N, UNIT, m, n, 1.0, L, ldl, B, ldb), call site MPF.cu:215-225. */
 int mpf_dtrsm_llnu(mpf_ctx *ctx, int32_t m, int64_t n, const double *d_L, int64_t ldl, double *d_B,
                    int64_t ldb);
@@ -306,6 +330,7 @@ int mpf_gecon(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t N, char no
  *      columns if colcnd < 0.1); 2 always; nothing when mpf_geequ reports a zero row or column.  d_work = Dr A Dc (ld = N).
  *      In the low-precision modes an equilibrated matrix gets one more global power of two, folded into Dr (equed then includes
  *      rows), so that max |Dr A Dc| lies in [2^13, 2^14): the fp16 operands saturate at 65504 and go subnormal below 2^-14.
+ *      (With option pivot_fp64 the pivots are searched in fp64, but this step stays: the update operands of these modes are still fp16.)
  *   2. factor d_work in the mode try_fp16 asks for (0: fp64, 1: fp16, 2: fp16x3), 3. mpf_gecon on those factors (norm '1',
  *      'I' for trans = 1), 4. if 1 / rcond > kappa_max (0: 1e4 for fp16, 1e6 for fp16x3) factor again in fp64 at once;
  *   5. otherwise refine against the ORIGINAL A: r = b - A x (or b - A^T x) in fp64, correction Dc (L U)^-1 P (Dr r) (trans = 1:
@@ -450,7 +475,8 @@ int mpf_rccl_info(mpf_ctx *ctx, mpf_rccl_info_t *out);
 int mpf_rccl_bcast_probe(mpf_ctx *ctx, int64_t bytes, int32_t root, int32_t reps, double *ms_per_bcast);
 int mpf_rccl_selftest(mpf_ctx *ctx); /* one small broadcast + all-reduce on the communicator (every rank calls it) */
 /* The panel loop MPF.cu:100-242 over the block-cyclic layout (look-ahead schedule: the owner of panel k+1 updates that block
- * first, runs its chain and posts the broadcast on a side stream under everybody's update k).  Returns this rank's info. */
+ * first, runs its chain and posts the broadcast on a side stream under everybody's update k).  Returns this rank's info.
+ * The fp64 pivot search (mpf_opts.pivot_search = 1, option pivot_fp64) is single-GPU only: -1 with a message here. */
 int mpf_factor_dist(mpf_ctx *ctx, double *d_Aloc, int64_t ldloc, int64_t N, int32_t nb, int32_t *d_ipiv, const mpf_dist *dist,
                     const mpf_opts *opts);
 /* Optional point-to-point transport next to the caller's own broadcast / all-reduce callbacks (with NULL callbacks in mpf_dist the

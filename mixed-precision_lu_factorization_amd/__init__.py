@@ -33,6 +33,7 @@ C_ABI_SYMBOLS = [
     "mpf_solve_gmres_ir", "mpf_trim", "mpf_dist_set_p2p",
     "mpf_solve_ir_trans", "mpf_lange", "mpf_geequ", "mpf_gecon", "mpf_gesvx",
     "mpf_getrs", "mpf_solve_ir_block", "mpf_gerfs", "mpf_gesvx_block",
+    "mpf_dgetf2_piv",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -40,7 +41,7 @@ CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference
 
 class MpfOpts(C.Structure):
     _fields_ = [("trailing", C.c_int32), ("verbose", C.c_int32), ("fused_panel", C.c_int32),
-                ("sync_timing", C.c_int32), ("no_lookahead", C.c_int32), ("superpanel", C.c_int32), ("pivot_path", C.c_int32), ("reserved", C.c_int32)]
+                ("sync_timing", C.c_int32), ("no_lookahead", C.c_int32), ("superpanel", C.c_int32), ("pivot_path", C.c_int32), ("pivot_search", C.c_int32)]
 
 
 class MpfStats(C.Structure):
@@ -52,7 +53,7 @@ class MpfStats(C.Structure):
                 ("pivot_path", C.c_int32), ("gemm_flops", C.c_double), ("gemm_bytes", C.c_double),
                 ("ms_gemm_big", C.c_double), ("gemm_big_flops", C.c_double), ("gemm_big_bytes", C.c_double),
                 ("ms_cvt", C.c_double), ("ms_blockrow", C.c_double), ("gemm_big_launches", C.c_int32), ("host_rows_streamed", C.c_int32),
-                ("host_late_segments", C.c_int32), ("reserved", C.c_int32)]
+                ("host_late_segments", C.c_int32), ("pivot_search", C.c_int32)]
 
 
 class MpfIrStats(C.Structure):
@@ -157,6 +158,7 @@ def load_library(probe=False):
     L.mpf_hgetf2.argtypes = [vp, vp, i64, i32, i32, vp]
     L.mpf_laswp.argtypes = [vp, vp, i64, i64, i32, i32, vp]
     L.mpf_dgetf2_npv.argtypes = [vp, vp, i64, i32, i32, i32]
+    L.mpf_dgetf2_piv.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp, C.POINTER(i32)]
     L.mpf_dtrsm_llnu.argtypes = [vp, i32, i64, vp, i64, vp, i64]
     L.mpf_dgemm_minus.argtypes = [vp, i64, i64, i32, vp, i64, vp, i64, vp, i64]
     L.mpf_hgemm_minus.argtypes = [vp, i64, i64, i32, vp, i64, vp, i64, vp, i64, i32]
@@ -366,9 +368,10 @@ class MPFContext:
 
     # ---- whole path ------------------------------------------------------------------------
     def factor(self, A, nb, ipiv=None, trailing=TRAIL_FP64, fused_panel=False, sync_timing=False, verbose=False,
-               no_lookahead=False, superpanel=0, pivot_path=0):
+               no_lookahead=False, superpanel=0, pivot_path=0, pivot_search=0):
         """mpf_factor_dev: in-place MPF of the column-major device matrix A (N x N).
-        Returns (ipiv int32 device tensor, info)."""
+        pivot_search: 0 = the reference's fp16 pre-pivoting, 1 = LAPACK's partial pivoting, searched in fp64 (also context option
+        pivot_fp64, which gesv, gesvx, gesvx_block and factor_host follow).  Returns (ipiv int32 device tensor, info)."""
         self._bind()
         t = self.torch
         n = A.shape[0]
@@ -376,7 +379,8 @@ class MPFContext:
         if ipiv is None:
             ipiv = t.arange(1, n + 1, dtype=t.int32, device=self.device)  # benchmark.cpp:215-217
         o = MpfOpts(trailing=trailing, verbose=int(verbose), fused_panel=int(fused_panel), sync_timing=int(sync_timing),
-                    no_lookahead=int(no_lookahead), superpanel=int(superpanel), pivot_path=int(pivot_path))
+                    no_lookahead=int(no_lookahead), superpanel=int(superpanel), pivot_path=int(pivot_path),
+                    pivot_search=int(pivot_search))
         rc = self.L.mpf_factor_dev(self.h, _ptr(A), _colmajor_ld(A), n, nb, _ptr(ipiv), C.byref(o))
         return ipiv, self._check(rc, "mpf_factor_dev")
 
@@ -392,7 +396,8 @@ class MPFContext:
         n = A_np.shape[0]
         if ipiv_np is None:
             ipiv_np = np.arange(1, n + 1, dtype=np.int32)
-        o = MpfOpts(trailing=kw.get("trailing", TRAIL_FP64), fused_panel=int(kw.get("fused_panel", False)))
+        o = MpfOpts(trailing=kw.get("trailing", TRAIL_FP64), fused_panel=int(kw.get("fused_panel", False)),
+                    pivot_search=int(kw.get("pivot_search", 0)))
         rc = self.L.mpf_factor_host(self.h, C.c_void_p(A_np.ctypes.data), n, nb, C.c_void_p(ipiv_np.ctypes.data),
                                     C.byref(o))
         return ipiv_np, self._check(rc, "mpf_factor_host")
@@ -471,14 +476,16 @@ class MPFContext:
         self._bind()
         self._check(self.L.mpf_dist_set_p2p(self.h, fn if fn is not None else C.cast(None, P2P_FN), None), "mpf_dist_set_p2p")
 
-    def factor_dist(self, Aloc, n, nb, dist, ipiv=None, trailing=TRAIL_FP64, no_lookahead=False, pivot_path=0, verbose=False, superpanel=0):
+    def factor_dist(self, Aloc, n, nb, dist, ipiv=None, trailing=TRAIL_FP64, no_lookahead=False, pivot_path=0, verbose=False, superpanel=0,
+                    pivot_search=0):
         """mpf_factor_dist: Aloc = this rank's column blocks (n x local columns, column-major); returns (ipiv, info).
         superpanel: panels per super-panel in the fp16 modes (0 = the context's default, 1 = one-level schedule)."""
         self._bind()
         t = self.torch
         if ipiv is None:
             ipiv = t.arange(1, n + 1, dtype=t.int32, device=self.device)
-        o = MpfOpts(trailing=trailing, no_lookahead=int(no_lookahead), pivot_path=int(pivot_path), verbose=int(verbose), superpanel=int(superpanel))
+        o = MpfOpts(trailing=trailing, no_lookahead=int(no_lookahead), pivot_path=int(pivot_path), verbose=int(verbose), superpanel=int(superpanel),
+                    pivot_search=int(pivot_search))
         ld = _colmajor_ld(Aloc) if Aloc.shape[1] > 0 else n
         rc = self.L.mpf_factor_dist(self.h, _ptr(Aloc) if Aloc.shape[1] > 0 else C.c_void_p(0), max(ld, n), n, nb, _ptr(ipiv),
                                     C.byref(dist), C.byref(o))
@@ -538,6 +545,18 @@ class MPFContext:
         self._bind()
         rows, cols = P.shape
         self._check(self.L.mpf_dgetf2_npv(self.h, _ptr(P), _colmajor_ld(P), rows, cols, int(fused)), "dgetf2_npv")
+
+    def dgetf2_piv(self, P, fused=False, ipiv_offset=0):
+        """mpf_dgetf2_piv: LAPACK dgetf2 (fp64 partial pivoting) in place on the column-major panel P (rows x cols).
+        Returns (ipiv int32[min(rows, cols)] = pivot row + 1 + ipiv_offset, info = first zero pivot or 0)."""
+        self._bind()
+        t = self.torch
+        rows, cols = P.shape
+        ipiv = t.zeros(min(rows, cols), dtype=t.int32, device=self.device)
+        info = C.c_int32(0)
+        self._check(self.L.mpf_dgetf2_piv(self.h, _ptr(P), _colmajor_ld(P), rows, cols, int(fused), int(ipiv_offset), _ptr(ipiv),
+                                          C.byref(info)), "dgetf2_piv")
+        return ipiv, info.value
 
     def dtrsm_llnu(self, Lm, B):
         self._bind()

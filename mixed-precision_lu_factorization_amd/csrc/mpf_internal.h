@@ -45,6 +45,7 @@ struct MpfWorkspace {
 // on two host threads never share or race on them.
 struct MpfTuning {
     int safe_pivots = 0;                 // MPF_SAFE_PIVOTS=1: generic (never-waiting) pivot path and schedule always
+    int pivot_fp64 = 0;                  // MPF_PIVOT_FP64=1: every factorization searches its pivots in fp64 (mpf_opts.pivot_search = 1; dpivot.hip)
     int chain_pipeline = 1;              // MPF_CHAIN_PIPELINE=0: the fp64 panel waits for the whole pivot kernel
     long long chain_pipeline_below = 10240; // MPF_CHAIN_PIPELINE_BELOW: fp64 mode pipelines the chain only below this trailing size (re-tuned in round 4
                                             // after the pivot kernel got faster: 8192 .. 14336 within 1 ms of each other, 18432 + 3 ms, 0 + 9 ms)
@@ -226,6 +227,8 @@ struct mpf_ctx {
     // generic (global-memory) fp16 pivot path, fp16_panel_generic.hip: packed fp16 panel + per-block candidates
     Buf<unsigned short> g16;
     Buf<unsigned long long> gcand;
+    // pivoting fp64 panel, dpivot.hip: per-workgroup candidates with their rows, two launch parities
+    Buf<unsigned long long> dpiv;
     // distributed path (mpf_dist.cpp): RCCL communicator (dlopen'ed), two panel message buffers
     void *rccl_comm = nullptr;
     int rccl_rank = 0, rccl_world = 0;
@@ -323,6 +326,11 @@ int launch_laswp(mpf_ctx *c, double *A, int64_t lda, int64_t ncols, int k, int c
 // resolve a panel's sequential swap list (<= 256 swaps, global 1-based pivots) into a moved-row list
 int launch_laswp_plan(mpf_ctx *c, const int *d_ipiv, int k, int cols, MovedList *out);
 int launch_dgetf2_npv(mpf_ctx *c, double *P, int64_t ld, int rows, int cols, int fused, int info_base);
+// dpivot.hip: LAPACK dgetf2 on the panel (fp64 pivot search, launch_dgetf2_npv's arithmetic); d_ipiv[j] = pivot row + 1 + ipiv_offset
+// for j < min(rows, cols); first zero pivot into the workspace's info word as launch_dgetf2_npv.  _reserve: its scratch for panels of
+// up to `rows` rows, so that a factorization allocates once, before its first launch
+int launch_dgetf2_piv(mpf_ctx *c, double *P, int64_t ld, int rows, int cols, int fused, int info_base, int ipiv_offset, int *d_ipiv);
+int dgetf2_piv_reserve(mpf_ctx *c, int rows);
 int launch_dtrsm_llnu(mpf_ctx *c, int m, int64_t n, const double *L, int64_t ldl, double *B, int64_t ldb);
 int launch_dgemm_minus(mpf_ctx *c, int64_t m, int64_t n, int k, const double *A, int64_t lda,
                        const double *B, int64_t ldb, double *C, int64_t ldc);
