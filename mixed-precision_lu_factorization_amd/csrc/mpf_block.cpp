@@ -6,10 +6,7 @@
 // equilibrated copy Dr A Dc: mpf_gesvx_block (mpf_expert.cpp) calls them with its scales, the public functions with none.
 // The right-hand sides go through the device in groups of at most GROUP_TILES tiles of BLK_T columns (solve_block.hip); every
 // triangular step and every residual is one pass over the factor block / over A for the whole group.
-#include "mpf_internal.h"
-#include <cfloat>
-#include <chrono>
-#include <cmath>
+#include "solve_common.h"
 
 namespace {
 constexpr int GROUP_TILES = 16;   // 512 columns per group: six N x 512 tile sets of scratch at most (mpf_gerfs; 805 MB at N = 32768)
@@ -102,22 +99,10 @@ int blk_refine_core(mpf_ctx *c, bool tr, const double *d_A, int64_t lda, const d
             if (!rc) rc = col_norms(c, R, g, N, ncols, nr);
             if (rc) return rc;
             bool any = false;
-            for (int64_t j = 0; j < ncols; ++j) {   // ir_core's rules, column by column
-                mask[(size_t)j] = 0;
-                if (!active[(size_t)j]) continue;
-                mpf_ir_stats &s = st[(size_t)(j0 + j)];
-                s.rel_residual = nr[(size_t)j] / nb2[(size_t)j];
-                s.history[it] = s.rel_residual;
-                s.iterations = it;
-                bool stop = false;
-                if (s.rel_residual <= tol) { s.converged = 1; stop = true; }
-                else if (it >= max_iter || !(s.rel_residual == s.rel_residual)) stop = true;
-                else if (it >= 2 && s.history[it] > 0.7 * s.history[it - 1] && s.history[it - 1] > 0.7 * s.history[it - 2]) {
-                    s.stalled = 1;
-                    stop = true;
-                }
-                if (stop) active[(size_t)j] = 0;
-                else { mask[(size_t)j] = 1; any = true; }
+            for (int64_t j = 0; j < ncols; ++j) {   // ir_step's rules, column by column; a stopped column is frozen
+                if (active[(size_t)j]) active[(size_t)j] = ir_step(st[(size_t)(j0 + j)], it, nr[(size_t)j] / nb2[(size_t)j], max_iter, tol);
+                mask[(size_t)j] = active[(size_t)j];
+                any = any || active[(size_t)j];
             }
             if (!any) break;
             MPF_HIP_TRY(c, hipMemcpyAsync(c->blk_mask, mask.data(), (size_t)tcols * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -140,9 +125,7 @@ int blk_bounds_core(mpf_ctx *c, bool tr, const double *d_A, int64_t lda, const d
     if (itmax <= 0) itmax = 5;
     if (itmax > 31) itmax = 31;
     int rc;
-    // LAPACK's constants: dlamch('E') is the relative machine epsilon 2^-53, not the spacing DBL_EPSILON
-    const double eps = 0x1p-53, safmin = DBL_MIN, nz = (double)(N + 1), safe1 = nz * safmin, safe2 = safe1 / eps;
-    constexpr int LACN2_ITMAX = 5;
+    const double eps = LAPACK_EPS, nz = (double)(N + 1), safe1 = gerfs_safe1(N), safe2 = gerfs_safe2(N);
     for (int32_t j0 = 0; j0 < nrhs; j0 += GROUP_TILES * BLK_T) {
         const int64_t ncols = std::min<int64_t>(nrhs - j0, GROUP_TILES * BLK_T);
         Group g;
@@ -212,71 +195,55 @@ int blk_bounds_core(mpf_ctx *c, bool tr, const double *d_A, int64_t lda, const d
             int r2 = launch_blk_scale(c, V, Wt, g.ldt, g.ntiles);
             return r2 ? r2 : tile_getrs(c, d_LU, ldlu, N, tr, V, V, S1, S2, g, pre, post);
         };
-        auto fill = [&]() {
+        std::vector<Lacn2Col> col((size_t)ncols);   // dlacn2's decisions per column (solve_rules.h); live = still in its loop
+        for (int64_t j = ncols; j < tcols; ++j) kind[j] = -1;
+        auto fill = [&](int stage) {   // 0: 1/N; 1: e_j for the live columns, 3 (zero) for the others; 2: the alternating vector
+            for (int64_t j = 0; j < ncols; ++j) { kind[j] = stage == 1 && !col[(size_t)j].live ? 3 : stage; at[j] = (int)col[(size_t)j].j; }
             int r2 = upload(d_kind, arg);
             return r2 ? r2 : launch_blk_lacn2_fill(c, V, N, ncols, g.ldt, d_kind, d_at);
         };
         auto sign = [&]() {   // live columns: v = isgn = sign(v); the others: v = 0
+            for (int64_t j = 0; j < ncols; ++j) mask[(size_t)j] = col[(size_t)j].live;
             int r2 = upload(c->blk_mask, mask);
             return r2 ? r2 : launch_blk_lacn2_sign(c, V, Isgn, N, ncols, g.ldt, c->blk_mask);
         };
-        std::vector<double> est((size_t)ncols, 0.0);
-        std::vector<int> iter((size_t)ncols, 1);
-        std::fill(mask.begin(), mask.end(), 0);
-        for (int64_t j = 0; j < tcols; ++j) { kind[j] = j < ncols ? 0 : -1; at[j] = 0; }
-        rc = fill();
+        rc = fill(0);
         if (!rc) rc = kase1();
         if (!rc) rc = col_reduce(c, 1, V, g, N, ncols, Isgn, nullptr, 2, red);
         if (rc) return rc;
-        for (int64_t j = 0; j < ncols; ++j) est[(size_t)j] = red[(size_t)j];
+        for (int64_t j = 0; j < ncols; ++j) col[(size_t)j].first_product(red[(size_t)j], N);
         if (N > 1) {
-            for (int64_t j = 0; j < ncols; ++j) mask[(size_t)j] = 1;   // (mask = the columns still in dlacn2's loop)
             rc = sign();
             if (!rc) rc = kase2();
             if (!rc) rc = col_reduce(c, 2, V, g, N, ncols, nullptr, d_at, 3, red);
             if (rc) return rc;
-            for (int64_t j = 0; j < ncols; ++j) { at[j] = (int)red[(size_t)(ncols + j)]; iter[(size_t)j] = 2; }
+            for (int64_t j = 0; j < ncols; ++j) col[(size_t)j].first_transposed((int64_t)red[(size_t)(ncols + j)]);
             for (;;) {
-                for (int64_t j = 0; j < ncols; ++j) kind[j] = mask[(size_t)j] ? 1 : 3;
-                rc = fill();
+                rc = fill(1);
                 if (!rc) rc = kase1();
                 if (!rc) rc = col_reduce(c, 1, V, g, N, ncols, Isgn, nullptr, 2, red);
                 if (rc) return rc;
                 bool any = false;
-                for (int64_t j = 0; j < ncols; ++j) {
-                    if (!mask[(size_t)j]) continue;
-                    const double estold = est[(size_t)j];
-                    est[(size_t)j] = red[(size_t)j];
-                    if (red[(size_t)(ncols + j)] == 0 || est[(size_t)j] <= estold) mask[(size_t)j] = 0;   // repeated signs, or no growth
-                    else any = true;
-                }
+                for (int64_t j = 0; j < ncols; ++j) any = col[(size_t)j].product(red[(size_t)j], red[(size_t)(ncols + j)] == 0) || any;
                 if (!any) break;
                 rc = sign();
                 if (!rc) rc = kase2();
                 if (!rc) rc = col_reduce(c, 2, V, g, N, ncols, nullptr, d_at, 3, red);   // (d_at still holds jlast)
                 if (rc) return rc;
                 any = false;
-                for (int64_t j = 0; j < ncols; ++j) {
-                    if (!mask[(size_t)j]) continue;
-                    at[j] = (int)red[(size_t)(ncols + j)];
-                    if (red[(size_t)(2 * ncols + j)] != red[(size_t)j] && iter[(size_t)j] < LACN2_ITMAX) { ++iter[(size_t)j]; any = true; }
-                    else mask[(size_t)j] = 0;
-                }
+                for (int64_t j = 0; j < ncols; ++j)
+                    any = col[(size_t)j].transposed((int64_t)red[(size_t)(ncols + j)], red[(size_t)j], red[(size_t)(2 * ncols + j)]) || any;
                 if (!any) break;
             }
-            for (int64_t j = 0; j < ncols; ++j) kind[j] = 2;   // final stage: the alternating vector
-            rc = fill();
+            rc = fill(2);   // final stage
             if (!rc) rc = kase1();
             if (!rc) rc = col_reduce(c, 1, V, g, N, ncols, Isgn, nullptr, 2, red);
             if (rc) return rc;
-            for (int64_t j = 0; j < ncols; ++j) {
-                const double temp = 2.0 * (red[(size_t)j] / (double)(3 * N));
-                if (temp > est[(size_t)j]) est[(size_t)j] = temp;
-            }
+            for (int64_t j = 0; j < ncols; ++j) col[(size_t)j].final_stage(red[(size_t)j], N);
         }
         for (int64_t j = 0; j < ncols; ++j) {
-            ferr[j0 + j] = xmax[(size_t)j] != 0 ? est[(size_t)j] / xmax[(size_t)j] : est[(size_t)j];
-            st[(size_t)(j0 + j)].lacn2_iterations = iter[(size_t)j];
+            ferr[j0 + j] = xmax[(size_t)j] != 0 ? col[(size_t)j].est / xmax[(size_t)j] : col[(size_t)j].est;
+            st[(size_t)(j0 + j)].lacn2_iterations = col[(size_t)j].iter;
             st[(size_t)(j0 + j)].solves = solves;
         }
     }
@@ -326,7 +293,7 @@ int mpf_solve_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda
     rc = blk_refine_core(c, trans == 1, d_A, lda, d_LU, ldlu, N, nrhs, d_B, ldb, d_X, ldx, max_iter, tol, nullptr, nullptr, st.data());
     if (rc) return rc;
     MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const double ms = ms_since(t0);
     for (auto &s : st) s.ms_total = ms;
     if (stats) std::copy(st.begin(), st.end(), stats);
     return solve_check_waits(c);
@@ -348,7 +315,7 @@ int mpf_gerfs(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const d
     rc = blk_bounds_core(c, trans == 1, d_A, lda, d_LU, ldlu, N, nrhs, d_B, ldb, d_X, ldx, itmax, ferr, berr, nullptr, nullptr, st.data());
     if (rc) return rc;
     MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const double ms = ms_since(t0);
     for (auto &s : st) s.ms_total = ms;
     if (stats) std::copy(st.begin(), st.end(), stats);
     return solve_check_waits(c);

@@ -15,7 +15,7 @@
 // The broadcast is a callback (mpf_dist.bcast) so that any transport can carry it; the built-in one is RCCL
 // (mpf_rccl_init: ncclBroadcast / ncclAllReduce on the context's communicator, resolved with dlopen so that single-GPU
 // users never load RCCL).  Tests drive the same loop through a gloo-backed callback with several ranks on one GPU.
-#include "mpf_internal.h"
+#include "solve_common.h"
 #include <dlfcn.h>
 #include <climits>
 #include <cstdio>
@@ -851,8 +851,8 @@ int mpf_solve_ir_dist(mpf_ctx *c, const double *d_Aloc, int64_t lda, const doubl
         double vote[2] = {p2p_fn ? 1.0 : 0.0, 1.0};
         MPF_HIP_TRY(c, hipMemcpyAsync(scal, vote, sizeof vote, hipMemcpyHostToDevice, S));
         { const int e = ar_fn(user, scal, 2, (void *)S); if (e) return e < 0 ? e : -5; }
-        MPF_HIP_TRY(c, hipMemcpyAsync(vote, scal, sizeof vote, hipMemcpyDeviceToHost, S));
-        MPF_HIP_TRY(c, hipStreamSynchronize(S));
+        rc = read_scalars(c, scal, vote, 2);
+        if (rc) return rc;
         if (vote[0] != vote[1]) { p2p_fn = nullptr; p2p_user = nullptr; }
     }
     double *up = xloc, *rbuf = c->solve_buf + 3 * SN;   // (xloc is only used by the residual, between two solves)
@@ -916,15 +916,7 @@ int mpf_solve_ir_dist(mpf_ctx *c, const double *d_Aloc, int64_t lda, const doubl
         }
         return e;
     };
-    auto norm = [&](const double *v, double &out) -> int {
-        int e = launch_norm2(c, v, N, scal);
-        if (e) return e;
-        double h = 0;
-        MPF_HIP_TRY(c, hipMemcpyAsync(&h, scal, sizeof(double), hipMemcpyDeviceToHost, S));
-        MPF_HIP_TRY(c, hipStreamSynchronize(S));
-        out = std::sqrt(h);
-        return 0;
-    };
+    auto norm = [&](const double *v, double &out) -> int { return vec_norm2(c, v, N, scal, out); };   // (S is c->stream)
     auto residual = [&](const double *x, double *rr) -> int { // rr = b - A x: own columns, then the sum over ranks
         int e = 0;
         for (int b = L.rank; b < L.nblocks && !e; b += L.world) // x restricted to the columns this rank owns
@@ -933,29 +925,8 @@ int mpf_solve_ir_dist(mpf_ctx *c, const double *d_Aloc, int64_t lda, const doubl
         if (!e && L.world > 1) { e = ar_fn(user, rr, N, (void *)S); if (e) e = e < 0 ? e : -5; }
         return e;
     };
-    double nb2 = 0;
-    rc = norm(d_b, nb2);
+    rc = refine_vector(c, N, d_b, d_x, max_iter, tol, st, r, d, norm, lu_solve, residual);
     if (rc) return rc;
-    if (nb2 == 0) nb2 = 1;
-    rc = lu_solve(d_b, d_x);
-    if (rc) return rc;
-    for (int it = 0;; ++it) {
-        rc = residual(d_x, r);
-        if (rc) return rc;
-        double nr = 0;
-        rc = norm(r, nr);
-        if (rc) return rc;
-        st.rel_residual = nr / nb2;
-        st.history[it] = st.rel_residual;
-        st.iterations = it;
-        if (st.rel_residual <= tol) { st.converged = 1; break; }
-        if (it >= max_iter || !(st.rel_residual == st.rel_residual)) break;
-        if (it >= 2 && st.history[it] > 0.7 * st.history[it - 1] && st.history[it - 1] > 0.7 * st.history[it - 2]) { st.stalled = 1; break; }
-        rc = lu_solve(r, d);
-        if (rc) return rc;
-        rc = launch_axpy(c, 1.0, d, d_x, N);
-        if (rc) return rc;
-    }
     hipEventRecord(c->ev1, S);
     MPF_HIP_TRY(c, hipStreamSynchronize(S));
     float ms = 0;

@@ -6,10 +6,8 @@
 //   mpf_gesvx            equilibrate, factor, estimate rcond, refine against the original matrix, fall back to fp64
 //   mpf_gesvx_block      the same steps for many right-hand sides: blocked refinement and dgerfs's bounds on the scaled factors
 // Kernels in solve_ext.hip; the device only ever hands scalars back to the host.
-#include "mpf_internal.h"
+#include "solve_common.h"
 #include <cfloat>
-#include <chrono>
-#include <cmath>
 
 namespace {
 // the context's expert-driver vectors, `len` doubles each: 0 .. 2 dlacn2 (x, sign(x), isgn; 0 also the norms' scratch),
@@ -26,14 +24,6 @@ int ext_vectors(mpf_ctx *c, int64_t len, Ext &e) {
     e.base = c->ext_vec;
     e.len = len;
     return 0;
-}
-int read_scalars(mpf_ctx *c, const double *d, double *out, int k) {
-    MPF_HIP_TRY(c, hipMemcpyAsync(out, d, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-double ms_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
 
 int lange_core(mpf_ctx *c, const Ext &e, const double *A, int64_t lda, int64_t M, int64_t N, char norm, double &out) {
@@ -94,6 +84,7 @@ int gecon_core(mpf_ctx *c, const Ext &e, const double *LU, int64_t ld, int64_t N
         (t ? st.solves_t : st.solves)++;
         return lu_apply(c, LU, ld, N, t, x);
     };
+    Lacn2Col col;   // dlacn2's decisions (solve_rules.h); the products and their reductions are formed here
     double sc[3];
     int rc = launch_lacn2_fill(c, x, N, 0, 0);
     if (!rc) rc = apply(false);
@@ -101,54 +92,49 @@ int gecon_core(mpf_ctx *c, const Ext &e, const double *LU, int64_t ld, int64_t N
     if (N == 1) {
         rc = launch_dasum(c, x, 1, s);
         if (!rc) rc = read_scalars(c, s, sc, 1);
-        ainvnm = sc[0];
-        st.iterations = 1;
+        col.first_product(sc[0], N);
+        ainvnm = col.est;
+        st.iterations = col.iter;
         return rc;
     }
     rc = launch_lacn2_sign(c, x, nullptr, N, xs, s);
     if (!rc) rc = read_scalars(c, s, sc, 2);
     if (rc) return rc;
-    double est = sc[0];
+    col.first_product(sc[0], N);
     MPF_HIP_TRY(c, hipMemcpyAsync(isgn, xs, vb, hipMemcpyDeviceToDevice, c->stream));
     MPF_HIP_TRY(c, hipMemcpyAsync(x, xs, vb, hipMemcpyDeviceToDevice, c->stream));
     rc = apply(true);
     if (!rc) rc = launch_idamax(c, x, N, s);
     if (!rc) rc = read_scalars(c, s, sc, 2);
     if (rc) return rc;
-    int64_t j = (int64_t)sc[1];
-    int iter = 2;
+    col.first_transposed((int64_t)sc[1]);
     for (;;) {
-        rc = launch_lacn2_fill(c, x, N, 1, j);
+        rc = launch_lacn2_fill(c, x, N, 1, col.j);
         if (!rc) rc = apply(false);
         if (!rc) rc = launch_lacn2_sign(c, x, isgn, N, xs, s);
         if (!rc) rc = read_scalars(c, s, sc, 2);
         if (rc) return rc;
-        const double estold = est;
-        est = sc[0];
-        if (sc[1] == 0 || est <= estold) break;   // repeated sign vector, or no growth: converged
+        if (!col.product(sc[0], sc[1] == 0)) break;
         MPF_HIP_TRY(c, hipMemcpyAsync(isgn, xs, vb, hipMemcpyDeviceToDevice, c->stream));
         MPF_HIP_TRY(c, hipMemcpyAsync(x, xs, vb, hipMemcpyDeviceToDevice, c->stream));
         rc = apply(true);
-        const int64_t jlast = j;
+        const int64_t jlast = col.j;
         if (!rc) rc = launch_idamax(c, x, N, s);
         if (rc) return rc;
         MPF_HIP_TRY(c, hipMemcpyAsync(s + 2, x + jlast, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         rc = read_scalars(c, s, sc, 3);
         if (rc) return rc;
-        j = (int64_t)sc[1];
-        if (sc[2] != sc[0] && iter < 5) { ++iter; continue; }
-        break;
+        if (!col.transposed((int64_t)sc[1], sc[0], sc[2])) break;
     }
-    st.iterations = iter;
+    st.iterations = col.iter;
     // final stage: the alternating test vector
     rc = launch_lacn2_fill(c, x, N, 2, 0);
     if (!rc) rc = apply(false);
     if (!rc) rc = launch_dasum(c, x, N, s);
     if (!rc) rc = read_scalars(c, s, sc, 1);
     if (rc) return rc;
-    const double temp = 2.0 * (sc[0] / (double)(3 * N));
-    if (temp > est) est = temp;
-    ainvnm = est;
+    col.final_stage(sc[0], N);
+    ainvnm = col.est;
     return 0;
 }
 // rcond from anorm and the factors; checks U's diagonal first.  The factors must be prepared.
@@ -170,57 +156,18 @@ int gecon_full(mpf_ctx *c, const Ext &e, const double *LU, int64_t ld, int64_t N
     return 0;
 }
 
-// out = post .* op(pre .* rhs), op = (L U)^-1 P (trans = 0) or P^T (L U)^-T (trans = 1) on factors prepared by solve_setup
-int fsolve(mpf_ctx *c, const Ext &e, const double *LU, int64_t ld, int64_t N, bool trans, const double *pre, const double *post,
-           const double *rhs, double *out) {
-    double *t = e.v(V_TMP);
-    int rc;
-    if (!trans) {
-        const double *src = rhs;
-        if (pre) { rc = launch_vscale(c, rhs, pre, 1.0, t, N); if (rc) return rc; src = t; }
-        rc = launch_gather_rows(c, src, c->perm_buf, out, N);
-        if (!rc) rc = lu_apply(c, LU, ld, N, false, out);
-    } else {
-        rc = launch_vscale(c, rhs, pre, 1.0, t, N);
-        if (!rc) rc = lu_apply(c, LU, ld, N, true, t);
-        if (!rc) rc = launch_scatter_rows(c, t, c->perm_buf, out, N);
-    }
-    if (!rc && post) rc = launch_vscale(c, out, post, 1.0, out, N);
-    return rc;
-}
+// the refinement scratch among the expert driver's vectors, or wherever else it lives (solve_ir_columns): residual, correction,
+// factor_solve's temporary, one scalar
+struct IrScratch { double *r, *d, *tmp, *s; };
+IrScratch ir_scratch(const Ext &e) { return {e.v(V_RES), e.v(V_COR), e.v(V_TMP), e.scal()}; }
 
-// refinement against the original A (mpf_solve_ir's rules), corrections through fsolve
-int ir_scaled(mpf_ctx *c, const Ext &e, const double *A, int64_t lda, const double *LU, int64_t ld, int64_t N, bool trans, const double *pre,
-              const double *post, const double *b, double *x, int32_t max_iter, double tol, mpf_ir_stats &st) {
-    double *r = e.v(V_RES), *d = e.v(V_COR), *s = e.scal();
-    double nb2 = 0;
-    int rc = launch_norm2(c, b, N, s);
-    if (!rc) rc = read_scalars(c, s, &nb2, 1);
-    if (rc) return rc;
-    nb2 = std::sqrt(nb2);
-    if (nb2 == 0) nb2 = 1;
-    rc = fsolve(c, e, LU, ld, N, trans, pre, post, b, x);
-    if (rc) return rc;
-    for (int it = 0;; ++it) {
-        rc = trans ? launch_residual_t(c, A, lda, x, b, r, N) : launch_residual(c, A, lda, x, b, r, N);
-        double nr = 0;
-        if (!rc) rc = launch_norm2(c, r, N, s);
-        if (!rc) rc = read_scalars(c, s, &nr, 1);
-        if (rc) return rc;
-        st.rel_residual = std::sqrt(nr) / nb2;
-        st.history[it] = st.rel_residual;
-        st.iterations = it;
-        if (st.rel_residual <= tol) { st.converged = 1; break; }
-        if (it >= max_iter || !(st.rel_residual == st.rel_residual)) break;
-        if (it >= 2 && st.history[it] > 0.7 * st.history[it - 1] && st.history[it - 1] > 0.7 * st.history[it - 2]) {
-            st.stalled = 1;
-            break;
-        }
-        rc = fsolve(c, e, LU, ld, N, trans, pre, post, r, d);
-        if (!rc) rc = launch_axpy(c, 1.0, d, x, N);
-        if (rc) return rc;
-    }
-    return 0;
+// refinement against the original op(A) (refine_vector: mpf_solve_ir's rules), x0 and the corrections through factor_solve
+int refine_on_factors(mpf_ctx *c, const IrScratch &w, const double *A, int64_t lda, const double *LU, int64_t ld, int64_t N, bool trans,
+                      const double *pre, const double *post, const double *b, double *x, int32_t max_iter, double tol, mpf_ir_stats &st) {
+    return refine_vector(c, N, b, x, max_iter, tol, st, w.r, w.d,
+                         [&](const double *v, double &out) { return vec_norm2(c, v, N, w.s, out); },
+                         [&](const double *rhs, double *out) { return factor_solve(c, LU, ld, N, trans, pre, post, w.tmp, rhs, out); },
+                         [&](const double *xx, double *r) { return trans ? launch_residual_t(c, A, lda, xx, b, r, N) : launch_residual(c, A, lda, xx, b, r, N); });
 }
 
 // Steps 1 .. 6 of the expert drivers (mpf_gesvx, mpf_gesvx_block): equilibrate, factor d_work, rcond, the kappa_max gate, one
@@ -283,15 +230,14 @@ int gesvx_steps(mpf_ctx *c, const Ext &e, const double *d_A, int64_t lda, int64_
     pre = tr ? ((gs.equed & 2) ? cs : nullptr) : ((gs.equed & 1) ? r : nullptr);
     post = tr ? ((gs.equed & 1) ? r : nullptr) : ((gs.equed & 2) ? cs : nullptr);
 
-    std::vector<int32_t> ident((size_t)N);
-    for (int64_t i = 0; i < N; ++i) ident[(size_t)i] = (int32_t)(i + 1);
     // factor d_work (already the scaled copy) in `mode`, prepare the solves, rcond of the factors
     auto factor_and_rcond = [&](int mode, double &rcond) -> int {
         auto t1 = std::chrono::steady_clock::now();
-        MPF_HIP_TRY(c, hipMemcpyAsync(d_ipiv, ident.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        int r2 = upload_identity_ipiv(c, d_ipiv, N);
+        if (r2) return r2;
         mpf_opts o{};
         o.trailing = mode;
-        int r2 = mpf_factor_dev(c, d_work, N, N, nb, d_ipiv, &o);
+        r2 = mpf_factor_dev(c, d_work, N, N, nb, d_ipiv, &o);
         if (r2 < 0) return r2;
         gs.info = r2;
         gs.ms_factor += ms_since(t1);
@@ -337,27 +283,41 @@ int gesvx_steps(mpf_ctx *c, const Ext &e, const double *d_A, int64_t lda, int64_
 }
 } // namespace
 
-extern "C" {
+int factor_solve(mpf_ctx *c, const double *LU, int64_t ld, int64_t N, bool trans, const double *pre, const double *post, double *tmp,
+                 const double *rhs, double *out) {
+    int rc;
+    if (!trans) {
+        const double *src = rhs;
+        if (pre) { rc = launch_vscale(c, rhs, pre, 1.0, tmp, N); if (rc) return rc; src = tmp; }
+        rc = launch_gather_rows(c, src, c->perm_buf, out, N);
+        if (!rc) rc = lu_apply(c, LU, ld, N, false, out);
+    } else {
+        rc = launch_vscale(c, rhs, pre, 1.0, tmp, N);
+        if (!rc) rc = lu_apply(c, LU, ld, N, true, tmp);
+        if (!rc) rc = launch_scatter_rows(c, tmp, c->perm_buf, out, N);
+    }
+    if (!rc && post) rc = launch_vscale(c, out, post, 1.0, out, N);
+    return rc;
+}
 
-int mpf_solve_ir_trans(mpf_ctx *c, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
-                       int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_iter,
-                       double tol, mpf_ir_stats *stats) {
-    if (!c || !d_A || !d_LU || !d_ipiv || !d_B || !d_X) return -1;
-    if (N <= 0 || nrhs < 0) { c->err = "solve_ir_trans: N must be positive, nrhs >= 0"; return -1; }
-    if (lda < N || ldlu < N) { c->err = "solve_ir_trans: lda / ldlu < N"; return -1; }
-    if (nrhs > 1 && (ldb < N || ldx < N)) { c->err = "solve_ir_trans: ldb / ldx < N"; return -1; }
+// One refinement per column on factors prepared once.  The plain solve keeps its scratch in solve_buf (residual, correction, the
+// scalar: mpf_solve_ir allocates nothing else); the transposed one needs factor_solve's temporary and takes the expert driver's vectors.
+int solve_ir_columns(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
+                     int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_iter, double tol,
+                     mpf_ir_stats *stats) {
     if (max_iter > 31) max_iter = 31;
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     hipEventRecord(c->ev0, c->stream);
     Ext e;
-    int rc = ext_vectors(c, N, e);
+    int rc = trans ? ext_vectors(c, N, e) : 0;
     if (!rc) rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
     if (rc) return rc;
+    const IrScratch w = trans ? ir_scratch(e) : IrScratch{c->solve_buf, c->solve_buf + c->solve_n, nullptr, c->solve_buf + 4 * c->solve_n};
     for (int j = 0; j < nrhs; ++j) {
         mpf_ir_stats st{};
         hipEvent_t e0 = nullptr;
         if (j > 0) { hipEventCreate(&e0); hipEventRecord(e0, c->stream); }
-        rc = ir_scaled(c, e, d_A, lda, d_LU, ldlu, N, true, nullptr, nullptr, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, max_iter, tol, st);
+        rc = refine_on_factors(c, w, d_A, lda, d_LU, ldlu, N, trans, nullptr, nullptr, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, max_iter, tol, st);
         if (rc) { if (e0) hipEventDestroy(e0); return rc; }
         hipEventRecord(c->ev1, c->stream);
         MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -368,6 +328,18 @@ int mpf_solve_ir_trans(mpf_ctx *c, const double *d_A, int64_t lda, const double 
         if (stats) stats[j] = st;
     }
     return solve_check_waits(c);
+}
+
+extern "C" {
+
+int mpf_solve_ir_trans(mpf_ctx *c, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
+                       int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_iter,
+                       double tol, mpf_ir_stats *stats) {
+    if (!c || !d_A || !d_LU || !d_ipiv || !d_B || !d_X) return -1;
+    if (N <= 0 || nrhs < 0) { c->err = "solve_ir_trans: N must be positive, nrhs >= 0"; return -1; }
+    if (lda < N || ldlu < N) { c->err = "solve_ir_trans: lda / ldlu < N"; return -1; }
+    if (nrhs > 1 && (ldb < N || ldx < N)) { c->err = "solve_ir_trans: ldb / ldx < N"; return -1; }
+    return solve_ir_columns(c, true, d_A, lda, d_LU, ldlu, d_ipiv, N, nrhs, d_B, ldb, d_X, ldx, max_iter, tol, stats);
 }
 
 int mpf_lange(mpf_ctx *c, const double *d_A, int64_t lda, int64_t M, int64_t N, char norm, double *out) {
@@ -440,7 +412,7 @@ int mpf_gesvx(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32_t nb,
     const double *pre = nullptr, *post = nullptr;
     rc = gesvx_steps(c, e, d_A, lda, N, nb, d_work, d_ipiv, tr, equilibrate, try_fp16, kappa_max, d_r, d_c, gs, pre, post,
                      [&](const double *pr, const double *po, mpf_ir_stats &ir) {
-                         return ir_scaled(c, e, d_A, lda, d_work, N, N, tr, pr, po, d_b, d_x, max_iter, tol, ir);
+                         return refine_on_factors(c, ir_scratch(e), d_A, lda, d_work, N, N, tr, pr, po, d_b, d_x, max_iter, tol, ir);
                      });
     if (rc) return rc;
     MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -475,19 +447,13 @@ int mpf_gesvx_block(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32
     const bool tr = trans == 1;
     const double *pre = nullptr, *post = nullptr;
     std::vector<mpf_ir_stats> cols((size_t)nrhs);
-    // one attempt: all columns on the factors in d_work; the attempt's summary is its column with the largest final rel_residual
-    // (a NaN counts as largest), so its `converged` says whether EVERY column converged
+    // one attempt: all columns on the factors in d_work; the attempt's summary is its worst column
     rc = gesvx_steps(c, e, d_A, lda, N, nb, d_work, d_ipiv, tr, equilibrate, try_fp16, kappa_max, d_r, d_c, gs, pre, post,
                      [&](const double *pr, const double *po, mpf_ir_stats &worst) {
                          std::fill(cols.begin(), cols.end(), mpf_ir_stats{});
                          int r2 = blk_refine_core(c, tr, d_A, lda, d_work, N, N, nrhs, d_B, ldb, d_X, ldx, max_iter, tol, pr, po, cols.data());
                          if (r2) return r2;
-                         size_t w = 0;
-                         for (size_t j = 1; j < cols.size(); ++j) {
-                             const double a = cols[j].rel_residual, b = cols[w].rel_residual;
-                             if (b == b && (a != a || a > b)) w = j;
-                         }
-                         worst = cols[w];
+                         worst = cols[worst_column(cols.data(), cols.size())];
                          return 0;
                      });
     if (rc) return rc;

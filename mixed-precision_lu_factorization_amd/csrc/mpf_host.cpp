@@ -1,7 +1,7 @@
 // C++ host side of libmpf_amd.so: context, the MPF panel loop (reference MPF.cu:66-256 re-architected
 // as an asynchronous HIP stream of kernels with no per-panel host synchronisation), the refinement
 // solve, the C ABI (include/mpf_c.h) and the drop-in C++ symbol MPF() (include/MPF.h).
-#include "mpf_internal.h"
+#include "solve_common.h"
 #include "../../include/MPF.h"
 #include <climits>
 #include <cstdio>
@@ -1629,7 +1629,7 @@ int mpf_factor_host(mpf_ctx *c, double *A_host, int64_t N, int32_t nb, int32_t *
     hipEventRecord(e0, c->stream);
     const auto t_up0 = std::chrono::steady_clock::now();
     hipMemcpyAsync(dA, A_host, up_bytes, hipMemcpyHostToDevice, c->stream);   // (from pageable memory: returns when the copy is done)
-    const double up_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up0).count();
+    const double up_ms = ms_since(t_up0);
     hipMemcpyAsync(dP, ipiv_host, pbytes, hipMemcpyHostToDevice, c->stream);
     hipEventRecord(e1, c->stream);
     if (plan.nseg) {
@@ -1730,7 +1730,7 @@ int mpf_factor_host(mpf_ctx *c, double *A_host, int64_t N, int32_t nb, int32_t *
             se = hipStreamSynchronize(c->stream);
         }
         // what the call still spent on the way home after the factorization's last kernel (wall clock)
-        c->stats.ms_d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_done).count();
+        c->stats.ms_d2h = ms_since(t_done);
         if (se != hipSuccess) rc = fail(c, -2, std::string("D2H failed: ") + hipGetErrorString(se));
     }
     hipEventDestroy(e0); hipEventDestroy(e1);
@@ -1767,16 +1767,15 @@ int mpf_gesv(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32_t nb, 
     if (N <= 0 || lda < N) return fail(c, -1, "gesv: bad N / lda");
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     mpf_gesv_stats gs{};
-    std::vector<int32_t> ident((size_t)N);
-    for (int64_t i = 0; i < N; ++i) ident[(size_t)i] = (int32_t)(i + 1); // benchmark.cpp:215-217
     auto t0 = std::chrono::steady_clock::now();
     auto attempt = [&](int mode, double &ms_fact, double &ms_ir, mpf_ir_stats &ir) -> int {
         MPF_HIP_TRY(c, hipMemcpy2DAsync(d_work, (size_t)N * 8, d_A, (size_t)lda * 8, (size_t)N * 8, (size_t)N,
                                         hipMemcpyDeviceToDevice, c->stream));
-        MPF_HIP_TRY(c, hipMemcpyAsync(d_ipiv, ident.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        int rc = upload_identity_ipiv(c, d_ipiv, N);
+        if (rc) return rc;
         mpf_opts o{};
         o.trailing = mode;
-        int rc = mpf_factor_dev(c, d_work, N, N, nb, d_ipiv, &o);
+        rc = mpf_factor_dev(c, d_work, N, N, nb, d_ipiv, &o);
         if (rc < 0) return rc;
         gs.info = rc;
         ms_fact = c->stats.ms_total;
@@ -1824,7 +1823,7 @@ int mpf_gesv(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32_t nb, 
         if (rc < 0) return rc;
         gs.path = 2;
     }
-    gs.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    gs.ms_total = ms_since(t0);
     if (stats) *stats = gs;
     return gs.ir_final.converged ? 0 : 1;
 }

@@ -5,9 +5,7 @@
 //   mpf_solve_gmres_ir    GMRES-IR (Carson & Higham): the correction equation A d = r is solved by GMRES preconditioned
 //                         with the low-precision factors, in fp64 -- for inputs where plain refinement does not contract
 //                         (kappa(A) times the factors' error is not << 1: the generator's own matrices in the fp16 mode)
-#include "mpf_internal.h"
-#include <chrono>
-#include <cmath>
+#include "solve_common.h"
 #include <cstring>
 
 // what every solve on one set of factors shares: the pivot sequence as a gather index and the inverted diagonal blocks
@@ -37,65 +35,26 @@ int solve_check_waits(mpf_ctx *c) {
     return 0;
 }
 
-namespace {
-int lu_solve(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t N, const double *rhs, double *out) { // out = U^-1 L^-1 P rhs
-    int e = launch_gather_rows(c, rhs, c->perm_buf, out, N);
-    if (!e) e = launch_trsv_lower_unit(c, d_LU, ldlu, out, N);
-    if (!e) e = launch_trsv_upper(c, d_LU, ldlu, out, N);
-    return e;
-}
-int read_scalar(mpf_ctx *c, const double *d, double &out) {
-    double h = 0;
-    MPF_HIP_TRY(c, hipMemcpyAsync(&h, d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+int read_scalars(mpf_ctx *c, const double *d, double *out, int k) {
+    MPF_HIP_TRY(c, hipMemcpyAsync(out, d, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    out = h;
     return 0;
 }
-int norm2(mpf_ctx *c, const double *v, int64_t N, double &out) {
-    double *scal = c->solve_buf + 4 * c->solve_n;
-    int e = launch_norm2(c, v, N, scal);
-    if (!e) e = read_scalar(c, scal, out);
-    out = std::sqrt(out);
-    return e;
+int upload_identity_ipiv(mpf_ctx *c, int32_t *d_ipiv, int64_t N) {
+    std::vector<int32_t> ident((size_t)N);
+    for (int64_t i = 0; i < N; ++i) ident[(size_t)i] = (int32_t)(i + 1); // benchmark.cpp:215-217
+    MPF_HIP_TRY(c, hipMemcpyAsync(d_ipiv, ident.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream)); // `ident` is a host temporary
+    return 0;
 }
+
+namespace {
+// mpf_solve_gmres_ir's scalars go through the solve scratch's scalar slot
+int norm2(mpf_ctx *c, const double *v, int64_t N, double &out) { return vec_norm2(c, v, N, c->solve_buf + 4 * c->solve_n, out); }
 int dot(mpf_ctx *c, const double *x, const double *y, int64_t N, double &out) {
     double *scal = c->solve_buf + 4 * c->solve_n;
     int e = launch_dot(c, x, y, N, scal);
-    if (!e) e = read_scalar(c, scal, out);
-    return e;
-}
-// classical refinement on prepared factors
-int ir_core(mpf_ctx *c, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, const double *d_b, double *d_x,
-            int32_t max_iter, double tol, mpf_ir_stats &st) {
-    const int64_t S = c->solve_n;
-    double *r = c->solve_buf, *d = c->solve_buf + S;
-    double nb2 = 0;
-    int rc = norm2(c, d_b, N, nb2);
-    if (rc) return rc;
-    if (nb2 == 0) nb2 = 1;
-    rc = lu_solve(c, d_LU, ldlu, N, d_b, d_x);
-    if (rc) return rc;
-    for (int it = 0;; ++it) {
-        rc = launch_residual(c, d_A, lda, d_x, d_b, r, N);
-        if (rc) return rc;
-        double nr = 0;
-        rc = norm2(c, r, N, nr);
-        if (rc) return rc;
-        st.rel_residual = nr / nb2;
-        st.history[it] = st.rel_residual;
-        st.iterations = it;
-        if (st.rel_residual <= tol) { st.converged = 1; break; }
-        if (it >= max_iter || !(st.rel_residual == st.rel_residual)) break;
-        if (it >= 2 && st.history[it] > 0.7 * st.history[it - 1] && st.history[it - 1] > 0.7 * st.history[it - 2]) {
-            st.stalled = 1; // plain refinement is not contracting: kappa(A) is too large for these factors
-            break;
-        }
-        rc = lu_solve(c, d_LU, ldlu, N, r, d);
-        if (rc) return rc;
-        rc = launch_axpy(c, 1.0, d, d_x, N);
-        if (rc) return rc;
-    }
-    return 0;
+    return e ? e : read_scalars(c, scal, &out, 1);
 }
 } // namespace
 
@@ -112,26 +71,7 @@ int mpf_solve_ir_nrhs(mpf_ctx *c, const double *d_A, int64_t lda, const double *
     if (!c || !d_A || !d_LU || !d_ipiv || !d_B || !d_X) return -1;
     if (N <= 0 || nrhs < 0) { c->err = "solve: N must be positive, nrhs >= 0"; return -1; }
     if (nrhs > 1 && (ldb < N || ldx < N)) { c->err = "solve: ldb / ldx < N"; return -1; }
-    if (max_iter > 31) max_iter = 31;
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    hipEventRecord(c->ev0, c->stream);
-    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
-    if (rc) return rc;
-    for (int j = 0; j < nrhs; ++j) {
-        mpf_ir_stats st{};
-        hipEvent_t e0 = nullptr;
-        if (j > 0) { hipEventCreate(&e0); hipEventRecord(e0, c->stream); }
-        rc = ir_core(c, d_A, lda, d_LU, ldlu, N, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, max_iter, tol, st);
-        if (rc) { if (e0) hipEventDestroy(e0); return rc; }
-        hipEventRecord(c->ev1, c->stream);
-        MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        float ms = 0;
-        hipEventElapsedTime(&ms, j > 0 ? e0 : c->ev0, c->ev1); // the first right-hand side carries the set-up
-        if (e0) hipEventDestroy(e0);
-        st.ms_total = ms;
-        if (stats) stats[j] = st;
-    }
-    return solve_check_waits(c);
+    return solve_ir_columns(c, false, d_A, lda, d_LU, ldlu, d_ipiv, N, nrhs, d_B, ldb, d_X, ldx, max_iter, tol, stats);
 }
 
 int mpf_solve_gmres_ir(mpf_ctx *c, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
@@ -153,11 +93,14 @@ int mpf_solve_gmres_ir(mpf_ctx *c, const double *d_A, int64_t lda, const double 
     const int64_t S = c->solve_n;
     double *r = c->solve_buf, *w = c->solve_buf + S;
     mpf_gmres_stats st{};
+    auto apply_factors = [&](const double *rhs, double *out) {   // out = U^-1 L^-1 P rhs
+        return factor_solve(c, d_LU, ldlu, N, false, nullptr, nullptr, nullptr, rhs, out);
+    };
     double nb2 = 0;
     rc = norm2(c, d_b, N, nb2);
     if (rc) return rc;
     if (nb2 == 0) nb2 = 1;
-    rc = lu_solve(c, d_LU, ldlu, N, d_b, d_x);
+    rc = apply_factors(d_b, d_x);
     if (rc) return rc;
     std::vector<double> H((size_t)(m + 1) * m), cs(m), sn(m), g(m + 1), y(m);
     // mpf_gesv gives GMRES-IR the time an fp64 refactorization would take (c->gmres_budget_ms; 0: no limit): every inner
@@ -176,7 +119,7 @@ int mpf_solve_gmres_ir(mpf_ctx *c, const double *d_A, int64_t lda, const double 
         if (st.rel_residual <= tol) { st.converged = 1; break; }
         if (outer >= max_outer || out_of_time || !(st.rel_residual == st.rel_residual)) break;
         // ---- GMRES on M^-1 A d = M^-1 r, M = P^T L U (the factors), modified Gram-Schmidt, Givens rotations on the host ----
-        rc = lu_solve(c, d_LU, ldlu, N, r, V);                           // z0 = M^-1 r
+        rc = apply_factors(r, V);                                       // z0 = M^-1 r
         if (rc) return rc;
         double beta = 0;
         rc = norm2(c, V, N, beta);
@@ -193,7 +136,7 @@ int mpf_solve_gmres_ir(mpf_ctx *c, const double *d_A, int64_t lda, const double 
             double *vk = V + (int64_t)k * N, *vn = V + (int64_t)(k + 1) * N;
             rc = launch_residual(c, d_A, lda, vk, nullptr, w, N);        // w = -A v_k
             if (!rc) rc = launch_scal(c, -1.0, w, N);
-            if (!rc) rc = lu_solve(c, d_LU, ldlu, N, w, vn);             // v_{k+1} = M^-1 A v_k
+            if (!rc) rc = apply_factors(w, vn);                         // v_{k+1} = M^-1 A v_k
             if (rc) return rc;
             for (int i = 0; i <= k; ++i) {
                 double h = 0;
@@ -220,8 +163,7 @@ int mpf_solve_gmres_ir(mpf_ctx *c, const double *d_A, int64_t lda, const double 
             g[k + 1] = -sn[k] * g[k];
             g[k] = cs[k] * g[k];
             st.inner_iterations++;
-            if (c->gmres_budget_ms > 0 &&
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count() > c->gmres_budget_ms) { out_of_time = true; st.budget_expired = 1; }
+            if (c->gmres_budget_ms > 0 && ms_since(t_start) > c->gmres_budget_ms) { out_of_time = true; st.budget_expired = 1; }
             if (std::fabs(g[k + 1]) <= inner_tol * beta || hn == 0 || out_of_time) { ++k; break; }
         }
         for (int i = k - 1; i >= 0; --i) {                               // back substitution
