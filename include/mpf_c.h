@@ -99,7 +99,8 @@ int mpf_get_stats(mpf_ctx *ctx, mpf_stats *out);
  * "superpanel_fp16", see csrc/mpf_internal.h MpfTuning for the list); afterwards only these calls change them, so contexts
  * on different host threads are independent.  Names: safe_pivots, chain_pipeline, chain_pipeline_below, fp16_work32,
  * superpanel_fp16, superpanel_fp64, no_lookahead, verbose, timeline, hp_spin_limit, hp_gate_ticks, hp_acq_fence, hgemm_pad,
- * hgemm_split_pad, hgemm_big, hgemm_big_tile, dgemm_dma, generic_fused, pivot_fp64, fp64_rowmajor, fp64_rowmajor_min_n, dist_instalments, dist_instalment_min_bytes, lazy_gather, dpanel_fused_form, trsm_laswp_fused.  mpf_option_name enumerates them (returns the count). */
+ * hgemm_split_pad, hgemm_big, hgemm_big_tile, dgemm_dma, generic_fused, pivot_fp64, fp64_rowmajor, fp64_rowmajor_min_n, dist_instalments, dist_instalment_min_bytes, lazy_gather, dpanel_fused_form, trsm_laswp_fused,
+ * gmres_group_tiles (tiles of 32 columns mpf_solve_gmres_ir_block takes together; 0 = automatic; same bits).  mpf_option_name enumerates them (returns the count). */
 /* Rows of the tallest panel the LDS-resident pivot kernel takes -- all its workgroups must be resident at once -- beside `waiters`
  * workgroups of kernels that wait for its progress (0: alone; a negative value -w: beside the pipelined chain's gated interchange
  * kernel on a panel of w columns).  Derived from the kernels' LDS / register footprints and the occupancy API (csrc/fp16_panel.hip):
@@ -376,6 +377,29 @@ int mpf_getrs(mpf_ctx *ctx, int32_t trans, const double *d_LU, int64_t ldlu, con
 int mpf_solve_ir_block(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu,
                        const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X,
                        int64_t ldx, int32_t max_iter, double tol, mpf_ir_stats *stats);
+
+/* GMRES-IR for all nrhs columns together, op(A) X = B with op(A) = A (trans = 0) or A^T (trans = 1): mpf_solve_gmres_ir's method on the
+ * tiles of the blocked solve, for factors on which classical refinement does not contract.  Per column, with M^-1 = getrs on the factors:
+ *   nb2 = ||b||_2 (0 reads 1); x = M^-1 b; outer step 0, 1, ...: r = b - op(A) x in fp64, rel = ||r||_2 / nb2, history[outer] = rel;
+ *   stop converged at rel <= tol, stop not converged at max_outer steps or on a NaN; z = M^-1 r, beta = ||z||_2 (0 or NaN: stop),
+ *   v_0 = z / beta, inner tolerance max(1e-14, min(1e-2, 0.1 tol / rel)); inner step k < restart: w = M^-1 op(A) v_k, orthogonalised
+ *   against v_0 .. v_k by CLASSICAL Gram-Schmidt applied TWICE (h = V^T w, w -= V h, h' = V^T w, w -= V h', H[0..k, k] = h + h',
+ *   H[k+1, k] = ||w||_2), Givens rotations on the host as mpf_solve_gmres_ir; the inner loop ends when the rotated residual is at
+ *   most inner tolerance x beta or ||w|| = 0; then x += V y.
+ * restart and max_outer are clamped as mpf_solve_gmres_ir clamps them (restart < 1: 30, at most 100; max_outer 1 .. 31).
+ * The columns of a group (option gmres_group_tiles) take every outer and every inner step together -- one pass over A and one over
+ * the factors per product for the whole group, one orthogonalisation of three sweeps over the basis and ONE host read-back per inner
+ * step whatever k is; a column whose inner loop has ended is frozen until the group's longest one ends.  Every sum has one fixed
+ * order and no column reads another: X[:, j] and its stats (but ms_total) have the same bits whatever the other columns, nrhs, j's
+ * position or the group width, and two calls return the same bits.  They are NOT the bits of mpf_solve_gmres_ir, which
+ * orthogonalises by modified Gram-Schmidt and sums in another order (as mpf_solve_ir_block's are not those of the per-column solves).
+ * d_B is preserved; rows N .. ldx-1 of d_X are not touched.  stats: nrhs host entries or NULL; budget_expired stays 0 (there is no
+ * wall-clock limit: a column's bits would depend on timing); ms_total is the wall time of the whole call, the same for every column.
+ * Returns 0 when every column converged, 1 when some column did not (the stats say which), < 0 on error.  nrhs = 0: returns 0, no
+ * work.  Synchronises; -4 as the other solves. */
+int mpf_solve_gmres_ir_block(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu,
+                             const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                             int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *stats /* nrhs host entries or NULL */);
 
 /* ---- error bounds for solves (build extension; LAPACK dgerfs on the tiles of the blocked solve) -----------------------------------
  * Refines a solution of op(A) X = B in place and returns, per column, the componentwise backward error berr and a bound ferr on

@@ -33,7 +33,7 @@ C_ABI_SYMBOLS = [
     "mpf_solve_gmres_ir", "mpf_trim", "mpf_dist_set_p2p",
     "mpf_solve_ir_trans", "mpf_lange", "mpf_geequ", "mpf_gecon", "mpf_gesvx",
     "mpf_getrs", "mpf_solve_ir_block", "mpf_gerfs", "mpf_gesvx_block",
-    "mpf_dgetf2_piv",
+    "mpf_dgetf2_piv", "mpf_solve_gmres_ir_block",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -177,6 +177,7 @@ def load_library(probe=False):
     L.mpf_gesvx.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, vp, i32, i32, i32, dbl, i32, dbl, vp, vp, C.POINTER(MpfGesvxStats)]
     L.mpf_getrs.argtypes = [vp, i32, vp, i64, vp, i64, i32, vp, i64]
     L.mpf_solve_ir_block.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, dbl, C.POINTER(MpfIrStats)]
+    L.mpf_solve_gmres_ir_block.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, i32, dbl, C.POINTER(MpfGmresStats)]
     L.mpf_gerfs.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, C.POINTER(dbl), C.POINTER(dbl),
                             C.POINTER(MpfGerfsStats)]
     L.mpf_gesvx_block.argtypes = [vp, vp, i64, i64, i32, vp, vp, i32, vp, i64, vp, i64, i32, i32, i32, dbl, i32, dbl, i32, vp, vp,
@@ -736,6 +737,21 @@ class MPFContext:
         rc = self.L.mpf_solve_ir_block(self.h, int(bool(trans)), _ptr(A), _colmajor_ld(A), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n,
                                        nrhs, _ptr(B), ldb, _ptr(X), ldx, max_iter, tol, st)
         self._check(rc, "mpf_solve_ir_block")
+        return X, list(st)[:nrhs]
+
+    def solve_gmres_ir_block(self, A, LU, ipiv, B, trans=False, max_outer=10, restart=30, tol=1e-12):
+        """mpf_solve_gmres_ir_block: GMRES-IR on all columns of B together, op(A) = A or A^T (trans).  Returns (X, list of per-column
+        MpfGmresStats); X is a vector when B is.  A column that did not converge does not raise: its stats say so."""
+        self._bind()
+        n = A.shape[0]
+        vec = B.dim() == 1
+        _, nrhs, ldb = self._rhs(B)
+        X = self.torch.empty(n, dtype=self.torch.float64, device=self.device) if vec else self.colmajor(n, nrhs)
+        ldx = n if vec else _colmajor_ld(X)
+        st = (MpfGmresStats * max(nrhs, 1))()
+        rc = self.L.mpf_solve_gmres_ir_block(self.h, int(bool(trans)), _ptr(A), _colmajor_ld(A), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n,
+                                             nrhs, _ptr(B), ldb, _ptr(X), ldx, max_outer, restart, tol, st)
+        self._check(rc, "mpf_solve_gmres_ir_block")
         return X, list(st)[:nrhs]
 
     # ---- error bounds for solves (include/mpf_c.h: mpf_gerfs) -------------------------------------------------------------------

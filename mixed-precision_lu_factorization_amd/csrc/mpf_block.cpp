@@ -2,11 +2,14 @@
 //   mpf_getrs            B := A^-1 B or A^-T B with the factors of mpf_factor_dev
 //   mpf_solve_ir_block   fp64 refinement of all columns together, per-column rules and stats of mpf_solve_ir_nrhs / _trans
 //   mpf_gerfs            LAPACK dgerfs: refinement by the componentwise backward error, berr and the forward bound ferr per column
-// The bodies of the last two are cores (blk_refine_core, blk_bounds_core) that take optional scale vectors for the factors of an
+//   mpf_solve_gmres_ir_block   GMRES-IR (mpf_solve_gmres_ir's method) on all columns of a group in lock-step, op(A) = A or A^T
+// The bodies of the second and third are cores (blk_refine_core, blk_bounds_core) that take optional scale vectors for the factors of an
 // equilibrated copy Dr A Dc: mpf_gesvx_block (mpf_expert.cpp) calls them with its scales, the public functions with none.
 // The right-hand sides go through the device in groups of at most GROUP_TILES tiles of BLK_T columns (solve_block.hip); every
 // triangular step and every residual is one pass over the factor block / over A for the whole group.
 #include "solve_common.h"
+#include <algorithm>
+#include <cstring>
 
 namespace {
 constexpr int GROUP_TILES = 16;   // 512 columns per group: six N x 512 tile sets of scratch at most (mpf_gerfs; 805 MB at N = 32768)
@@ -250,6 +253,149 @@ int blk_bounds_core(mpf_ctx *c, bool tr, const double *d_A, int64_t lda, const d
     return 0;
 }
 
+// The body of mpf_solve_gmres_ir_block (mpf_internal.h).  Per column the rules are GmresCol's (solve_rules.h); the columns of a group
+// take every outer step and every inner step together: one launch_blk_residual and one tile_getrs per product, one orthogonalisation
+// (launch_gmres_ortho) and ONE read-back -- h, h', ||w||^2 of every column -- per inner step.  A column whose inner loop has ended
+// waits (live = 0: the kernels leave its basis and its w alone) until the group's longest one ends, then every column applies its own
+// x += V y.  Tile sets: B, X, R (the residual, then in place M^-1 of it: z and w), two of tile_getrs's scratch, and one that stays
+// zero (the "b" of the product -op(A) v_k); the basis is restart + 1 more in c->krylov.
+int blk_gmres_core(mpf_ctx *c, bool tr, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
+                   const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_outer, int32_t restart, double tol,
+                   mpf_gmres_stats *st) {
+    const int m = restart, WORK = 6;
+    const int64_t ldt = (N + 255) / 256 * 256;
+    int gt = c->tune.gmres_group_tiles;
+    if (gt <= 0) {   // automatic: the widest group whose basis and working sets fit in 2 GiB
+        const int64_t per_tile = (int64_t)(m + 1 + WORK) * ldt * BLK_T * (int64_t)sizeof(double);
+        gt = (int)std::max<int64_t>(1, std::min<int64_t>(GROUP_TILES, (2ll << 30) / per_tile));
+    }
+    gt = std::min(gt, GROUP_TILES);
+    int rc;
+    // option timeline: event pairs around the factor solves (0), the residuals (1) and the orthogonalisation (2) of the inner steps
+    const bool tl = c->tune.timeline != 0;
+    EvPool pool(c);
+    struct Pair { hipEvent_t a, b; int what; };
+    std::vector<Pair> pairs;
+    auto timed = [&](int what, int r2) {   // closes the pair opened by `open`
+        if (tl) { pairs.back().what = what; hipEventRecord(pairs.back().b, c->stream); }
+        return r2;
+    };
+    auto open = [&]() { if (tl) { pairs.push_back({pool.get(), pool.get(), 0}); hipEventRecord(pairs.back().a, c->stream); } };
+    double inner_wall_ms = 0;
+    long inner_steps = 0;
+    for (int32_t j0 = 0; j0 < nrhs; j0 += gt * BLK_T) {
+        const int64_t ncols = std::min<int64_t>(nrhs - j0, (int64_t)gt * BLK_T);
+        Group g;
+        rc = group_tiles(c, N, (int)((ncols + BLK_T - 1) / BLK_T), WORK, g);
+        if (rc) return rc;
+        const int64_t tc = (int64_t)BLK_T * g.ntiles, vs = g.ldt * tc;
+        double *Bt = g.t(0), *Xt = g.t(1), *R = g.t(2), *S1 = g.t(3), *S2 = g.t(4), *Zero = g.t(5);
+        MPF_HIP_TRY(c, c->krylov.grow((int64_t)(m + 1) * vs));
+        MPF_HIP_TRY(c, c->blk_part.grow(tc));   // (the column norms' output)
+        MPF_HIP_TRY(c, c->gm_part.grow((int64_t)gmres_ortho_chunks(g.ldt) * std::max(m, 4) * tc));
+        MPF_HIP_TRY(c, c->gm_out.grow((2 * (int64_t)m + 1) * tc));
+        MPF_HIP_TRY(c, c->gm_ctl.grow(((int64_t)m + 2) * tc));
+        double *V = c->krylov;
+        MPF_HIP_TRY(c, hipMemsetAsync(V, 0, (size_t)((int64_t)(m + 1) * vs) * sizeof(double), c->stream));
+        // what the host sends: per step [scale (tc doubles) | live (tc ints)], per outer step [y (m x tc doubles) | counts (tc ints)]
+        std::vector<double> ctl((size_t)((m + 1) * tc), 0.0), out((size_t)((2 * m + 1) * tc));
+        const double *d_scale = c->gm_ctl, *d_y = c->gm_ctl;
+        const int *d_live = (const int *)(c->gm_ctl + tc), *d_cnt = (const int *)(c->gm_ctl + (int64_t)m * tc);
+        auto send_step = [&](const std::vector<int> &live) {   // (the next read-back synchronises before `ctl` changes again)
+            std::memcpy(ctl.data() + tc, live.data(), (size_t)tc * sizeof(int));
+            MPF_HIP_TRY(c, hipMemcpyAsync(c->gm_ctl, ctl.data(), (size_t)(tc + (tc + 1) / 2) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            return 0;
+        };
+        rc = launch_blk_load(c, d_B + (int64_t)j0 * ldb, ldb, nullptr, N, ncols, Bt, g.ldt, g.ntiles);
+        std::vector<double> nb2, nr;
+        if (!rc) rc = col_norms(c, Bt, g, N, ncols, nb2);
+        if (!rc) rc = tile_getrs(c, d_LU, ldlu, N, tr, Bt, Xt, S1, S2, g);   // x0
+        if (rc) return rc;
+        for (auto &v : nb2) if (v == 0) v = 1;
+        std::vector<GmresCol> col((size_t)ncols, GmresCol(m));
+        std::vector<int> active((size_t)ncols, 1), live((size_t)tc, 0), cnt((size_t)tc, 0);
+        for (int outer = 0;; ++outer) {
+            rc = launch_blk_residual(c, d_A, lda, N, tr, Xt, Bt, R, g.ldt, g.ntiles);
+            if (!rc) rc = col_norms(c, R, g, N, ncols, nr);
+            if (rc) return rc;
+            bool any = false;
+            for (int64_t j = 0; j < ncols; ++j) {
+                if (active[(size_t)j]) active[(size_t)j] = col[(size_t)j].outer_check(st[(size_t)(j0 + j)], outer, nr[(size_t)j] / nb2[(size_t)j], max_outer, tol);
+                any = any || active[(size_t)j];
+            }
+            if (!any) break;
+            rc = tile_getrs(c, d_LU, ldlu, N, tr, R, R, S1, S2, g);   // z = M^-1 r
+            if (!rc) rc = col_norms(c, R, g, N, ncols, nr);           // beta
+            if (rc) return rc;
+            any = false;
+            for (int64_t j = 0; j < ncols; ++j) {
+                if (active[(size_t)j]) active[(size_t)j] = col[(size_t)j].begin_inner(nr[(size_t)j], st[(size_t)(j0 + j)].rel_residual, tol);
+                live[(size_t)j] = active[(size_t)j];
+                cnt[(size_t)j] = 0;
+                ctl[(size_t)j] = active[(size_t)j] ? 1.0 / nr[(size_t)j] : 0.0;
+                any = any || active[(size_t)j];
+            }
+            if (!any) break;
+            rc = send_step(live);
+            if (!rc) rc = launch_gmres_append(c, R, d_scale, V, g.ldt, N, g.ntiles);   // v_0 = z / beta
+            if (rc) return rc;
+            const auto t_inner = std::chrono::steady_clock::now();
+            for (int k = 0; any; ++k) {
+                const int64_t len = (int64_t)(k + 1) * tc;
+                open();
+                rc = timed(1, launch_blk_residual(c, d_A, lda, N, tr, V + (int64_t)k * vs, Zero, R, g.ldt, g.ntiles));   // -op(A) v_k
+                open();
+                if (!rc) rc = timed(0, tile_getrs(c, d_LU, ldlu, N, tr, R, R, S1, S2, g));                              // -M^-1 op(A) v_k
+                open();
+                if (!rc) rc = timed(2, launch_gmres_ortho(c, V, vs, k + 1, R, g.ldt, N, g.ntiles, d_live, c->gm_part, c->gm_out));
+                if (rc) return rc;
+                MPF_HIP_TRY(c, hipMemcpyAsync(out.data(), c->gm_out, (size_t)(2 * len + tc) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+                MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+                ++inner_steps;
+                any = false;
+                for (int64_t j = 0; j < ncols; ++j) {
+                    ctl[(size_t)j] = 0.0;
+                    if (!live[(size_t)j]) continue;
+                    double *h = out.data() + j;
+                    for (int i = 0; i <= k; ++i) h[(size_t)i * tc] += h[(size_t)(len + i * tc)];   // H[0 .. k, k] = h + h'
+                    const double hn = std::sqrt(out[(size_t)(2 * len + j)]);
+                    live[(size_t)j] = col[(size_t)j].inner_step(st[(size_t)(j0 + j)], h, (size_t)tc, hn);
+                    if (live[(size_t)j] && hn > 0) ctl[(size_t)j] = 1.0 / hn;
+                    any = any || live[(size_t)j];
+                }
+                if (!any) break;
+                rc = send_step(live);
+                if (!rc) rc = launch_gmres_append(c, R, d_scale, V + (int64_t)(k + 1) * vs, g.ldt, N, g.ntiles);   // v_{k+1} = w / hn
+                if (rc) return rc;
+            }
+            inner_wall_ms += ms_since(t_inner);
+            std::fill(ctl.begin(), ctl.end(), 0.0);
+            for (int64_t j = 0; j < ncols; ++j) {   // every column that ran this outer step: its own y, its own count
+                if (!active[(size_t)j]) continue;
+                GmresCol &cj = col[(size_t)j];
+                cj.solve_y();
+                cnt[(size_t)j] = cj.k;
+                for (int i = 0; i < cj.k; ++i) ctl[(size_t)(i * tc + j)] = cj.y[(size_t)i];
+            }
+            std::memcpy(ctl.data() + (int64_t)m * tc, cnt.data(), (size_t)tc * sizeof(int));
+            MPF_HIP_TRY(c, hipMemcpyAsync(c->gm_ctl, ctl.data(), (size_t)(m * tc + (tc + 1) / 2) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            rc = launch_gmres_xupdate(c, V, vs, d_y, d_cnt, Xt, g.ldt, N, g.ntiles);
+            if (rc) return rc;
+            MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));   // `ctl` is a host vector reused by the next step
+            std::fill(ctl.begin(), ctl.end(), 0.0);
+        }
+        rc = launch_blk_store(c, Xt, g.ldt, nullptr, N, ncols, d_X + (int64_t)j0 * ldx, ldx);
+        if (rc) return rc;
+    }
+    if (tl) {   // factor solves, residuals, orthogonalisation (device time between the events), the inner loops' wall time, their steps
+        MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        double acc[3] = {0, 0, 0};
+        for (auto &p : pairs) { float ms = 0; if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) acc[p.what] += ms; }
+        fprintf(stderr, "GMRES_TL %.4f %.4f %.4f %.4f %ld\n", acc[0], acc[1], acc[2], inner_wall_ms, inner_steps);
+    }
+    return 0;
+}
+
 extern "C" {
 
 int mpf_getrs(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv, int64_t N, int32_t nrhs, double *d_B,
@@ -319,6 +465,31 @@ int mpf_gerfs(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const d
     for (auto &s : st) s.ms_total = ms;
     if (stats) std::copy(st.begin(), st.end(), stats);
     return solve_check_waits(c);
+}
+
+int mpf_solve_gmres_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu,
+                             const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                             int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *stats) {
+    if (!c) return -1;
+    if (check_args(c, "solve_gmres_ir_block", trans, N, nrhs, ldlu, ldb)) return -1;
+    if (lda < N || ldx < N) { c->err = "solve_gmres_ir_block: leading dimension < N"; return -1; }
+    if (nrhs == 0) return 0;
+    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X) { c->err = "solve_gmres_ir_block: null pointer"; return -1; }
+    gmres_clamp(max_outer, restart);
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
+    if (rc) return rc;
+    std::vector<mpf_gmres_stats> st((size_t)nrhs);
+    rc = blk_gmres_core(c, trans == 1, d_A, lda, d_LU, ldlu, N, nrhs, d_B, ldb, d_X, ldx, max_outer, restart, tol, st.data());
+    if (rc) return rc;
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const double ms = ms_since(t0);
+    bool all = true;
+    for (auto &s2 : st) { s2.ms_total = ms; all = all && s2.converged; }
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    rc = solve_check_waits(c);
+    return rc ? rc : (all ? 0 : 1);
 }
 
 } // extern "C"

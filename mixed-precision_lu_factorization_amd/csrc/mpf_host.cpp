@@ -71,6 +71,7 @@ const OptDesc kOpts[] = {
     OPT_I(host_late_q_pct, "MPF_HOST_LATE_Q_PCT", 1, 1000),
     OPT_L(host_sink_min_n, "MPF_HOST_SINK_MIN_N", 0, 1ll << 40),
     OPT_I(dist_solve_p2p, "MPF_DIST_SOLVE_P2P", 0, 1),
+    OPT_I(gmres_group_tiles, "MPF_GMRES_GROUP_TILES", 0, 16),
 #ifdef MPF_PROBE
     OPT_I(hp_stamp, "MPF_HP_STAMP", 0, 1),
     OPT_I(hp_r256_upto, "MPF_HP_R256_UPTO", 0, 1 << 30),

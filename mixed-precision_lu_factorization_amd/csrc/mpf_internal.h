@@ -116,6 +116,9 @@ struct MpfTuning {
                                          // panel PAIR (K = 2 nb) while the update is the longer side (factor_rm_pairs; same bits)
     long long fp64_pair_min_n = 16384;   // MPF_FP64_PAIR_MIN_N: ... that is, while the trailing matrix of the pair's first panel is larger than this (measured at
                                          // N = 32768: 9216 .. 16384 within 1.5 ms of each other, profiles/pair_ab.log; below, the pair's two chains no longer fit under its update)
+    int gmres_group_tiles = 0;           // MPF_GMRES_GROUP_TILES: 32-column tiles mpf_solve_gmres_ir_block takes through the device together: n >= 1 exactly n
+                                         // (at most 16), 0 = automatic -- the most (<= 16, >= 1) whose restart + 1 basis sets and six working sets fit in
+                                         // 2 GiB.  The results do not depend on it (every column's arithmetic is its own)
 #ifdef MPF_PROBE                         // libmpf_probe.so only (tools/): measured-slower variants and diagnostics
     int hp_stamp = 0;                    // MPF_HP_STAMP=1: cycle-stamped build of the pivot kernel
     int hp_r256_upto = 1 << 30;          // MPF_HP_R256_UPTO: panels above that many rows use 128-row workgroups
@@ -201,6 +204,9 @@ struct mpf_ctx {
     // error bounds (mpf_gerfs, solve_bounds.hip): results + partials of the per-column reductions, per-column arguments of the dlacn2 steps
     Buf<double> blk_red;
     Buf<int> blk_colarg;
+    // blocked GMRES-IR (blk_gmres_core, solve_gmres.hip; its basis lives in `krylov`): partials of the orthogonalisation, its results
+    // [h | h' | ||w||^2], and what the host sends per step ([scale | live] per column; [y | counts] per outer step)
+    Buf<double> gm_part, gm_out, gm_ctl;
     // factored 32x32 diagonal tiles of the fp64 panel, parked here until every workgroup of the sub-panel launches has
     // read the UNfactored tile from the matrix (dpanel.hip); one tile per 32 panel columns, grown on demand
     Buf<double> dtiles;
@@ -443,6 +449,20 @@ int blk_refine_core(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, cons
 int blk_bounds_core(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
                     const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *ferr, double *berr, const double *pre,
                     const double *post, mpf_gerfs_stats *st);
+// solve_gmres.hip: the orthogonalisation (classical Gram-Schmidt twice) and the vector updates of the blocked GMRES-IR; basis slot i at
+// V + i * vs, tiles as above.  launch_gmres_ortho: W = -W orthogonalised against the slots 0 .. ns - 1 on the columns with live[j] != 0,
+// out = [h (ns x tc) | h' (ns x tc) | ||w||^2 (tc)], tc = BLK_T * ntiles; part: gmres_ortho_chunks(ldt) * max(ns, 4) * tc doubles
+int gmres_ortho_chunks(int64_t ldt);
+int launch_gmres_ortho(mpf_ctx *c, const double *V, int64_t vs, int ns, double *W, int64_t ldt, int64_t n, int ntiles, const int *live,
+                       double *part, double *out);
+int launch_gmres_append(mpf_ctx *c, const double *src, const double *scale, double *dst, int64_t ldt, int64_t n, int ntiles);   // dst = src * scale[j] where scale[j] != 0
+int launch_gmres_xupdate(mpf_ctx *c, const double *V, int64_t vs, const double *y, const int *cnt, double *X, int64_t ldt, int64_t n,
+                         int ntiles);   // X[:, j] += sum_{i < cnt[j]} y[i * tc + j] V_i[:, j]
+// mpf_block.cpp: the body of mpf_solve_gmres_ir_block after its argument checks and solve_setup; restart and max_outer clamped
+// (gmres_clamp); `st` holds nrhs zeroed entries; neither synchronises at its end nor sets ms_total.
+int blk_gmres_core(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
+                   const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_outer, int32_t restart, double tol,
+                   mpf_gmres_stats *st);
 
 // ---- host-side helpers shared by the schedules (mpf_host.cpp, mpf_dist.cpp) --------------------------------------------
 struct StreamSwap { // launch_* helpers use c->stream: point it at another stream for a scope

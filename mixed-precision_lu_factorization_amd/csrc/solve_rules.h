@@ -1,10 +1,14 @@
 // The decisions of the solve layer, host arithmetic only (no HIP: a plain C++17 compiler takes this file, tests/solve_rules_driver.cpp
-// does): when refinement stops, dlacn2's state machine, the summary column of a blocked attempt, dgerfs's constants.  Every solve path
-// -- refine_vector (solve_common.h), blk_refine_core, gecon_core, blk_bounds_core, mpf_gesvx_block -- takes them from here.
+// does): when refinement stops, dlacn2's state machine, the summary column of a blocked attempt, dgerfs's constants, GMRES-IR's
+// per-column decisions.  Every solve path -- refine_vector (solve_common.h), blk_refine_core, gecon_core, blk_bounds_core,
+// mpf_gesvx_block, blk_gmres_core -- takes them from here.
 #pragma once
+#include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 #include "../../include/mpf_c.h"
 
 // One refinement step's book-keeping: `rel` = ||r|| / ||b|| after `it` corrections.  Records it, then decides whether another
@@ -68,5 +72,75 @@ struct Lacn2Col {
     void final_stage(double altsum, int64_t N) {
         const double temp = 2.0 * (altsum / (double)(3 * N));
         if (temp > est) est = temp;
+    }
+};
+
+// GMRES-IR's clamps (mpf_solve_gmres_ir's): restart < 1 reads 30, at most 100; max_outer 1 .. 31 (history has 32 entries)
+inline void gmres_clamp(int32_t &max_outer, int32_t &restart) {
+    if (restart < 1) restart = 30;
+    if (restart > 100) restart = 100;
+    if (max_outer < 1) max_outer = 1;
+    if (max_outer > 31) max_outer = 31;
+}
+
+// GMRES-IR for one column as the decisions between its products (mpf_solve_gmres_ir's arithmetic, tests/gmres_block_model.py); the
+// caller forms the products, the orthogonalisation and the norms.  Sequence per outer step: r = b - op(A) x -> outer_check(||r|| / ||b||);
+// z = M^-1 r -> begin_inner(||z||); then, while inner_step returns true: w = M^-1 op(A) v_k orthogonalised against v_0 .. v_k ->
+// inner_step(h, hn); at last solve_y() and x += sum_{i < k} y[i] v_i.
+struct GmresCol {
+    int m = 0;           // restart length
+    int k = 0;           // inner steps taken in this outer step (= basis vectors that enter x)
+    double beta = 0, inner_tol = 0;
+    std::vector<double> H, cs, sn, g, y;   // H[i * m + j]: the Hessenberg matrix, triangular after the rotations
+    explicit GmresCol(int restart = 1) : m(restart), H((size_t)(restart + 1) * restart), cs(restart), sn(restart), g(restart + 1), y(restart) {}
+    // `rel` = ||r|| / ||b|| before outer step `outer`.  Records it; true: an inner loop follows.  False: the column has stopped for good
+    // -- converged at the tolerance, or not (max_outer steps done, or a NaN).
+    bool outer_check(mpf_gmres_stats &st, int outer, double rel, int max_outer, double tol) const {
+        st.rel_residual = rel;
+        st.history[outer] = rel;
+        st.outer_iterations = outer;
+        if (rel <= tol) { st.converged = 1; return false; }
+        return !(outer >= max_outer || !(rel == rel));
+    }
+    // `b` = ||M^-1 r||.  False (b is 0 or a NaN): the column has stopped for good.  Else v_0 = z / b, g = b e_0, and the inner tolerance
+    // reduces the preconditioned residual far enough for this outer step to reach the target.
+    bool begin_inner(double b, double rel, double tol) {
+        k = 0;
+        beta = b;
+        if (b == 0 || !(b == b)) return false;
+        std::fill(g.begin(), g.end(), 0.0);
+        g[0] = b;
+        inner_tol = std::max(1e-14, std::min(1e-2, 0.1 * tol / rel));
+        return true;
+    }
+    // Column k of the Hessenberg matrix: h[i * stride] = v_i . w for i = 0 .. k (both Gram-Schmidt passes added), hn = ||w|| after them.
+    // Applies the earlier rotations, forms the new one, updates g; true: another inner step follows (v_{k+1} = w / hn is needed).
+    bool inner_step(mpf_gmres_stats &st, const double *h, size_t stride, double hn) {
+        for (int i = 0; i <= k; ++i) H[(size_t)i * m + k] = h[(size_t)i * stride];
+        H[(size_t)(k + 1) * m + k] = hn;
+        for (int i = 0; i < k; ++i) {
+            const double t = cs[i] * H[(size_t)i * m + k] + sn[i] * H[(size_t)(i + 1) * m + k];
+            H[(size_t)(i + 1) * m + k] = -sn[i] * H[(size_t)i * m + k] + cs[i] * H[(size_t)(i + 1) * m + k];
+            H[(size_t)i * m + k] = t;
+        }
+        const double a = H[(size_t)k * m + k], b2 = H[(size_t)(k + 1) * m + k], den = std::hypot(a, b2);
+        cs[k] = den > 0 ? a / den : 1.0;
+        sn[k] = den > 0 ? b2 / den : 0.0;
+        H[(size_t)k * m + k] = den;
+        H[(size_t)(k + 1) * m + k] = 0;
+        g[k + 1] = -sn[k] * g[k];
+        g[k] = cs[k] * g[k];
+        st.inner_iterations++;
+        ++k;
+        if (std::fabs(g[k]) <= inner_tol * beta || hn == 0) return false;
+        return k < m;
+    }
+    // back substitution: y[0 .. k)
+    void solve_y() {
+        for (int i = k - 1; i >= 0; --i) {
+            double s2 = g[i];
+            for (int j = i + 1; j < k; ++j) s2 -= H[(size_t)i * m + j] * y[j];
+            y[i] = s2 / H[(size_t)i * m + i];
+        }
     }
 };
