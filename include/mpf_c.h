@@ -48,7 +48,15 @@ typedef struct mpf_opts {
                               the columns left and right of the panel, then the TRSM and the update as they are.  In the fp64 trailing
                               mode IPIV and the factors equal, bit for bit, what the same loop gives through the step operators
                               mpf_dgetf2_piv, mpf_laswp, mpf_dtrsm_llnu, mpf_dgemm_minus.  Also option pivot_fp64 / MPF_PIVOT_FP64=1, which
-                              turns it on for every entry point that factors internally.  Not available in mpf_factor_dist. */
+                              turns it on for every entry point that factors internally.  Not available in mpf_factor_dist.
+                              2: tournament pivoting (the panel of communication-avoiding LU) in fp64 -- the rule of mpf_dgetf2_tp: every
+                              256-row slab of a 32-column sub-panel picks its own 32 best rows by partial pivoting, the winners are merged
+                              eight slabs at a time, the sub-panel is factored without pivoting on the rows that won.  1 + ceil(log8(slabs))
+                              selection launches per 32 columns instead of 33.  Scale-invariant like 1; |l_ij| <= 1 is NOT promised (a
+                              panel of at most 256 rows gives exactly the pivots and bits of 1).  The same loop as 1 with mpf_dgetf2_tp as
+                              the panel, the same bit statement against the step operators (mpf_dgetf2_tp, mpf_laswp, mpf_dtrsm_llnu,
+                              mpf_dgemm_minus).  Also option pivot_fp64 = 2 / MPF_PIVOT_FP64=2; an explicit pivot_search of 1 or 2 wins over
+                              the option.  Not available in mpf_factor_dist. */
 } mpf_opts;
 
 typedef struct mpf_stats {
@@ -81,8 +89,9 @@ typedef struct mpf_stats {
                                    what was left of the way home after the last kernel) */
     int32_t host_late_segments; /* mpf_factor_host: column segments of the matrix that went UP while the factorization had started on the
                                    first part (0: the whole matrix first, as MPF.cu:82; ms_h2d is then the whole upload, otherwise the first part's) */
-    int32_t pivot_search;       /* the pivot rule that ran: 0 fp16 image (the reference's), 1 fp64 partial pivoting -- then lookahead = 0,
-                                   superpanel = 1, ms_hpanel = 0 and ms_dpanel is the pivoting panel (event_timers = 2 for the phase timers) */
+    int32_t pivot_search;       /* the pivot rule that ran: 0 fp16 image (the reference's), 1 fp64 partial pivoting, 2 fp64 tournament
+                                   pivoting -- for 1 and 2 lookahead = 0, superpanel = 1, ms_hpanel = 0 and ms_dpanel is the pivoting panel
+                                   (event_timers = 2 for the phase timers) */
 } mpf_stats;
 
 /* ---- lifetime -------------------------------------------------------------------------- */
@@ -99,7 +108,7 @@ int mpf_get_stats(mpf_ctx *ctx, mpf_stats *out);
  * "superpanel_fp16", see csrc/mpf_internal.h MpfTuning for the list); afterwards only these calls change them, so contexts
  * on different host threads are independent.  Names: safe_pivots, chain_pipeline, chain_pipeline_below, fp16_work32,
  * superpanel_fp16, superpanel_fp64, no_lookahead, verbose, timeline, hp_spin_limit, hp_gate_ticks, hp_acq_fence, hgemm_pad,
- * hgemm_split_pad, hgemm_big, hgemm_big_tile, dgemm_dma, generic_fused, pivot_fp64, fp64_rowmajor, fp64_rowmajor_min_n, dist_instalments, dist_instalment_min_bytes, lazy_gather, dpanel_fused_form, trsm_laswp_fused,
+ * hgemm_split_pad, hgemm_big, hgemm_big_tile, dgemm_dma, generic_fused, pivot_fp64 (0 .. 2: the pivot_search every driver that factors internally uses), fp64_rowmajor, fp64_rowmajor_min_n, dist_instalments, dist_instalment_min_bytes, lazy_gather, dpanel_fused_form, trsm_laswp_fused,
  * gmres_group_tiles (tiles of 32 columns mpf_solve_gmres_ir_block takes together; 0 = automatic; same bits).  mpf_option_name enumerates them (returns the count). */
 /* Rows of the tallest panel the LDS-resident pivot kernel takes -- all its workgroups must be resident at once -- beside `waiters`
  * workgroups of kernels that wait for its progress (0: alone; a negative value -w: beside the pipelined chain's gated interchange
@@ -183,6 +192,34 @@ int mpf_dgetf2_npv(mpf_ctx *ctx, double *d_P, int64_t ld, int32_t rows, int32_t 
  * spinning, no bounded waits, no LDS-residency or co-residency requirement. */
 int mpf_dgetf2_piv(mpf_ctx *ctx, double *d_P, int64_t ld, int32_t rows, int32_t cols, int32_t fused,
                    int32_t ipiv_offset, int32_t *d_ipiv, int32_t *info /* host, optional */);
+/* The same panel with TOURNAMENT pivoting (build extension; the panel of CALU: Grigori, Demmel, Xiang): the same arguments and
+ * limits as mpf_dgetf2_piv.  The rule is this project's own contract:
+ * The panel goes by sub-panels of 32 columns.  At the sub-panel that starts at panel column j0, of width w = min(32, kmax - j0),
+ * kmax = min(rows, cols), columns j0 .. j0+w-1 have received the updates of all earlier sub-panels and the active rows are j0 .. rows-1.
+ * select(S), on a stack S of m <= 256 rows x w columns, is dgetf2's pivot choice on a private copy; it returns an ordered list of
+ *   min(m, w) rows of S.  At step s = 0, 1, ... the row not yet chosen with the largest |x_s| is taken (a NaN counts as 0;
+ *   comparison is a strict >, so the smallest position wins a tie; if every key is 0 that is the smallest position not yet
+ *   chosen), and it changes places with the row at position s -- positions are the private copy's CURRENT ones, as in dgetf2, so
+ *   the row a pivot displaced stands where that pivot was, and an all-zero column keeps position s.  Then every row not chosen
+ *   computes m = x_s / pivot_s and x_c <- x_c - m u_c for c = s+1 .. w-1, product and difference rounded separately -- ALWAYS
+ *   unfused, so the pivots do not depend on `fused`.
+ * Tournament: level 0 groups the active rows by 256 consecutive rows counted from j0 (group g = rows j0 + 256 g ..) and runs select
+ *   on each group.  Level l >= 1 stacks the lists of up to 8 consecutive groups (in group order, each list in its ranking order; the
+ *   rows' values AS THEY WERE ON ENTRY to the sub-panel, not the eliminated ones) into <= 256 rows and runs select again, until one
+ *   list is left: the winners q_0 .. q_{w-1}.  With one group at level 0 (at most 256 active rows) this is LAPACK's partial pivoting.
+ * Interchanges: for s = 0 .. w-1, with p the row at which original row q_s stands after the interchanges 0 .. s-1,
+ *   d_ipiv[j0+s] = p + 1 + ipiv_offset, and rows j0+s and p are exchanged in ALL columns of the panel.
+ * Factorization: the sub-panel is then factored WITHOUT pivoting in mpf_dgetf2_npv's arithmetic (contract C3), honouring `fused`:
+ *   the multiplier is a_ij / a_jj, each element is updated once per k in ascending order; the columns right of it follow as in
+ *   mpf_dgetf2_piv.
+ * Bit contract (mpf_dgetf2_piv's): the factored panel equals, bit for bit, mpf_dgetf2_npv applied to the panel with its rows
+ * pre-permuted by the returned pivots.  info: the first zero diagonal entry the no-pivot factorization met, 1-based, or 0.
+ * Consequences: the pivots of A 2^k are those of A; where rows - j0 <= 256 at every sub-panel (e.g. rows <= 256) pivots and bits are
+ * mpf_dgetf2_piv's; |l_ij| <= 1 is NOT promised (growth as in every communication-avoiding LU: in practice as stable as partial pivoting).
+ * Launches per sub-panel: 1 + ceil(log8(ceil((rows - j0) / 256))) selections (at most 4 up to 1 M rows), then the interchange, the
+ * factorization, the U row-block and the update -- all ordinary launches, no kernel waits for another workgroup (csrc/dpivot.hip). */
+int mpf_dgetf2_tp(mpf_ctx *ctx, double *d_P, int64_t ld, int32_t rows, int32_t cols, int32_t fused,
+                  int32_t ipiv_offset, int32_t *d_ipiv, int32_t *info /* host, optional */);
 /* cublasDtrsm(LEFT, LOWER, N, UNIT, m, n, 1.0, L, ldl, B, ldb), call site MPF.cu:215-225. */
 int mpf_dtrsm_llnu(mpf_ctx *ctx, int32_t m, int64_t n, const double *d_L, int64_t ldl, double *d_B,
                    int64_t ldb);
@@ -500,7 +537,7 @@ int mpf_rccl_bcast_probe(mpf_ctx *ctx, int64_t bytes, int32_t root, int32_t reps
 int mpf_rccl_selftest(mpf_ctx *ctx); /* one small broadcast + all-reduce on the communicator (every rank calls it) */
 /* The panel loop MPF.cu:100-242 over the block-cyclic layout (look-ahead schedule: the owner of panel k+1 updates that block
  * first, runs its chain and posts the broadcast on a side stream under everybody's update k).  Returns this rank's info.
- * The fp64 pivot search (mpf_opts.pivot_search = 1, option pivot_fp64) is single-GPU only: -1 with a message here. */
+ * The fp64 pivot rules (mpf_opts.pivot_search = 1 or 2, option pivot_fp64) are single-GPU only: -1 with a message here. */
 int mpf_factor_dist(mpf_ctx *ctx, double *d_Aloc, int64_t ldloc, int64_t N, int32_t nb, int32_t *d_ipiv, const mpf_dist *dist,
                     const mpf_opts *opts);
 /* Optional point-to-point transport next to the caller's own broadcast / all-reduce callbacks (with NULL callbacks in mpf_dist the

@@ -33,7 +33,7 @@ C_ABI_SYMBOLS = [
     "mpf_solve_gmres_ir", "mpf_trim", "mpf_dist_set_p2p",
     "mpf_solve_ir_trans", "mpf_lange", "mpf_geequ", "mpf_gecon", "mpf_gesvx",
     "mpf_getrs", "mpf_solve_ir_block", "mpf_gerfs", "mpf_gesvx_block",
-    "mpf_dgetf2_piv", "mpf_solve_gmres_ir_block",
+    "mpf_dgetf2_piv", "mpf_solve_gmres_ir_block", "mpf_dgetf2_tp",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -159,6 +159,7 @@ def load_library(probe=False):
     L.mpf_laswp.argtypes = [vp, vp, i64, i64, i32, i32, vp]
     L.mpf_dgetf2_npv.argtypes = [vp, vp, i64, i32, i32, i32]
     L.mpf_dgetf2_piv.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp, C.POINTER(i32)]
+    L.mpf_dgetf2_tp.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp, C.POINTER(i32)]
     L.mpf_dtrsm_llnu.argtypes = [vp, i32, i64, vp, i64, vp, i64]
     L.mpf_dgemm_minus.argtypes = [vp, i64, i64, i32, vp, i64, vp, i64, vp, i64]
     L.mpf_hgemm_minus.argtypes = [vp, i64, i64, i32, vp, i64, vp, i64, vp, i64, i32]
@@ -371,8 +372,9 @@ class MPFContext:
     def factor(self, A, nb, ipiv=None, trailing=TRAIL_FP64, fused_panel=False, sync_timing=False, verbose=False,
                no_lookahead=False, superpanel=0, pivot_path=0, pivot_search=0):
         """mpf_factor_dev: in-place MPF of the column-major device matrix A (N x N).
-        pivot_search: 0 = the reference's fp16 pre-pivoting, 1 = LAPACK's partial pivoting, searched in fp64 (also context option
-        pivot_fp64, which gesv, gesvx, gesvx_block and factor_host follow).  Returns (ipiv int32 device tensor, info)."""
+        pivot_search: 0 = the reference's fp16 pre-pivoting, 1 = LAPACK's partial pivoting, searched in fp64, 2 = tournament pivoting
+        in fp64 (mpf_dgetf2_tp's rule); also context option pivot_fp64 = 1 or 2, which gesv, gesvx, gesvx_block and factor_host follow.
+        Returns (ipiv int32 device tensor, info)."""
         self._bind()
         t = self.torch
         n = A.shape[0]
@@ -557,6 +559,18 @@ class MPFContext:
         info = C.c_int32(0)
         self._check(self.L.mpf_dgetf2_piv(self.h, _ptr(P), _colmajor_ld(P), rows, cols, int(fused), int(ipiv_offset), _ptr(ipiv),
                                           C.byref(info)), "dgetf2_piv")
+        return ipiv, info.value
+
+    def dgetf2_tp(self, P, fused=False, ipiv_offset=0):
+        """mpf_dgetf2_tp: the same panel with tournament pivoting (the rule in include/mpf_c.h), in place on the column-major panel P.
+        Returns (ipiv int32[min(rows, cols)] = pivot row + 1 + ipiv_offset, info = first zero diagonal entry or 0)."""
+        self._bind()
+        t = self.torch
+        rows, cols = P.shape
+        ipiv = t.zeros(min(rows, cols), dtype=t.int32, device=self.device)
+        info = C.c_int32(0)
+        self._check(self.L.mpf_dgetf2_tp(self.h, _ptr(P), _colmajor_ld(P), rows, cols, int(fused), int(ipiv_offset), _ptr(ipiv),
+                                         C.byref(info)), "dgetf2_tp")
         return ipiv, info.value
 
     def dtrsm_llnu(self, Lm, B):

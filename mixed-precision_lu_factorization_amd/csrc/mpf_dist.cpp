@@ -334,7 +334,7 @@ int mpf_factor_dist(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_
     if (opts) o = *opts;
     if (o.trailing < MPF_TRAIL_FP64 || o.trailing > MPF_TRAIL_FP16X3) { c->err = "mpf_factor_dist: unknown trailing mode"; return -1; }
     if (o.pivot_search != 0 || c->tune.pivot_fp64) {
-        c->err = "mpf_factor_dist: the fp64 pivot search (mpf_opts.pivot_search = 1, option pivot_fp64) is single-GPU only; use mpf_factor_dev";
+        c->err = "mpf_factor_dist: the fp64 pivot rules (mpf_opts.pivot_search = 1 or 2, option pivot_fp64) are single-GPU only; use mpf_factor_dev";
         return -1;
     }
     // fp16 modes: the full-slab pivot kernel (a CU per workgroup) except where a panel leaves fewer than 72 CUs free -- the gated

@@ -25,7 +25,7 @@ struct OptDesc { const char *name, *env; size_t off; bool wide; long long lo, hi
 #define OPT_L(field, env, lo, hi) {#field, env, offsetof(MpfTuning, field), true, lo, hi}
 const OptDesc kOpts[] = {
     OPT_I(safe_pivots, "MPF_SAFE_PIVOTS", 0, 1),
-    OPT_I(pivot_fp64, "MPF_PIVOT_FP64", 0, 1),
+    OPT_I(pivot_fp64, "MPF_PIVOT_FP64", 0, 2),
     OPT_I(chain_pipeline, "MPF_CHAIN_PIPELINE", 0, 1),
     OPT_L(chain_pipeline_below, "MPF_CHAIN_PIPELINE_BELOW", 0, 1ll << 40),
     OPT_I(fp16_work32, "MPF_FP16_WORK32", 0, 1),
@@ -307,6 +307,22 @@ int mpf_dgetf2_piv(mpf_ctx *c, double *d_P, int64_t ld, int32_t rows, int32_t co
     *info = v == INT_MAX ? 0 : v;
     return 0;
 }
+int mpf_dgetf2_tp(mpf_ctx *c, double *d_P, int64_t ld, int32_t rows, int32_t cols, int32_t fused, int32_t ipiv_offset,
+                  int32_t *d_ipiv, int32_t *info) {
+    if (!c || !d_P || !d_ipiv) return -1;
+    if (rows < 1 || cols < 1 || cols > 65535) return fail(c, -1, "dgetf2_tp: need rows >= 1 and 1 <= cols <= 65535");
+    if (ld < rows) return fail(c, -1, "dgetf2_tp: ld < rows");
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const int imax = INT_MAX;
+    MPF_HIP_TRY(c, hipMemcpyAsync(&c->ws->info, &imax, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    const int rc = launch_dgetf2_tp(c, d_P, ld, rows, cols, fused, 0, ipiv_offset, d_ipiv);
+    if (rc || !info) return rc;
+    int v = 0;
+    MPF_HIP_TRY(c, hipMemcpyAsync(&v, &c->ws->info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *info = v == INT_MAX ? 0 : v;
+    return 0;
+}
 int mpf_dtrsm_llnu(mpf_ctx *c, int32_t m, int64_t n, const double *d_L, int64_t ldl, double *d_B, int64_t ldb) {
     if (!c) return -1;
     if (m > 0 && n > 0 && (ldl < m || ldb < m)) return fail(c, -1, "dtrsm: leading dimension < m");
@@ -466,11 +482,11 @@ static int factor_sync_timed(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
 // are the reference's sequential per-column swaps over ALL N columns (no deferred left-hand side), the TRSM is blocked
 // by 256 rows, K is cut to what the update kernels address.  Same per-element operations in the same order as the
 // tuned schedules: results are bit-identical (tests/test_gpu_generic.py).
-// piv64 (mpf_opts.pivot_search = 1): the pivot kernel, the interchange and the no-pivot panel give way to ONE pivoting fp64 panel
+// piv64 (mpf_opts.pivot_search = 1: partial pivoting, 2: tournament pivoting -- the other panel launcher): the pivot kernel, the interchange and the no-pivot panel give way to ONE pivoting fp64 panel
 // (dpivot.hip, booked under ms_dpanel), which exchanges the panel's own columns itself; the interchange then covers the columns
 // left and right of the panel.  TRSM and update are the same.
 static int factor_generic(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, int32_t *d_ipiv, const mpf_opts &o,
-                          mpf_stats &st, bool force_generic_pivots, bool piv64) {
+                          mpf_stats &st, bool force_generic_pivots, int piv64) {
     EvPool ev(c);
     ev.keep = &st.ms_gemm;
     hipStream_t S = c->stream;
@@ -482,7 +498,9 @@ static int factor_generic(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32
         if (pr <= 1) break;                                  // MPF.cu:104
         double *Ap = d_A + k * lda + k;
         if (piv64) {
-            rc = ev.timed(st.ms_dpanel, S, [&] { return launch_dgetf2_piv(c, Ap, lda, pr, pc, o.fused_panel, (int)k, (int)k, d_ipiv + k); });
+            rc = ev.timed(st.ms_dpanel, S, [&] {
+                return piv64 == 2 ? launch_dgetf2_tp(c, Ap, lda, pr, pc, o.fused_panel, (int)k, (int)k, d_ipiv + k)
+                                  : launch_dgetf2_piv(c, Ap, lda, pr, pc, o.fused_panel, (int)k, (int)k, d_ipiv + k); });
             if (rc) break;
             rc = ev.timed(st.ms_laswp, S, [&] {
                 int e = launch_laswp_seq(c, d_A, lda, k, (int)k, pc, d_ipiv + k, N);
@@ -520,7 +538,7 @@ static int factor_generic(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32
             count_gemm(st, o, n, n, pc);
         }
         st.panels++;
-        if (o.verbose) printf("panel k=%lld rows=%d cols=%d (generic schedule%s)\n", (long long)k, pr, pc, piv64 ? ", fp64 pivot search" : "");
+        if (o.verbose) printf("panel k=%lld rows=%d cols=%d (generic schedule%s)\n", (long long)k, pr, pc, piv64 == 2 ? ", fp64 tournament pivoting" : piv64 ? ", fp64 pivot search" : "");
     }
     hipError_t se = hipStreamSynchronize(S);
     if (!rc && se != hipSuccess) return fail(c, -2, std::string("factorization failed: ") + hipGetErrorString(se));
@@ -1478,8 +1496,10 @@ int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, 
     mpf_opts o{};
     if (opts) o = *opts;
     if (o.trailing < MPF_TRAIL_FP64 || o.trailing > MPF_TRAIL_FP16X3) return fail(c, -1, "mpf_factor: unknown trailing mode");
-    if (o.pivot_search < 0 || o.pivot_search > 1) return fail(c, -1, "mpf_factor: unknown pivot_search (0: fp16 image, 1: fp64 partial pivoting)");
-    const bool piv64 = o.pivot_search == 1 || c->tune.pivot_fp64 != 0;   // fp64 pivot search: the generic schedule's loop in every mode
+    if (o.pivot_search < 0 || o.pivot_search > 2)
+        return fail(c, -1, "mpf_factor: unknown pivot_search (0: fp16 image, 1: fp64 partial pivoting, 2: fp64 tournament pivoting)");
+    // fp64 pivot rules (1 partial, 2 tournament pivoting): the generic schedule's loop in every mode; an explicit rule wins over the option
+    const int piv64 = o.pivot_search != 0 ? o.pivot_search : c->tune.pivot_fp64;
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     // tuned schedules need every panel to fit the LDS pivot kernel (<= 256 columns, all its workgroups resident at once);
     // anything else, and callers that ask for it, get the generic schedule
@@ -1495,10 +1515,10 @@ int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, 
         int e = mpf_ensure_h_images(c, N + HP_MAXCOLS + 64, (int)kimg, sb > 1); if (e) return e;   // + room for the block-row L images
     }
     { const int e = mpf_factor_setup(c, N, nb, (int)((N + nb - 1) / nb), !generic); if (e) return e; }
-    if (piv64) { const int e = dgetf2_piv_reserve(c, (int)N); if (e) return e; }
+    if (piv64) { const int e = piv64 == 2 ? dgetf2_tp_reserve(c, (int)N) : dgetf2_piv_reserve(c, (int)N); if (e) return e; }
     mpf_stats st{};
     st.n = N; st.nb = nb; st.superpanel = sb;
-    st.pivot_search = piv64 ? 1 : 0;
+    st.pivot_search = piv64;
     const bool lookahead = !o.sync_timing && !o.no_lookahead && !c->tune.no_lookahead && c->pstream != nullptr;
     // the row-major working copy of the fp64 mode is allocated BEFORE the clock starts (a context's first call pays hipMalloc
     // of N x N doubles once; ms_total is the factorization)
@@ -1581,7 +1601,7 @@ int mpf_factor_host(mpf_ctx *c, double *A_host, int64_t N, int32_t nb, int32_t *
     // the call recovers from by itself: a pivot kernel whose workgroups were not all resident (-4) -> once more on the generic path.
     const bool want_sink = c->tune.host_sink && N >= c->tune.host_sink_min_n && c->pstream != nullptr && !(opts && (opts->sync_timing || opts->no_lookahead)) &&
                            !(opts && opts->trailing != MPF_TRAIL_FP64) && !(opts && opts->pivot_path == 1) &&
-                           !(opts && opts->pivot_search == 1) && !c->tune.pivot_fp64;   // (the generic schedule reports no block rows)
+                           !(opts && opts->pivot_search != 0) && !c->tune.pivot_fp64;   // (the generic schedule reports no block rows)
     bool armed = false;
     if (want_sink) {
         if (c->host_A0.grow((int64_t)((bytes + pbytes + sizeof(double) - 1) / sizeof(double))) != hipSuccess)   // A, then P

@@ -45,7 +45,8 @@ struct MpfWorkspace {
 // on two host threads never share or race on them.
 struct MpfTuning {
     int safe_pivots = 0;                 // MPF_SAFE_PIVOTS=1: generic (never-waiting) pivot path and schedule always
-    int pivot_fp64 = 0;                  // MPF_PIVOT_FP64=1: every factorization searches its pivots in fp64 (mpf_opts.pivot_search = 1; dpivot.hip)
+    int pivot_fp64 = 0;                  // MPF_PIVOT_FP64=1: every factorization searches its pivots in fp64 (mpf_opts.pivot_search = 1; dpivot.hip);
+                                         // 2: by tournament pivoting (mpf_opts.pivot_search = 2; dpivot.hip)
     int chain_pipeline = 1;              // MPF_CHAIN_PIPELINE=0: the fp64 panel waits for the whole pivot kernel
     long long chain_pipeline_below = 10240; // MPF_CHAIN_PIPELINE_BELOW: fp64 mode pipelines the chain only below this trailing size (re-tuned in round 4
                                             // after the pivot kernel got faster: 8192 .. 14336 within 1 ms of each other, 18432 + 3 ms, 0 + 9 ms)
@@ -235,6 +236,8 @@ struct mpf_ctx {
     Buf<unsigned long long> gcand;
     // pivoting fp64 panel, dpivot.hip: per-workgroup candidates with their rows, two launch parities
     Buf<unsigned long long> dpiv;
+    // tournament-pivoting fp64 panel, dpivot.hip: two alternating candidate buffers (32 rows with their indices per group) + the winners
+    Buf<double> dtp;
     // distributed path (mpf_dist.cpp): RCCL communicator (dlopen'ed), two panel message buffers
     void *rccl_comm = nullptr;
     int rccl_rank = 0, rccl_world = 0;
@@ -337,6 +340,9 @@ int launch_dgetf2_npv(mpf_ctx *c, double *P, int64_t ld, int rows, int cols, int
 // up to `rows` rows, so that a factorization allocates once, before its first launch
 int launch_dgetf2_piv(mpf_ctx *c, double *P, int64_t ld, int rows, int cols, int fused, int info_base, int ipiv_offset, int *d_ipiv);
 int dgetf2_piv_reserve(mpf_ctx *c, int rows);
+// dpivot.hip: the same panel with tournament pivoting (mpf_dgetf2_tp's rule): the same arguments, the same info word
+int launch_dgetf2_tp(mpf_ctx *c, double *P, int64_t ld, int rows, int cols, int fused, int info_base, int ipiv_offset, int *d_ipiv);
+int dgetf2_tp_reserve(mpf_ctx *c, int rows);
 int launch_dtrsm_llnu(mpf_ctx *c, int m, int64_t n, const double *L, int64_t ldl, double *B, int64_t ldb);
 int launch_dgemm_minus(mpf_ctx *c, int64_t m, int64_t n, int k, const double *A, int64_t lda,
                        const double *B, int64_t ldb, double *C, int64_t ldc);
