@@ -465,6 +465,63 @@ int mpf_gerfs(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, const
               const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
               int32_t itmax, double *ferr, double *berr, mpf_gerfs_stats *stats);
 
+/* ---- extra-precise refinement (build extension; LAPACK dgerfsx / dla_gerfsx_extended with the XBLAS residual) ---------------------
+ * Every other solve here takes its residual from an fp64 MFMA product, so it stops at a forward error of about kappa(A) 2^-53.  These
+ * two entry points add the precision above fp64: the residual is accumulated in twice the working precision, and refinement is
+ * steered by the size of the corrections, not of the residual.
+ *
+ * mpf_residual_x, the step operator: R = B - op(A) X (op(A) = A or A^T), all matrices column-major on the device (lda, ldx, ldb,
+ * ldr >= N).  Every element is accumulated as an unevaluated pair (hi, lo) from (b, 0): for each k, p = a x, e = fma(a, x, -p) (the
+ * product's exact error), (hi, t) = TwoSum(hi, -p) (Knuth's six operations), lo += t - e; partials of 4096 columns of op(A) are pairs
+ * and are added by the same pair addition in ascending order; the element returned is hi + lo, rounded once.  Its error is at most
+ * 2^-53 |r| + about (N + 1)^2 2^-106 (|b| + |op(A)| |x|)_i.  A non-finite operand makes that element NaN or +-Inf.  One fixed order per
+ * element, the same for every column: R[:, j] has the same bits whatever stands beside it, and two calls return the same bits.
+ * This is fp64 VALU work, about ten instructions per product: several times the cost of the MFMA residual.
+ * Rows N .. ldr - 1 of d_R are not touched.  nrhs = 0: returns 0, no work.  Synchronises. */
+int mpf_residual_x(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, int64_t N, int32_t nrhs,
+                   const double *d_X, int64_t ldx, const double *d_B, int64_t ldb, double *d_R, int64_t ldr);
+
+/* mpf_gerfsx: refines a solution X of op(A) X = B in place (X as mpf_gerfs takes it) and returns, per column, a normwise and a
+ * componentwise forward error bound without a dlacn2 run.  err_norm and err_comp are HOST arrays of nrhs doubles, both required;
+ * stats: nrhs host entries or NULL.  ithresh = 0 means LAPACK's 10; larger values are clamped to 31.
+ * The rule is dla_gerfsx_extended's with the residual precision fixed at "extra" (where LAPACK would raise the precision, the state
+ * becomes NOPROG instead).  eps = 2^-53, rthresh = 0.5, dz_ub = 0.25, HUGE = DBL_MAX.  Per column: x_state = WORKING, z_state =
+ * UNSTABLE, dxratmax = dzratmax = 0, final_dx_x = final_dz_z = prev_dx = prev_dz = HUGE.  Iteration cnt = 0, 1, .. < ithresh:
+ *   r = b - op(A) x as mpf_residual_x forms it; d = op(A)^-1 r on the factors;
+ *   normx = max_i |x_i|, normdx = max_i |d_i|, dz = max_i |d_i| / |x_i| (HUGE where x_i = 0 != d_i, 0 where both are 0);
+ *   a NaN among the three, or an infinite normx or normdx: x_state = NAN, stop;
+ *   dx_x = normdx / normx (normx = 0: 0 if normdx = 0, else HUGE); dxrat = normdx / prev_dx; dzrat = dz / prev_dz;
+ *   x_state NOPROG and dxrat <= rthresh: WORKING again;
+ *   x_state WORKING: dx_x <= eps: CONV; else dxrat > rthresh: NOPROG; else dxratmax = max(dxratmax, dxrat); on leaving WORKING
+ *     final_dx_x = dx_x;
+ *   z_state UNSTABLE and dz <= dz_ub: WORKING;  z_state NOPROG and dzrat <= rthresh: WORKING;
+ *   z_state WORKING: dz <= eps: CONV; else dz > dz_ub: UNSTABLE, dzratmax = 0, final_dz_z = HUGE; else dzrat > rthresh: NOPROG; else
+ *     dzratmax = max(dzratmax, dzrat); in NOPROG or CONV final_dz_z = dz;
+ *   neither state WORKING: stop, and this iteration's d is NOT applied (as in LAPACK); else prev_dx = normdx, prev_dz = dz, x += d.
+ * At the end a state still WORKING takes the last dx_x / dz as its final value, and
+ *   err_norm = final_dx_x / (1 - dxratmax),  err_comp = final_dz_z / (1 - dzratmax),  both at least max(10, sqrt(N)) eps;
+ * a column in state NAN returns +Inf for both.  err_norm bounds max_i |x_i - xtrue_i| / max_i |x_i|, err_comp bounds
+ * max_i |x_i - xtrue_i| / |x_i|; err_comp means something where z_state ends CONV.
+ * All columns of a group of 512 take every step together: one residual, one pass over the factors, one reduction launch with one
+ * read-back and one masked update per step; a column that has stopped is frozen.  A column's arithmetic depends on nothing but its own
+ * data: X[:, j], both bounds and the stats (but ms_total) have the same bits whatever the other columns, nrhs, j's position or the
+ * group, and two calls return the same bits.
+ * What it is not: it computes no berr (mpf_gerfs does), keeps no doubled-precision x (LAPACK's last escalation stage), takes no scale
+ * vectors and is not wired into mpf_gesvx_block or mpf_gesv.
+ * Returns 0 when every column ended with x_state = CONV, 1 otherwise (the stats say which), < 0 on error.  nrhs = 0: returns 0, no
+ * work.  Rows N .. ldx - 1 of d_X are not touched; d_B is preserved.  Synchronises; -4 as the other solves. */
+typedef struct mpf_gerfsx_stats {
+    int32_t iterations;        /* corrections applied to this column (0 .. ithresh) */
+    int32_t x_state;           /* 0 WORKING (ithresh reached), 1 NOPROG, 2 CONV, 3 NAN */
+    int32_t z_state;           /* -1 UNSTABLE, 0 WORKING, 1 NOPROG, 2 CONV */
+    int32_t solves;            /* tile solves that entered this column's decisions: iterations, + 1 when the last d was not applied */
+    double final_dx_x, final_dz_z, dxratmax, dzratmax;
+    double ms_total;           /* wall time of the whole call, the same for every column */
+} mpf_gerfsx_stats;
+int mpf_gerfsx(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu,
+               const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+               int32_t ithresh, double *err_norm, double *err_comp, mpf_gerfsx_stats *stats);
+
 /* ---- expert driver for many right-hand sides (build extension; mpf_gesvx's steps on the tiles of the blocked solve) -----------------
  * Solves op(A) X = B for nrhs columns with ONE factorization: steps 1 .. 4 are mpf_gesvx's, from the same code (equilibrate, factor
  * d_work in the mode try_fp16 asks for, rcond of those factors, the kappa_max gate).  They depend on A only: for the same A and

@@ -34,6 +34,7 @@ C_ABI_SYMBOLS = [
     "mpf_solve_ir_trans", "mpf_lange", "mpf_geequ", "mpf_gecon", "mpf_gesvx",
     "mpf_getrs", "mpf_solve_ir_block", "mpf_gerfs", "mpf_gesvx_block",
     "mpf_dgetf2_piv", "mpf_solve_gmres_ir_block", "mpf_dgetf2_tp",
+    "mpf_residual_x", "mpf_gerfsx",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -94,6 +95,12 @@ class MpfGesvxStats(C.Structure):
 
 class MpfGerfsStats(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("lacn2_iterations", C.c_int32), ("solves", C.c_int32), ("reserved", C.c_int32),
+                ("ms_total", C.c_double)]
+
+
+class MpfGerfsxStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("x_state", C.c_int32), ("z_state", C.c_int32), ("solves", C.c_int32),
+                ("final_dx_x", C.c_double), ("final_dz_z", C.c_double), ("dxratmax", C.c_double), ("dzratmax", C.c_double),
                 ("ms_total", C.c_double)]
 
 
@@ -181,6 +188,9 @@ def load_library(probe=False):
     L.mpf_solve_gmres_ir_block.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, i32, dbl, C.POINTER(MpfGmresStats)]
     L.mpf_gerfs.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, C.POINTER(dbl), C.POINTER(dbl),
                             C.POINTER(MpfGerfsStats)]
+    L.mpf_residual_x.argtypes = [vp, i32, vp, i64, i64, i32, vp, i64, vp, i64, vp, i64]
+    L.mpf_gerfsx.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, C.POINTER(dbl), C.POINTER(dbl),
+                             C.POINTER(MpfGerfsxStats)]
     L.mpf_gesvx_block.argtypes = [vp, vp, i64, i64, i32, vp, vp, i32, vp, i64, vp, i64, i32, i32, i32, dbl, i32, dbl, i32, vp, vp,
                                   C.POINTER(dbl), C.POINTER(dbl), C.POINTER(MpfGesvxStats), C.POINTER(MpfIrStats), C.POINTER(MpfGerfsStats)]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
@@ -793,6 +803,49 @@ class MPFContext:
                               _ptr(B), ldb, _ptr(Xr), ldx, int(itmax), ferr.ctypes.data_as(dp), berr.ctypes.data_as(dp), st)
         self._check(rc, "mpf_gerfs")
         return Xr, ferr[:nrhs], berr[:nrhs], list(st)[:nrhs]
+
+    # ---- extra-precise refinement (include/mpf_c.h: mpf_residual_x, mpf_gerfsx) -------------------------------------------------------
+    def residual_x(self, A, X, B, trans=False):
+        """mpf_residual_x: R = B - op(A) X with every element accumulated in twice the working precision and rounded once.  Returns
+        a new R (a vector when B is); A, X, B stay untouched."""
+        self._bind()
+        n = A.shape[0]
+        vec = B.dim() == 1
+        _, nrhs, ldb = self._rhs(B)
+        _, nx, ldx = self._rhs(X)
+        assert nx == nrhs, "residual_x: B and X need the same number of columns"
+        R = self.torch.empty(n, dtype=self.torch.float64, device=self.device) if vec else self.colmajor(n, nrhs)
+        ldr = n if vec else _colmajor_ld(R)
+        rc = self.L.mpf_residual_x(self.h, int(bool(trans)), _ptr(A), _colmajor_ld(A), n, nrhs, _ptr(X), ldx, _ptr(B), ldb, _ptr(R), ldr)
+        self._check(rc, "mpf_residual_x")
+        return R
+
+    def gerfsx(self, A, LU, ipiv, B, X, trans=False, ithresh=0, overwrite=False):
+        """mpf_gerfsx (LAPACK dgerfsx with the extra-precise residual): refines the solution X of op(A) X = B and returns
+        (X, err_norm, err_comp, stats) -- the normwise and componentwise forward error bounds as numpy arrays with one entry per column,
+        stats a list per column (x_state 2 = converged).  X is copied first and B, X stay untouched, unless overwrite=True: then X itself
+        is refined in place and returned.  ithresh = 0: LAPACK's 10 iterations at most.  A column that did not converge does not raise:
+        its stats say so."""
+        import numpy as np
+        self._bind()
+        n = A.shape[0]
+        if overwrite:
+            Xr = X
+        elif X.dim() == 1:
+            Xr = X.clone()
+        else:
+            Xr = self.colmajor(n, X.shape[1])
+            Xr.copy_(X)
+        _, nrhs, ldb = self._rhs(B)
+        _, nx, ldx = self._rhs(Xr)
+        assert nx == nrhs, "gerfsx: B and X need the same number of columns"
+        en, ec = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+        st = (MpfGerfsxStats * max(nrhs, 1))()
+        dp = C.POINTER(C.c_double)
+        rc = self.L.mpf_gerfsx(self.h, int(bool(trans)), _ptr(A), _colmajor_ld(A), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n, nrhs,
+                               _ptr(B), ldb, _ptr(Xr), ldx, int(ithresh), en.ctypes.data_as(dp), ec.ctypes.data_as(dp), st)
+        self._check(rc, "mpf_gerfsx")
+        return Xr, en[:nrhs], ec[:nrhs], list(st)[:nrhs]
 
     # ---- expert driver for many right-hand sides (include/mpf_c.h: mpf_gesvx_block) ---------------------------------------------
     def gesvx_block(self, A, B, nb=256, trans=False, equilibrate=1, try_fp16=1, kappa_max=0.0, max_iter=10, tol=1e-12, itmax=0,

@@ -3,6 +3,7 @@
 //   mpf_solve_ir_block   fp64 refinement of all columns together, per-column rules and stats of mpf_solve_ir_nrhs / _trans
 //   mpf_gerfs            LAPACK dgerfs: refinement by the componentwise backward error, berr and the forward bound ferr per column
 //   mpf_solve_gmres_ir_block   GMRES-IR (mpf_solve_gmres_ir's method) on all columns of a group in lock-step, op(A) = A or A^T
+//   mpf_residual_x, mpf_gerfsx   LAPACK dgerfsx: the residual in pairs of doubles, refinement steered by the corrections' size (blk_xrefine_core)
 // The bodies of the second and third are cores (blk_refine_core, blk_bounds_core) that take optional scale vectors for the factors of an
 // equilibrated copy Dr A Dc: mpf_gesvx_block (mpf_expert.cpp) calls them with its scales, the public functions with none.
 // The right-hand sides go through the device in groups of at most GROUP_TILES tiles of BLK_T columns (solve_block.hip); every
@@ -253,6 +254,69 @@ int blk_bounds_core(mpf_ctx *c, bool tr, const double *d_A, int64_t lda, const d
     return 0;
 }
 
+// The body of mpf_gerfsx (mpf_internal.h): dla_gerfsx_extended's loop on all columns of a group in lock-step.  Per step one residual in
+// pairs of doubles (launch_blk_residual_x), one tile_getrs, one launch and one read-back of the three measures, XrCol's decision per
+// column (solve_rules.h) and one masked update; a column that has stopped is frozen.  Tile sets: B, X, R (then in place d) and
+// tile_getrs's two.
+int blk_xrefine_core(mpf_ctx *c, bool tr, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
+                     const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t ithresh, double *err_norm, double *err_comp,
+                     mpf_gerfsx_stats *st) {
+    int rc;
+    for (int32_t j0 = 0; j0 < nrhs; j0 += GROUP_TILES * BLK_T) {
+        const int64_t ncols = std::min<int64_t>(nrhs - j0, GROUP_TILES * BLK_T);
+        Group g;
+        rc = group_tiles(c, N, (int)((ncols + BLK_T - 1) / BLK_T), 5, g);
+        if (rc) return rc;
+        const int64_t tcols = (int64_t)BLK_T * g.ntiles;
+        double *Bt = g.t(0), *Xt = g.t(1), *R = g.t(2), *W = g.t(3), *Z = g.t(4);
+        MPF_HIP_TRY(c, c->blk_mask.grow(tcols));
+        rc = launch_blk_load(c, d_B + (int64_t)j0 * ldb, ldb, nullptr, N, ncols, Bt, g.ldt, g.ntiles);
+        if (!rc) rc = launch_blk_load(c, d_X + (int64_t)j0 * ldx, ldx, nullptr, N, ncols, Xt, g.ldt, g.ntiles);
+        if (rc) return rc;
+        std::vector<XrCol> col((size_t)ncols);
+        std::vector<int> active((size_t)ncols, 1), mask((size_t)tcols, 0), solves((size_t)ncols, 0);
+        std::vector<double> red((size_t)(3 * ncols));
+        for (int cnt = 0; cnt < ithresh; ++cnt) {
+            rc = launch_blk_residual_x(c, d_A, lda, N, tr, Xt, Bt, R, g.ldt, g.ntiles);
+            if (!rc) rc = tile_getrs(c, d_LU, ldlu, N, tr, R, R, W, Z, g);   // d = op(A)^-1 r (into R: the next step rebuilds r)
+            if (!rc) rc = launch_blk_xr_measure(c, Xt, R, g.ldt, N, ncols);
+            if (rc) return rc;
+            MPF_HIP_TRY(c, hipMemcpyAsync(red.data(), c->blk_red, red.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+            bool any = false;
+            for (int64_t j = 0; j < ncols; ++j) {
+                if (active[(size_t)j]) {
+                    ++solves[(size_t)j];
+                    active[(size_t)j] = col[(size_t)j].step(red[(size_t)j], red[(size_t)(ncols + j)], red[(size_t)(2 * ncols + j)]);
+                }
+                mask[(size_t)j] = active[(size_t)j];
+                any = any || active[(size_t)j];
+            }
+            if (!any) break;
+            MPF_HIP_TRY(c, hipMemcpyAsync(c->blk_mask, mask.data(), (size_t)tcols * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            rc = launch_blk_masked_axpy(c, R, c->blk_mask, Xt, g.ldt, g.ntiles);
+            if (rc) return rc;
+            MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));   // `mask` is a host vector reused by the next step
+        }
+        rc = launch_blk_store(c, Xt, g.ldt, nullptr, N, ncols, d_X + (int64_t)j0 * ldx, ldx);
+        if (rc) return rc;
+        for (int64_t j = 0; j < ncols; ++j) {
+            XrCol &cj = col[(size_t)j];
+            cj.finish(N, err_norm[j0 + j], err_comp[j0 + j]);
+            mpf_gerfsx_stats &s = st[(size_t)(j0 + j)];
+            s.iterations = cj.corrections;
+            s.x_state = cj.x_state;
+            s.z_state = cj.z_state;
+            s.solves = solves[(size_t)j];
+            s.final_dx_x = cj.final_dx_x;
+            s.final_dz_z = cj.final_dz_z;
+            s.dxratmax = cj.dxratmax;
+            s.dzratmax = cj.dzratmax;
+        }
+    }
+    return 0;
+}
+
 // The body of mpf_solve_gmres_ir_block (mpf_internal.h).  Per column the rules are GmresCol's (solve_rules.h); the columns of a group
 // take every outer step and every inner step together: one launch_blk_residual and one tile_getrs per product, one orthogonalisation
 // (launch_gmres_ortho) and ONE read-back -- h, h', ||w||^2 of every column -- per inner step.  A column whose inner loop has ended
@@ -465,6 +529,56 @@ int mpf_gerfs(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const d
     for (auto &s : st) s.ms_total = ms;
     if (stats) std::copy(st.begin(), st.end(), stats);
     return solve_check_waits(c);
+}
+
+int mpf_residual_x(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t N, int32_t nrhs, const double *d_X, int64_t ldx,
+                   const double *d_B, int64_t ldb, double *d_R, int64_t ldr) {
+    if (!c) return -1;
+    if (check_args(c, "residual_x", trans, N, nrhs, lda, ldb)) return -1;
+    if (ldx < N || ldr < N) { c->err = "residual_x: leading dimension < N"; return -1; }
+    if (nrhs == 0) return 0;
+    if (!d_A || !d_X || !d_B || !d_R) { c->err = "residual_x: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int32_t j0 = 0; j0 < nrhs; j0 += GROUP_TILES * BLK_T) {
+        const int64_t ncols = std::min<int64_t>(nrhs - j0, GROUP_TILES * BLK_T);
+        Group g;
+        int rc = group_tiles(c, N, (int)((ncols + BLK_T - 1) / BLK_T), 3, g);
+        if (rc) return rc;
+        double *Bt = g.t(0), *Xt = g.t(1), *R = g.t(2);
+        rc = launch_blk_load(c, d_B + (int64_t)j0 * ldb, ldb, nullptr, N, ncols, Bt, g.ldt, g.ntiles);
+        if (!rc) rc = launch_blk_load(c, d_X + (int64_t)j0 * ldx, ldx, nullptr, N, ncols, Xt, g.ldt, g.ntiles);
+        if (!rc) rc = launch_blk_residual_x(c, d_A, lda, N, trans == 1, Xt, Bt, R, g.ldt, g.ntiles);
+        if (!rc) rc = launch_blk_store(c, R, g.ldt, nullptr, N, ncols, d_R + (int64_t)j0 * ldr, ldr);
+        if (rc) return rc;
+    }
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mpf_gerfsx(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
+               int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t ithresh, double *err_norm,
+               double *err_comp, mpf_gerfsx_stats *stats) {
+    if (!c) return -1;
+    if (check_args(c, "gerfsx", trans, N, nrhs, ldlu, ldb)) return -1;
+    if (lda < N || ldx < N) { c->err = "gerfsx: leading dimension < N"; return -1; }
+    if (nrhs == 0) return 0;
+    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !err_norm || !err_comp) { c->err = "gerfsx: null pointer"; return -1; }
+    if (ithresh <= 0) ithresh = 10;
+    if (ithresh > 31) ithresh = 31;
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = solve_setup(c, d_LU, ldlu, d_ipiv, N);
+    if (rc) return rc;
+    std::vector<mpf_gerfsx_stats> st((size_t)nrhs);
+    rc = blk_xrefine_core(c, trans == 1, d_A, lda, d_LU, ldlu, N, nrhs, d_B, ldb, d_X, ldx, ithresh, err_norm, err_comp, st.data());
+    if (rc) return rc;
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const double ms = ms_since(t0);
+    bool all = true;
+    for (auto &s : st) { s.ms_total = ms; all = all && s.x_state == XrCol::X_CONV; }
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    rc = solve_check_waits(c);
+    return rc ? rc : (all ? 0 : 1);
 }
 
 int mpf_solve_gmres_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu,

@@ -445,6 +445,17 @@ int launch_blk_scale(mpf_ctx *c, double *v, const double *w, int64_t ldt, int nt
 int launch_blk_ferr_weight(mpf_ctx *c, const double *r, double *w, int64_t n, int64_t ncols, int64_t ldt, double nzeps, double safe1, double safe2);
 int launch_blk_lacn2_fill(mpf_ctx *c, double *v, int64_t n, int64_t ncols, int64_t ldt, const int *kind, const int *at);
 int launch_blk_lacn2_sign(mpf_ctx *c, double *v, double *isgn, int64_t n, int64_t ncols, int64_t ldt, const int *live);
+// extra-precise refinement (solve_xr.hip).  launch_blk_residual_x: launch_blk_residual with every element accumulated as an unevaluated
+// pair of doubles (its partial pairs take 2 x the plain residual's room in c->blk_part).  launch_blk_xr_measure: max |x|, max |d| and
+// max |d_i| / |x_i| (DBL_MAX where x_i = 0 != d_i) per column of the tiles X and D, one launch, into c->blk_red (3 x ncols doubles)
+int launch_blk_residual_x(mpf_ctx *c, const double *A, int64_t lda, int64_t n, bool trans, const double *X, const double *B, double *R,
+                          int64_t ldt, int ntiles);
+int launch_blk_xr_measure(mpf_ctx *c, const double *X, const double *D, int64_t ldt, int64_t n, int64_t ncols);
+// mpf_block.cpp: the body of mpf_gerfsx after its argument checks and solve_setup (ithresh clamped there); `st` holds nrhs zeroed
+// entries; neither synchronises at its end nor sets ms_total
+int blk_xrefine_core(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
+                     const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t ithresh, double *err_norm, double *err_comp,
+                     mpf_gerfsx_stats *st);
 // mpf_block.cpp: the bodies of mpf_solve_ir_block and mpf_gerfs on the ORIGINAL system (A, B, X) with the preconditioner
 //     op(A)^-1 v ~ post .* op(L U, P)^-1 (pre .* v)        (pre / post: scale vectors of the factored matrix Dr A Dc, or null)
 // trans = 0: pre = Dr, post = Dc; trans = 1: pre = Dc, post = Dr.  The factors are prepared (solve_setup); `st` holds nrhs zeroed

@@ -1,7 +1,7 @@
 // The decisions of the solve layer, host arithmetic only (no HIP: a plain C++17 compiler takes this file, tests/solve_rules_driver.cpp
 // does): when refinement stops, dlacn2's state machine, the summary column of a blocked attempt, dgerfs's constants, GMRES-IR's
-// per-column decisions.  Every solve path -- refine_vector (solve_common.h), blk_refine_core, gecon_core, blk_bounds_core,
-// mpf_gesvx_block, blk_gmres_core -- takes them from here.
+// per-column decisions, dgerfsx's per-column state machine.  Every solve path -- refine_vector (solve_common.h), blk_refine_core,
+// gecon_core, blk_bounds_core, mpf_gesvx_block, blk_gmres_core, blk_xrefine_core -- takes them from here.
 #pragma once
 #include <algorithm>
 #include <cfloat>
@@ -142,5 +142,59 @@ struct GmresCol {
             for (int j = i + 1; j < k; ++j) s2 -= H[(size_t)i * m + j] * y[j];
             y[i] = s2 / H[(size_t)i * m + i];
         }
+    }
+};
+
+// mpf_gerfsx's rule for one column (mpf_c.h states it in full): LAPACK dla_gerfsx_extended's state machine with the residual precision
+// fixed at "extra" -- wherever LAPACK would raise the precision, the state becomes NOPROG.  The caller forms r = b - op(A) x,
+// d = op(A)^-1 r and the three measures; step() is called once per iteration and says whether x += d follows (false: the column has
+// stopped for good; the caller also stops it after ithresh iterations), finish() gives the two bounds.
+struct XrCol {
+    enum { X_WORKING = 0, X_NOPROG = 1, X_CONV = 2, X_NAN = 3 };
+    enum { Z_UNSTABLE = -1, Z_WORKING = 0, Z_NOPROG = 1, Z_CONV = 2 };
+    static constexpr double RTHRESH = 0.5, DZ_UB = 0.25, HUGEVAL = DBL_MAX;
+    int x_state = X_WORKING, z_state = Z_UNSTABLE;
+    int corrections = 0;
+    double dxratmax = 0, dzratmax = 0, final_dx_x = HUGEVAL, final_dz_z = HUGEVAL, prev_dx = HUGEVAL, prev_dz = HUGEVAL;
+    double last_dx_x = HUGEVAL, last_dz = HUGEVAL;   // of the latest step (what a state still WORKING ends with)
+    // normx = max |x_i|, normdx = max |d_i|, dz = max |d_i| / |x_i|
+    bool step(double normx, double normdx, double dz) {
+        if (normx != normx || normdx != normdx || dz != dz || std::isinf(normx) || std::isinf(normdx)) {
+            x_state = X_NAN;
+            return false;
+        }
+        const double dx_x = normx != 0 ? normdx / normx : (normdx == 0 ? 0.0 : HUGEVAL);
+        const double dxrat = normdx / prev_dx, dzrat = dz / prev_dz;
+        last_dx_x = dx_x;
+        last_dz = dz;
+        if (x_state == X_NOPROG && dxrat <= RTHRESH) x_state = X_WORKING;
+        if (x_state == X_WORKING) {
+            if (dx_x <= LAPACK_EPS) x_state = X_CONV;
+            else if (dxrat > RTHRESH) x_state = X_NOPROG;
+            else if (dxratmax < dxrat) dxratmax = dxrat;
+            if (x_state > X_WORKING) final_dx_x = dx_x;
+        }
+        if (z_state == Z_UNSTABLE && dz <= DZ_UB) z_state = Z_WORKING;
+        if (z_state == Z_NOPROG && dzrat <= RTHRESH) z_state = Z_WORKING;
+        if (z_state == Z_WORKING) {
+            if (dz <= LAPACK_EPS) z_state = Z_CONV;
+            else if (dz > DZ_UB) { z_state = Z_UNSTABLE; dzratmax = 0; final_dz_z = HUGEVAL; }
+            else if (dzrat > RTHRESH) z_state = Z_NOPROG;
+            else if (dzratmax < dzrat) dzratmax = dzrat;
+            if (z_state > Z_WORKING) final_dz_z = dz;
+        }
+        if (x_state != X_WORKING && z_state != Z_WORKING) return false;   // this iteration's correction is NOT applied, as in LAPACK
+        prev_dx = normdx;
+        prev_dz = dz;
+        ++corrections;
+        return true;
+    }
+    void finish(int64_t N, double &err_norm, double &err_comp) {
+        if (x_state == X_NAN) { err_norm = err_comp = HUGE_VAL; return; }
+        if (x_state == X_WORKING) final_dx_x = last_dx_x;
+        if (z_state == Z_WORKING) final_dz_z = last_dz;
+        const double err_lbnd = std::max(10.0, std::sqrt((double)N)) * LAPACK_EPS;   // dgerfsx's floor
+        err_norm = std::max(final_dx_x / (1 - dxratmax), err_lbnd);
+        err_comp = std::max(final_dz_z / (1 - dzratmax), err_lbnd);
     }
 };
