@@ -731,18 +731,29 @@ class MPFContext:
             return B.view(-1, 1), 1, max(B.shape[0], 1)
         return B, B.shape[1], _colmajor_ld(B)
 
+    def _out_like(self, n, B):
+        """(new output, ld) shaped like the right-hand side B: a vector when B is, else n x nrhs column-major."""
+        if B.dim() == 1:
+            return self.torch.empty(n, dtype=self.torch.float64, device=self.device), n
+        X = self.colmajor(n, B.shape[1])
+        return X, _colmajor_ld(X)
+
+    def _inout(self, n, X, overwrite):
+        """X itself (overwrite), or a copy of it: a vector's clone, a matrix's column-major copy."""
+        if overwrite:
+            return X
+        if X.dim() == 1:
+            return X.clone()
+        Xc = self.colmajor(n, X.shape[1])
+        Xc.copy_(X)
+        return Xc
+
     def getrs(self, LU, ipiv, B, trans=False, overwrite=False):
         """mpf_getrs: X = A^-1 B (or A^-T B) with the factors of A.  Returns a new column-major X and leaves B untouched, unless
         overwrite=True: then B itself is solved in place and returned."""
         self._bind()
         n = LU.shape[0]
-        if overwrite:
-            X = B
-        elif B.dim() == 1:
-            X = B.clone()
-        else:
-            X = self.colmajor(n, B.shape[1])
-            X.copy_(B)
+        X = self._inout(n, B, overwrite)
         _, nrhs, ldx = self._rhs(X)
         rc = self.L.mpf_getrs(self.h, int(bool(trans)), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n, nrhs, _ptr(X), ldx)
         self._check(rc, "mpf_getrs")
@@ -753,10 +764,8 @@ class MPFContext:
         Returns (X, list of per-column stats); X is a vector when B is."""
         self._bind()
         n = A.shape[0]
-        vec = B.dim() == 1
         _, nrhs, ldb = self._rhs(B)
-        X = self.torch.empty(n, dtype=self.torch.float64, device=self.device) if vec else self.colmajor(n, nrhs)
-        ldx = n if vec else _colmajor_ld(X)
+        X, ldx = self._out_like(n, B)
         st = (MpfIrStats * max(nrhs, 1))()
         rc = self.L.mpf_solve_ir_block(self.h, int(bool(trans)), _ptr(A), _colmajor_ld(A), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n,
                                        nrhs, _ptr(B), ldb, _ptr(X), ldx, max_iter, tol, st)
@@ -768,10 +777,8 @@ class MPFContext:
         MpfGmresStats); X is a vector when B is.  A column that did not converge does not raise: its stats say so."""
         self._bind()
         n = A.shape[0]
-        vec = B.dim() == 1
         _, nrhs, ldb = self._rhs(B)
-        X = self.torch.empty(n, dtype=self.torch.float64, device=self.device) if vec else self.colmajor(n, nrhs)
-        ldx = n if vec else _colmajor_ld(X)
+        X, ldx = self._out_like(n, B)
         st = (MpfGmresStats * max(nrhs, 1))()
         rc = self.L.mpf_solve_gmres_ir_block(self.h, int(bool(trans)), _ptr(A), _colmajor_ld(A), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n,
                                              nrhs, _ptr(B), ldb, _ptr(X), ldx, max_outer, restart, tol, st)
@@ -786,13 +793,7 @@ class MPFContext:
         import numpy as np
         self._bind()
         n = A.shape[0]
-        if overwrite:
-            Xr = X
-        elif X.dim() == 1:
-            Xr = X.clone()
-        else:
-            Xr = self.colmajor(n, X.shape[1])
-            Xr.copy_(X)
+        Xr = self._inout(n, X, overwrite)
         _, nrhs, ldb = self._rhs(B)
         _, nx, ldx = self._rhs(Xr)
         assert nx == nrhs, "gerfs: B and X need the same number of columns"
@@ -810,12 +811,10 @@ class MPFContext:
         a new R (a vector when B is); A, X, B stay untouched."""
         self._bind()
         n = A.shape[0]
-        vec = B.dim() == 1
         _, nrhs, ldb = self._rhs(B)
         _, nx, ldx = self._rhs(X)
         assert nx == nrhs, "residual_x: B and X need the same number of columns"
-        R = self.torch.empty(n, dtype=self.torch.float64, device=self.device) if vec else self.colmajor(n, nrhs)
-        ldr = n if vec else _colmajor_ld(R)
+        R, ldr = self._out_like(n, B)
         rc = self.L.mpf_residual_x(self.h, int(bool(trans)), _ptr(A), _colmajor_ld(A), n, nrhs, _ptr(X), ldx, _ptr(B), ldb, _ptr(R), ldr)
         self._check(rc, "mpf_residual_x")
         return R
@@ -829,13 +828,7 @@ class MPFContext:
         import numpy as np
         self._bind()
         n = A.shape[0]
-        if overwrite:
-            Xr = X
-        elif X.dim() == 1:
-            Xr = X.clone()
-        else:
-            Xr = self.colmajor(n, X.shape[1])
-            Xr.copy_(X)
+        Xr = self._inout(n, X, overwrite)
         _, nrhs, ldb = self._rhs(B)
         _, nx, ldx = self._rhs(Xr)
         assert nx == nrhs, "gerfsx: B and X need the same number of columns"
@@ -858,13 +851,11 @@ class MPFContext:
         self._bind()
         t = self.torch
         n = A.shape[0]
-        vec = B.dim() == 1
         _, nrhs, ldb = self._rhs(B)
         if work is None:
             work = self.colmajor(n, n)
         ipiv = t.empty(n, dtype=t.int32, device=self.device)
-        X = t.empty(n, dtype=t.float64, device=self.device) if vec else self.colmajor(n, nrhs)
-        ldx = n if vec else _colmajor_ld(X)
+        X, ldx = self._out_like(n, B)
         r = t.empty(n, dtype=t.float64, device=self.device) if want_scales else None
         c = t.empty(n, dtype=t.float64, device=self.device) if want_scales else None
         st = MpfGesvxStats()

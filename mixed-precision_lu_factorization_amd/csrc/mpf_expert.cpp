@@ -447,11 +447,12 @@ int mpf_gesvx_block(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32
     const bool tr = trans == 1;
     const double *pre = nullptr, *post = nullptr;
     std::vector<mpf_ir_stats> cols((size_t)nrhs);
+    const BlkRhs rhs{nrhs, d_B, ldb, d_X, ldx};
     // one attempt: all columns on the factors in d_work; the attempt's summary is its worst column
     rc = gesvx_steps(c, e, d_A, lda, N, nb, d_work, d_ipiv, tr, equilibrate, try_fp16, kappa_max, d_r, d_c, gs, pre, post,
                      [&](const double *pr, const double *po, mpf_ir_stats &worst) {
                          std::fill(cols.begin(), cols.end(), mpf_ir_stats{});
-                         int r2 = blk_refine_core(c, tr, d_A, lda, d_work, N, N, nrhs, d_B, ldb, d_X, ldx, max_iter, tol, pr, po, cols.data());
+                         int r2 = blk_refine_core(BlkSys{c, tr, d_A, lda, d_work, N, N, pr, po}, rhs, max_iter, tol, cols.data());
                          if (r2) return r2;
                          worst = cols[worst_column(cols.data(), cols.size())];
                          return 0;
@@ -463,7 +464,7 @@ int mpf_gesvx_block(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32
     std::vector<mpf_gerfs_stats> rst((size_t)nrhs);
     if (ferr) {
         const auto t1 = std::chrono::steady_clock::now();
-        rc = blk_bounds_core(c, tr, d_A, lda, d_work, N, N, nrhs, d_B, ldb, d_X, ldx, itmax, ferr, berr, pre, post, rst.data());
+        rc = blk_bounds_core(BlkSys{c, tr, d_A, lda, d_work, N, N, pre, post}, rhs, itmax, ferr, berr, rst.data());
         if (rc) return rc;
         MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
         const double ms = ms_since(t1);

@@ -451,21 +451,17 @@ int launch_blk_lacn2_sign(mpf_ctx *c, double *v, double *isgn, int64_t n, int64_
 int launch_blk_residual_x(mpf_ctx *c, const double *A, int64_t lda, int64_t n, bool trans, const double *X, const double *B, double *R,
                           int64_t ldt, int ntiles);
 int launch_blk_xr_measure(mpf_ctx *c, const double *X, const double *D, int64_t ldt, int64_t n, int64_t ncols);
-// mpf_block.cpp: the body of mpf_gerfsx after its argument checks and solve_setup (ithresh clamped there); `st` holds nrhs zeroed
-// entries; neither synchronises at its end nor sets ms_total
-int blk_xrefine_core(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
-                     const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t ithresh, double *err_norm, double *err_comp,
-                     mpf_gerfsx_stats *st);
-// mpf_block.cpp: the bodies of mpf_solve_ir_block and mpf_gerfs on the ORIGINAL system (A, B, X) with the preconditioner
+// mpf_block.cpp: what every core of the blocked solve layer receives.  BlkSys: op(A) = A or A^T (tr), the ORIGINAL matrix and its
+// prepared factors (solve_setup) with the preconditioner
 //     op(A)^-1 v ~ post .* op(L U, P)^-1 (pre .* v)        (pre / post: scale vectors of the factored matrix Dr A Dc, or null)
-// trans = 0: pre = Dr, post = Dc; trans = 1: pre = Dc, post = Dr.  The factors are prepared (solve_setup); `st` holds nrhs zeroed
-// entries; neither core synchronises at its end nor sets ms_total.
-int blk_refine_core(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
-                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_iter, double tol, const double *pre,
-                    const double *post, mpf_ir_stats *st);
-int blk_bounds_core(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
-                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *ferr, double *berr, const double *pre,
-                    const double *post, mpf_gerfs_stats *st);
+// tr = 0: pre = Dr, post = Dc; tr = 1: pre = Dc, post = Dr.  BlkRhs: the right-hand sides and the solutions, column-major.
+struct BlkSys { mpf_ctx *c; bool tr; const double *A; int64_t lda; const double *LU; int64_t ldlu; int64_t N; const double *pre, *post; };
+struct BlkRhs { int32_t nrhs; const double *B; int64_t ldb; double *X; int64_t ldx; };
+// The bodies of mpf_solve_ir_block, mpf_gerfs and mpf_gerfsx (ithresh clamped by the caller; no scales) after the argument checks and
+// solve_setup; `st` holds nrhs zeroed entries; no core synchronises at its end or sets ms_total.
+int blk_refine_core(const BlkSys &s, const BlkRhs &r, int32_t max_iter, double tol, mpf_ir_stats *st);
+int blk_bounds_core(const BlkSys &s, const BlkRhs &r, int32_t itmax, double *ferr, double *berr, mpf_gerfs_stats *st);
+int blk_xrefine_core(const BlkSys &s, const BlkRhs &r, int32_t ithresh, double *err_norm, double *err_comp, mpf_gerfsx_stats *st);
 // solve_gmres.hip: the orthogonalisation (classical Gram-Schmidt twice) and the vector updates of the blocked GMRES-IR; basis slot i at
 // V + i * vs, tiles as above.  launch_gmres_ortho: W = -W orthogonalised against the slots 0 .. ns - 1 on the columns with live[j] != 0,
 // out = [h (ns x tc) | h' (ns x tc) | ||w||^2 (tc)], tc = BLK_T * ntiles; part: gmres_ortho_chunks(ldt) * max(ns, 4) * tc doubles
@@ -475,11 +471,8 @@ int launch_gmres_ortho(mpf_ctx *c, const double *V, int64_t vs, int ns, double *
 int launch_gmres_append(mpf_ctx *c, const double *src, const double *scale, double *dst, int64_t ldt, int64_t n, int ntiles);   // dst = src * scale[j] where scale[j] != 0
 int launch_gmres_xupdate(mpf_ctx *c, const double *V, int64_t vs, const double *y, const int *cnt, double *X, int64_t ldt, int64_t n,
                          int ntiles);   // X[:, j] += sum_{i < cnt[j]} y[i * tc + j] V_i[:, j]
-// mpf_block.cpp: the body of mpf_solve_gmres_ir_block after its argument checks and solve_setup; restart and max_outer clamped
-// (gmres_clamp); `st` holds nrhs zeroed entries; neither synchronises at its end nor sets ms_total.
-int blk_gmres_core(mpf_ctx *c, bool trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, int32_t nrhs,
-                   const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t max_outer, int32_t restart, double tol,
-                   mpf_gmres_stats *st);
+// mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
+int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 
 // ---- host-side helpers shared by the schedules (mpf_host.cpp, mpf_dist.cpp) --------------------------------------------
 struct StreamSwap { // launch_* helpers use c->stream: point it at another stream for a scope

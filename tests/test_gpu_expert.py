@@ -2,32 +2,19 @@
 import numpy as np
 import pytest
 
+import blk_helpers as H
 import lacn2_model as M
 
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(np.float64).eps
 
 
-def _rand(n, seed):
-    rng = np.random.default_rng(seed)
-    return np.asfortranarray(rng.uniform(-1, 1, (n, n)))
-
-
-def _factor(ctx, A_np, nb=128, trailing=0):
-    dA = ctx.from_numpy_f(A_np)
-    W = dA.clone()
-    ipiv, info = ctx.factor(W, nb, trailing=trailing)
-    ctx.synchronize()
-    return dA, W, ipiv, info
-
-
 @pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257, 1000, 2085, 4096])
 def test_solve_trans_sizes(ctx, n):
     """A^T x = b with fp64 factors: one solve within c kappa eps of numpy, refinement to 1e-12."""
     import torch
-    A = _rand(n, 100 + n)
-    A[np.arange(n), np.arange(n)] += 2.0 if n > 1 else 0.5
-    dA, W, ipiv, info = _factor(ctx, A)
+    A = H.rand(n, 100 + n)
+    dA, W, ipiv, info = H.factor(ctx, A)
     assert info == 0
     b_np = np.random.default_rng(n).uniform(-1, 1, n)
     b = torch.from_numpy(b_np).to(ctx.device)
@@ -46,8 +33,7 @@ def test_solve_trans_lda_nrhs_repeatable(ctx):
     """lda > N with the padding untouched, three right-hand sides, and two calls with the same bits."""
     import torch
     n, lda, nrhs = 777, 800, 3
-    A = _rand(n, 7)
-    A[np.arange(n), np.arange(n)] += 3.0
+    A = H.rand(n, 7, dominant=3.0)
     buf = ctx.colmajor(lda, n)
     buf.fill_(7.5)
     dA = buf[:n, :]
@@ -119,7 +105,7 @@ def test_geequ_matches_restatement_and_scaled_copy(ctx, mpf):
     assert np.all(np.frexp(rr)[0] == 0.5) and np.all(np.frexp(cc)[0] == 0.5)
     # equilibrate = 2, fp64: the work matrix holds the factors of Dr A Dc
     S = np.asfortranarray((A * rr[:, None]) * cc[None, :])
-    _, W_ref, ip_ref, _ = _factor(ctx, S, nb=256)
+    _, W_ref, ip_ref, _ = H.factor(ctx, S, nb=256, check=False)
     b = torch.from_numpy(rng.uniform(-1, 1, n)).to(ctx.device)
     A0 = dA.clone()
     x, st, W, ipiv, r2, c2 = ctx.gesvx(dA, b, nb=256, equilibrate=2, try_fp16=0, want_scales=True)
@@ -137,10 +123,10 @@ def test_geequ_matches_restatement_and_scaled_copy(ctx, mpf):
 
 @pytest.mark.parametrize("n", [1, 5, 64, 300, 1024, 2048])
 def test_gecon_against_restatement(ctx, n):
-    A = _rand(n, 30 + n)
+    A = H.rand(n, 30 + n, dominant=None)
     if n > 1:
         A[:, 0] *= 1e3
-    dA, W, ipiv, info = _factor(ctx, A)
+    dA, W, ipiv, info = H.factor(ctx, A, check=False)
     LU = ctx.to_numpy_f(W)
     Lm = np.tril(LU, -1) + np.eye(n)
     Um = np.triu(LU)
@@ -160,8 +146,8 @@ def test_gecon_against_restatement(ctx, n):
 
 def test_gecon_degenerate(ctx):
     n = 100
-    A = _rand(n, 9)
-    dA, W, ipiv, info = _factor(ctx, A)
+    A = H.rand(n, 9, dominant=None)
+    dA, W, ipiv, info = H.factor(ctx, A, check=False)
     rcond, _ = ctx.gecon(W, 0.0, "1")
     assert rcond == 0.0
     W[3, 3] = 0.0

@@ -19,72 +19,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import blk_helpers as H
 import gerfs_model as G
 
 pytestmark = pytest.mark.gpu
 EPS = G.EPS
 LD = np.longdouble
-
-
-def _rand(n, seed, dominant=2.0):
-    A = np.random.default_rng(seed).uniform(-1, 1, (n, n))
-    A[np.arange(n), np.arange(n)] += dominant if n > 1 else 0.5
-    return np.asfortranarray(A)
-
-
-def _ill(n, kappa, seed):
-    rng = np.random.default_rng(seed)
-    U, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    V, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    s = np.logspace(0, -np.log10(kappa), n)
-    return np.asfortranarray((U * s) @ V.T)
-
-
-def _factor(ctx, A_np, ld=None, nb=128, trailing=0):
-    """Device copy of A and its factors (LU stored with leading dimension ld)."""
-    n = A_np.shape[0]
-    dA = ctx.from_numpy_f(A_np)
-    buf = ctx.colmajor(ld or n, n)
-    W = buf[:n]
-    W.copy_(dA)
-    ipiv, info = ctx.factor(W, nb, trailing=trailing)
-    ctx.synchronize()
-    assert info == 0
-    return dA, W, ipiv
-
-
-def _dev(ctx, M_np, ld=None, fill=7.5):
-    """Column-major device copy of M with leading dimension ld (rows beyond N hold `fill`): (the N-row view, the whole buffer)."""
-    import torch
-    n, m = M_np.shape
-    buf = ctx.colmajor(ld or n, m)
-    buf.fill_(fill)
-    v = buf[:n]
-    v.copy_(torch.from_numpy(np.ascontiguousarray(M_np)))
-    return v, buf
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def _host_solvers(LU, ipiv, trans):
-    """(solve, solve_t) = (op(A)^-1 V, op(A)^-T V) on the host with the DEVICE's factors P A = L U, as products with the explicit
-    (L U)^-1: the model's solves are then one matrix product each."""
-    n = LU.shape[0]
-    perm = np.arange(n)
-    for i, p in enumerate(np.asarray(ipiv, dtype=np.int64) - 1):
-        perm[[i, p]] = perm[[p, i]]
-    M = np.linalg.inv((np.tril(LU, -1) + np.eye(n)) @ np.triu(LU))
-
-    def inv(v):
-        return M @ v[perm]
-
-    def inv_t(v):
-        out = np.empty_like(v)
-        out[perm] = M.T @ v
-        return out
-    return (inv_t, inv) if trans else (inv, inv_t)
 
 
 def _ld_product(Al, Xl):
@@ -154,14 +94,14 @@ def _check(ref, X, ferr, berr, model, fp16, bound_holds=True, cols=None, tag=Non
 def _run(ctx, A, trans, B_np, trailing, ld=None, nb=128, itmax=0):
     """Factor, start from getrs, refine on the device and in the model.  Returns (ref, X, ferr, berr, stats, model, buffers)."""
     n = A.shape[0]
-    dA, W, ipiv = _factor(ctx, A, ld=ld, nb=nb, trailing=trailing)
-    B, Bbuf = _dev(ctx, B_np, ld)
+    dA, W, ipiv, _ = H.factor(ctx, A, ld=ld, nb=nb, trailing=trailing)
+    B, Bbuf = H.dev(ctx, B_np, ld)
     X0 = ctx.getrs(W, ipiv, B, trans=trans)
-    Xv, Xbuf = _dev(ctx, X0.cpu().numpy(), ld)
+    Xv, Xbuf = H.dev(ctx, X0.cpu().numpy(), ld)
     X, ferr, berr, st = ctx.gerfs(dA, W, ipiv, B, Xv, trans=trans, itmax=itmax, overwrite=True)
     ctx.synchronize()
     assert X.data_ptr() == Xv.data_ptr()
-    solve, solve_t = _host_solvers(ctx.to_numpy_f(W), ipiv.cpu().numpy(), trans)
+    solve, solve_t = H.host_solvers(ctx.to_numpy_f(W), ipiv.cpu().numpy(), trans)
     model = G.gerfs_model(A, solve, solve_t, B_np, X0.cpu().numpy(), trans, itmax)
     return _Ref(A, trans, B_np), X.cpu().numpy(), ferr, berr, st, model, (Bbuf, Xbuf)
 
@@ -177,7 +117,7 @@ SHAPES = [(1, 1, None), (2, 17, None), (63, 33, None), (256, 65, None), (257, 17
 def test_bounds(ctx, n, nrhs, ld, trans, trailing):
     """berr is what it says, ferr bounds the error and is not slack: fp64 factors of every shape, fp16 factors of the diagonally
     dominant matrix of every shape.  Rows N .. ld - 1 of X and B keep their sentinel."""
-    A = _rand(n, 500 + n, dominant=float(n) ** 0.5 if trailing else 2.0)
+    A = H.rand(n, 500 + n, dominant=float(n) ** 0.5 if trailing else 2.0)
     B_np = np.random.default_rng(nrhs).uniform(-1, 1, (n, nrhs))
     ref, X, ferr, berr, st, model, (Bbuf, Xbuf) = _run(ctx, A, trans, B_np, trailing, ld=ld, itmax=10 if trailing else 0)
     _check(ref, X, ferr, berr, model, fp16=bool(trailing), tag=(n, nrhs, trans, trailing))
@@ -194,7 +134,7 @@ def test_bounds_grow_with_kappa(ctx):
     matrices error <= ferr is false in the model too: not asserted.)"""
     ferrs = []
     for n, kappa, seed in ((257, 1e6, 6), (300, 1e10, 7)):
-        A = _ill(n, kappa, seed)
+        A = H.ill(n, kappa, seed)
         B_np = np.random.default_rng(seed).uniform(-1, 1, (n, 17))
         for trans in (0, 1):
             ref, X, ferr, berr, st, model, _ = _run(ctx, A, trans, B_np, 0)
@@ -208,7 +148,7 @@ def lowp(ctx):
     """N = 4096, 40 columns scaled 1e-6 .. 1e6 and one zero column, fp16 factors of a diagonally dominant matrix, both op(A): the
     device's and the model's refinement from getrs's X, itmax = 10.  Shared and left unchanged."""
     n, nrhs = 4096, 40
-    A = _rand(n, 21, dominant=float(n) ** 0.5)
+    A = H.rand(n, 21, dominant=float(n) ** 0.5)
     B_np = np.random.default_rng(5).uniform(-1, 1, (n, nrhs)) * np.logspace(-6, 6, nrhs)
     B_np[:, 7] = 0.0
     return {trans: _run(ctx, A, trans, B_np, 1, nb=256, itmax=10) for trans in (0, 1)}
@@ -253,14 +193,14 @@ def small16(ctx):
     """N = 1000 on fp16 factors, 37 columns scaled 1e-3 .. 1e3 (test_column_independence's setting in test_gpu_getrs.py)."""
     import torch
     n, nrhs = 1000, 37
-    A = _rand(n, 11)
-    dA, W, ipiv = _factor(ctx, A, trailing=1)
+    A = H.rand(n, 11)
+    dA, W, ipiv, _ = H.factor(ctx, A, trailing=1)
     B = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, (n, nrhs)) * np.logspace(-3, 3, nrhs)).to(ctx.device)
     return dA, W, ipiv, B.t().contiguous().t()
 
 
 def _key(X, ferr, berr, st, j):
-    return (_bits(X.cpu().numpy()[:, j]).tolist(), _bits(ferr[j:j + 1])[0], _bits(berr[j:j + 1])[0], st[j].iterations, st[j].lacn2_iterations)
+    return (H.bits(X.cpu().numpy()[:, j]).tolist(), H.bits(ferr[j:j + 1])[0], H.bits(berr[j:j + 1])[0], st[j].iterations, st[j].lacn2_iterations)
 
 
 @pytest.mark.parametrize("trans", [0, 1])
@@ -314,10 +254,10 @@ def test_arguments(ctx, mpf):
     naming ipiv; rows N .. ld - 1 of X and B keep their sentinel."""
     import torch
     n, ld = 64, 80
-    A = _rand(n, 9)
-    dA, W, ipiv = _factor(ctx, A)
-    B, Bbuf = _dev(ctx, np.ones((n, 2)), ld)
-    X, Xbuf = _dev(ctx, np.linalg.solve(A, np.ones((n, 2))), ld)
+    A = H.rand(n, 9)
+    dA, W, ipiv, _ = H.factor(ctx, A)
+    B, Bbuf = H.dev(ctx, np.ones((n, 2)), ld)
+    X, Xbuf = H.dev(ctx, np.linalg.solve(A, np.ones((n, 2))), ld)
     L, h = ctx.L, ctx.h
     p = lambda t: C.c_void_p(t.data_ptr())
     ctx._bind()

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import blk_helpers as H
 import gerfsx_model as G
 
 pytestmark = pytest.mark.gpu
@@ -18,62 +19,13 @@ EPS = G.EPS
 FILL = 7.5
 
 
-def _factor(ctx, A_np, nb=128, trailing=0):
-    n = A_np.shape[0]
-    dA = ctx.from_numpy_f(A_np)
-    W = ctx.colmajor(n, n)
-    W.copy_(dA)
-    ipiv, info = ctx.factor(W, nb, trailing=trailing)
-    ctx.synchronize()
-    assert info == 0
-    return dA, W, ipiv
-
-
-def _dev(ctx, M_np, ld=None):
-    """Column-major device copy of M with leading dimension ld (rows beyond N hold FILL): (the N-row view, the whole buffer)."""
-    import torch
-    n, m = M_np.shape
-    buf = ctx.colmajor(ld or n, m)
-    buf.fill_(FILL)
-    v = buf[:n]
-    v.copy_(torch.from_numpy(np.ascontiguousarray(M_np)))
-    return v, buf
-
-
-def _ld(t):
-    return t.stride(1) if t.shape[1] > 1 else max(t.shape[0], 1)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def _host_solvers(LU, ipiv, trans):
-    """(solve, solve_t) = (op(A)^-1 V, op(A)^-T V) on the host with the DEVICE's factors P A = L U, as products with the explicit
-    (L U)^-1 (tests/test_gpu_gerfs.py: _host_solvers)."""
-    n = LU.shape[0]
-    perm = np.arange(n)
-    for i, p in enumerate(np.asarray(ipiv, dtype=np.int64) - 1):
-        perm[[i, p]] = perm[[p, i]]
-    M = np.linalg.inv((np.tril(LU, -1) + np.eye(n)) @ np.triu(LU))
-
-    def inv(v):
-        return M @ v[perm]
-
-    def inv_t(v):
-        out = np.empty_like(v)
-        out[perm] = M.T @ v
-        return out
-    return (inv_t, inv) if trans else (inv, inv_t)
-
-
 def _resx(ctx, dA, lda, X_np, B_np, trans, pad):
     """mpf_residual_x through the C ABI on buffers with `pad` extra rows of FILL: (R, whether every padding row kept FILL)."""
     n, m = B_np.shape
     ld = n + pad
-    X, Xbuf = _dev(ctx, X_np, ld)
-    B, Bbuf = _dev(ctx, B_np, ld)
-    R, Rbuf = _dev(ctx, np.full((n, m), FILL), ld)
+    X, Xbuf = H.dev(ctx, X_np, ld)
+    B, Bbuf = H.dev(ctx, B_np, ld)
+    R, Rbuf = H.dev(ctx, np.full((n, m), FILL), ld)
     ctx._bind()
     p = lambda t: C.c_void_p(t.data_ptr())
     rc = ctx.L.mpf_residual_x(ctx.h, int(trans), p(dA), lda, n, m, p(X), ld, p(B), ld, p(R), ld)
@@ -93,7 +45,7 @@ def _gerfsx(ctx, dA, W, ipiv, B, X, trans, ithresh=0):
     en, ec = np.zeros(max(m, 1)), np.zeros(max(m, 1))
     st = (mpf.MpfGerfsxStats * max(m, 1))()
     dp = C.POINTER(C.c_double)
-    rc = ctx.L.mpf_gerfsx(ctx.h, int(trans), p(dA), _ld(dA), p(W), _ld(W), p(ipiv), n, m, p(B), _ld(B), p(X), _ld(X), int(ithresh),
+    rc = ctx.L.mpf_gerfsx(ctx.h, int(trans), p(dA), H.ld(dA), p(W), H.ld(W), p(ipiv), n, m, p(B), H.ld(B), p(X), H.ld(X), int(ithresh),
                           en.ctypes.data_as(dp), ec.ctypes.data_as(dp), st)
     assert rc >= 0, ctx.L.mpf_last_error(ctx.h)
     return rc, en[:m], ec[:m], list(st)[:m]
@@ -101,8 +53,8 @@ def _gerfsx(ctx, dA, W, ipiv, B, X, trans, ithresh=0):
 
 def _key(X_np, en, ec, st, j):
     s = st[j]
-    return (_bits(X_np[:, j]).tolist(), _bits(en[j:j + 1])[0], _bits(ec[j:j + 1])[0], s.iterations, s.x_state, s.z_state, s.solves,
-            _bits(np.array([s.final_dx_x, s.final_dz_z, s.dxratmax, s.dzratmax])).tolist())
+    return (H.bits(X_np[:, j]).tolist(), H.bits(en[j:j + 1])[0], H.bits(ec[j:j + 1])[0], s.iterations, s.x_state, s.z_state, s.solves,
+            H.bits(np.array([s.final_dx_x, s.final_dz_z, s.dxratmax, s.dzratmax])).tolist())
 
 
 # ---- the residual ---------------------------------------------------------------------------------------------------------------
@@ -118,7 +70,7 @@ def test_residual_full_mantissa(ctx, n, trans):
     A = G.rand(n, 40 + n)
     Aop = np.ascontiguousarray(A.T if trans else A)
     B = rng.uniform(-1, 1, (n, max(NRHS)))
-    dA, Abuf = _dev(ctx, A, n + 5)
+    dA, Abuf = H.dev(ctx, A, n + 5)
     for kind, X in (("solution", np.linalg.solve(Aop, B)), ("random", rng.uniform(-1, 1, B.shape))):
         Rx = G.exact_residual(Aop, X, B)
         S = np.abs(B) + np.abs(Aop) @ np.abs(X)
@@ -149,7 +101,7 @@ def test_residual_partial_seam_exact(ctx, trans):
     Ri = Bi - Aopi @ Xi                                   # |terms| <= 4100 x 2^50 + 2^62 < 2^63
     assert np.abs(Ri).max() < 2 ** 53
     Rx = Ri * 2.0 ** -50
-    dA, _ = _dev(ctx, A)
+    dA, _ = H.dev(ctx, A)
     R, untouched = _resx(ctx, dA, n, X, B, trans, pad=1)
     print("non-zero entries", np.count_nonzero(Rx), "of", Rx.size, "wrong", np.count_nonzero(R != Rx))
     assert np.count_nonzero(Rx) > 0.5 * Rx.size
@@ -164,7 +116,7 @@ def wide(ctx):
     import torch
     n, m = 64, 513
     A = G.rand(n, 8)
-    dA, W, ipiv = _factor(ctx, A, nb=32)
+    dA, W, ipiv, _ = H.factor(ctx, A, nb=32)
     B = torch.from_numpy(np.random.default_rng(9).uniform(-1, 1, (n, m)) * np.logspace(-3, 3, m)).to(ctx.device).t().contiguous().t()
     out = {}
     for trans in (0, 1):
@@ -185,21 +137,21 @@ def test_column_independence(ctx, wide, trans):
     assert all(s.ms_total == full[3][0].ms_total for s in full[3])
     X2, en2, ec2, st2 = ctx.gerfsx(dA, W, ipiv, B, X0, trans=trans)
     again = (X2.cpu().numpy(), en2, ec2, st2)
-    assert np.array_equal(_bits(ctx.residual_x(dA, X0, B, trans=trans).cpu().numpy()), _bits(R))
+    assert np.array_equal(H.bits(ctx.residual_x(dA, X0, B, trans=trans).cpu().numpy()), H.bits(R))
     for j in range(B.shape[1]):
         assert _key(*again, j) == _key(*full, j), j
     pick = np.random.default_rng(4).permutation(513)[:37]
     pick[:4] = (512, 0, 31, 32)
     idx = torch.from_numpy(pick).to(ctx.device)
     Bp, Xp0 = B[:, idx].t().contiguous().t(), X0[:, idx].t().contiguous().t()
-    assert np.array_equal(_bits(ctx.residual_x(dA, Xp0, Bp, trans=trans).cpu().numpy()), _bits(R[:, pick]))
+    assert np.array_equal(H.bits(ctx.residual_x(dA, Xp0, Bp, trans=trans).cpu().numpy()), H.bits(R[:, pick]))
     Xp, enp, ecp, stp = ctx.gerfsx(dA, W, ipiv, Bp, Xp0, trans=trans)
     permd = (Xp.cpu().numpy(), enp, ecp, stp)
     for i, j in enumerate(pick):
         assert _key(*permd, i) == _key(*full, int(j)), j
     for j in (0, 32, 512):
         bj, xj = B[:, j:j + 1].contiguous(), X0[:, j:j + 1].contiguous()
-        assert np.array_equal(_bits(ctx.residual_x(dA, xj, bj, trans=trans).cpu().numpy()[:, 0]), _bits(R[:, j])), j
+        assert np.array_equal(H.bits(ctx.residual_x(dA, xj, bj, trans=trans).cpu().numpy()[:, 0]), H.bits(R[:, j])), j
         Xa, ena, eca, sta = ctx.gerfsx(dA, W, ipiv, bj, xj, trans=trans)
         assert _key(Xa.cpu().numpy(), ena, eca, sta, 0) == _key(*full, j), j
         assert np.array_equal(xj.cpu().numpy(), X0[:, j:j + 1].cpu().numpy()), "overwrite=False changed X"
@@ -218,8 +170,8 @@ def test_fp64_factors(ctx, kappa, seed, trans):
     B_np = np.random.default_rng(seed).uniform(-1, 1, (n, m))
     Minv = np.linalg.inv(Aop)
     Xh, Xl = G.reference_pair(Aop, B_np, lambda V: Minv @ V)
-    dA, W, ipiv = _factor(ctx, A)
-    B, _ = _dev(ctx, B_np)
+    dA, W, ipiv, _ = H.factor(ctx, A)
+    B, _ = H.dev(ctx, B_np)
     X = ctx.getrs(W, ipiv, B, trans=trans)
     rc, en, ec, st = _gerfsx(ctx, dA, W, ipiv, B, X, trans)
     e_norm, e_comp = G.errors(X.cpu().numpy(), Xh, Xl)
@@ -243,14 +195,14 @@ def lowp(ctx):
     n, m = 300, 5
     A = G.rand(n, 11)
     B_np = np.random.default_rng(3).uniform(-1, 1, (n, m))
-    dA, W, ipiv = _factor(ctx, A, trailing=1)
-    B, _ = _dev(ctx, B_np)
+    dA, W, ipiv, _ = H.factor(ctx, A, trailing=1)
+    B, _ = H.dev(ctx, B_np)
     LU, ip = ctx.to_numpy_f(W), ipiv.cpu().numpy()
     ref = {}
     for trans in (0, 1):
         Aop = np.ascontiguousarray(A.T if trans else A)
         Minv = np.linalg.inv(Aop)
-        ref[trans] = (Aop, G.reference_pair(Aop, B_np, lambda V: Minv @ V), _host_solvers(LU, ip, trans)[0])
+        ref[trans] = (Aop, G.reference_pair(Aop, B_np, lambda V: Minv @ V), H.host_solvers(LU, ip, trans)[0])
     return dA, W, ipiv, B, B_np, ref
 
 
@@ -289,8 +241,8 @@ def test_stops_without_convergence(ctx, trans):
     B_np = np.random.default_rng(5).uniform(-1, 1, (n, m))
     Minv = np.linalg.inv(Aop)
     Xh, Xl = G.reference_pair(Aop, B_np, lambda V: Minv @ V)
-    dA, W, ipiv = _factor(ctx, A, trailing=1)
-    B, _ = _dev(ctx, B_np)
+    dA, W, ipiv, _ = H.factor(ctx, A, trailing=1)
+    B, _ = H.dev(ctx, B_np)
     X = ctx.getrs(W, ipiv, B, trans=trans)
     rc, en, ec, st = _gerfsx(ctx, dA, W, ipiv, B, X, trans)
     X_np = X.cpu().numpy()
@@ -306,11 +258,11 @@ def test_edges(ctx):
     +Inf bounds) and leaves its neighbours' bits alone; N = 1."""
     n, m = 65, 35
     A = G.rand(n, 2)
-    dA, W, ipiv = _factor(ctx, A, nb=32)
+    dA, W, ipiv, _ = H.factor(ctx, A, nb=32)
     B_np = np.random.default_rng(6).uniform(-1, 1, (n, m))
     B_np[:, 4] = 0.0
     for trans in (0, 1):
-        B, _ = _dev(ctx, B_np)
+        B, _ = H.dev(ctx, B_np)
         X0 = ctx.getrs(W, ipiv, B, trans=trans)
         X, en, ec, st = ctx.gerfsx(dA, W, ipiv, B, X0, trans=trans)
         X_np = X.cpu().numpy()
@@ -319,7 +271,7 @@ def test_edges(ctx):
         assert st[4].final_dx_x == 0.0 and en[4] == lbnd and ec[4] == lbnd
         Bn_np = B_np.copy()
         Bn_np[7, 33] = np.nan
-        Bn, _ = _dev(ctx, Bn_np)
+        Bn, _ = H.dev(ctx, Bn_np)
         Xn0 = X0.clone()
         Xn0[:, 33] = ctx.getrs(W, ipiv, Bn[:, 33:34].contiguous(), trans=trans)[:, 0]
         rc, enn, ecn, stn = _gerfsx(ctx, dA, W, ipiv, Bn, Xn0, trans)
@@ -329,8 +281,8 @@ def test_edges(ctx):
             if j != 33:
                 assert _key(Xn_np, enn, ecn, stn, j) == _key(X_np, en, ec, st, j), j
     A1 = np.array([[0.75]])
-    dA1, W1, ipiv1 = _factor(ctx, A1, nb=32)
-    b1, _ = _dev(ctx, np.array([[1.0, -3.0, 1e-5]]))
+    dA1, W1, ipiv1, _ = H.factor(ctx, A1, nb=32)
+    b1, _ = H.dev(ctx, np.array([[1.0, -3.0, 1e-5]]))
     for trans in (0, 1):
         X, en, ec, st = ctx.gerfsx(dA1, W1, ipiv1, b1, ctx.getrs(W1, ipiv1, b1, trans=trans), trans=trans)
         want = np.array([[1.0, -3.0, 1e-5]]) / 0.75           # (a correction at 2^-53 or below is not applied: x may stay one ulp off)
@@ -345,10 +297,10 @@ def test_arguments(ctx, mpf):
     import torch
     n, ld = 64, 80
     A = G.rand(n, 9)
-    dA, W, ipiv = _factor(ctx, A)
-    B, Bbuf = _dev(ctx, np.ones((n, 2)), ld)
-    X, Xbuf = _dev(ctx, np.linalg.solve(A, np.ones((n, 2))), ld)
-    R, Rbuf = _dev(ctx, np.full((n, 2), FILL), ld)
+    dA, W, ipiv, _ = H.factor(ctx, A)
+    B, Bbuf = H.dev(ctx, np.ones((n, 2)), ld)
+    X, Xbuf = H.dev(ctx, np.linalg.solve(A, np.ones((n, 2))), ld)
+    R, Rbuf = H.dev(ctx, np.full((n, 2), FILL), ld)
     L, h = ctx.L, ctx.h
     p = lambda t: C.c_void_p(t.data_ptr())
     null = C.c_void_p(0)

@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import blk_helpers as H
 import gesvx_block_model as GB
 import lacn2_model as M
 
@@ -22,20 +23,6 @@ pytestmark = pytest.mark.gpu
 EPS = GB.EPS
 LD = np.longdouble
 NB = 128
-
-
-def _rand(n, seed, dominant=2.0):
-    A = np.random.default_rng(seed).uniform(-1, 1, (n, n))
-    A[np.arange(n), np.arange(n)] += dominant if n > 1 else 0.5
-    return np.asfortranarray(A)
-
-
-def _ill(n, kappa, seed):
-    rng = np.random.default_rng(seed)
-    U, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    V, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    s = np.logspace(0, -np.log10(kappa), n)
-    return np.asfortranarray((U * s) @ V.T)
 
 
 def _badly_scaled(n, seed):
@@ -49,27 +36,6 @@ def _rhs_of(A, trans, X):
     scales, the fp64 residual there is eps times that, and the 2-norm stop rule ||r|| <= tol ||b|| cannot be met on ANY factors;
     a B that is a product has |b| of the size of |op(A)| |x| row by row."""
     return np.asfortranarray((A.T if trans else A) @ X)
-
-
-def _dev(ctx, M_np, ld=None, fill=7.5):
-    """Column-major device copy of M with leading dimension ld (rows beyond N hold `fill`): (the N-row view, the whole buffer)."""
-    import torch
-    n, m = M_np.shape
-    buf = ctx.colmajor(ld or n, m)
-    buf.fill_(fill)
-    v = buf[:n]
-    v.copy_(torch.from_numpy(np.ascontiguousarray(M_np)))
-    return v, buf
-
-
-def _bits(a):
-    if hasattr(a, "cpu"):
-        a = a.cpu().numpy()
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
 
 
 def _raw(ctx, mpf, dA, n, nrhs, B, ldb, X, ldx, work, ipiv, trans=0, equilibrate=1, try_fp16=1, kappa_max=0.0, max_iter=10, tol=1e-12,
@@ -88,7 +54,7 @@ def _raw(ctx, mpf, dA, n, nrhs, B, ldb, X, ldx, work, ipiv, trans=0, equilibrate
 
 
 def _key(X, ferr, berr, ir, rfs, j):
-    return (_bits(X[:, j]).tolist(), _bits(ferr[j:j + 1])[0], _bits(berr[j:j + 1])[0], ir[j].iterations, ir[j].converged,
+    return (H.bits(X[:, j]).tolist(), H.bits(ferr[j:j + 1])[0], H.bits(berr[j:j + 1])[0], ir[j].iterations, ir[j].converged,
             rfs[j].iterations, rfs[j].lacn2_iterations)
 
 
@@ -99,22 +65,22 @@ def test_composition_is_factor_then_solve_ir_block_then_gerfs(ctx, mpf, n, nrhs,
     """equilibrate = 0, try_fp16 = 0: X, ferr, berr and the per-column counts are the bits of ctx.factor + solve_ir_block + gerfs, d_work
     and ipiv are ctx.factor's; bounds=False returns solve_ir_block's X untouched; the rows beyond N of B and X keep their sentinel."""
     import torch
-    A = _rand(n, 40 + n)
+    A = H.rand(n, 40 + n)
     B_np = np.random.default_rng(nrhs).uniform(-1, 1, (n, nrhs)) * np.logspace(-3, 3, nrhs)
     ld = n + 3
     dA = ctx.from_numpy_f(A)
     W = dA.clone()
     ipiv_ref, info = ctx.factor(W, NB)
     assert info == 0
-    B, Bbuf = _dev(ctx, B_np, ld)
+    B, Bbuf = H.dev(ctx, B_np, ld)
     X1, ist = ctx.solve_ir_block(dA, W, ipiv_ref, B, trans=trans)
     X2, ferr_ref, berr_ref, rst = ctx.gerfs(dA, W, ipiv_ref, B, X1, trans=trans)
-    X, Xbuf = _dev(ctx, np.zeros((n, nrhs)), ld)
+    X, Xbuf = H.dev(ctx, np.zeros((n, nrhs)), ld)
     work, ipiv = ctx.colmajor(n, n), torch.zeros(n, dtype=torch.int32, device=ctx.device)
     rc, ferr, berr, st, ir, rfs = _raw(ctx, mpf, dA, n, nrhs, B, ld, X, ld, work, ipiv, trans=trans, equilibrate=0, try_fp16=0)
     assert rc == 0 and st.path == 2 and st.equed == 0 and st.skipped_by_rcond == 0
     assert torch.equal(work, W) and torch.equal(ipiv, ipiv_ref)
-    assert _same(X, X2.view(n, nrhs)) and _same(ferr, ferr_ref) and _same(berr, berr_ref)
+    assert H.same(X, X2.view(n, nrhs)) and H.same(ferr, ferr_ref) and H.same(berr, berr_ref)
     for j in range(nrhs):
         assert (ir[j].iterations, ir[j].converged, ir[j].stalled) == (ist[j].iterations, ist[j].converged, ist[j].stalled), j
         assert ir[j].rel_residual == ist[j].rel_residual and ir[j].ms_total == ir[0].ms_total, j
@@ -123,10 +89,10 @@ def test_composition_is_factor_then_solve_ir_block_then_gerfs(ctx, mpf, n, nrhs,
     assert st.ir_final.rel_residual == ir[worst].rel_residual and st.ms_ir >= rfs[0].ms_total > 0
     assert bool((Xbuf[n:] == 7.5).all()) and bool((Bbuf[n:] == 7.5).all()), "padding rows were written"
     rc, _, _, st, ir, _ = _raw(ctx, mpf, dA, n, nrhs, B, ld, X, ld, work, ipiv, trans=trans, equilibrate=0, try_fp16=0, bounds=False)
-    assert rc == 0 and _same(X, X1.view(n, nrhs)), "without the bounds stage X is solve_ir_block's"
+    assert rc == 0 and H.same(X, X1.view(n, nrhs)), "without the bounds stage X is solve_ir_block's"
     Xw, fe, be, _, _, rs, _, _ = ctx.gesvx_block(dA, B[:, 0].contiguous() if nrhs == 1 else B, nb=NB, trans=trans, equilibrate=0, try_fp16=0,
                                                  bounds=False)
-    assert fe is None and be is None and rs is None and Xw.dim() == (1 if nrhs == 1 else 2) and _same(Xw.view(n, nrhs), X1.view(n, nrhs))
+    assert fe is None and be is None and rs is None and Xw.dim() == (1 if nrhs == 1 else 2) and H.same(Xw.view(n, nrhs), X1.view(n, nrhs))
 
 
 # ---- 2. row-scaling invariance: the scaled loads and stores ----------------------------------------------------------------------------
@@ -143,7 +109,7 @@ def test_row_scaling_invariance(ctx, n, nrhs, trans, try_fp16):
     factor 10 or more away from tol = 1e-12 on either side.  The per-column iteration counts are asserted equal first."""
     import torch
     rng = np.random.default_rng(7 * n + trans)
-    A0 = _rand(n, 60 + n, dominant=float(n) ** 0.5)
+    A0 = H.rand(n, 60 + n, dominant=float(n) ** 0.5)
     k = rng.integers(-20, 21, n)
     A = np.asfortranarray(np.ldexp(A0, -k[:, None]))
     B0 = rng.uniform(-1, 1, (n, nrhs)) * np.logspace(-3, 3, nrhs)
@@ -161,11 +127,11 @@ def test_row_scaling_invariance(ctx, n, nrhs, trans, try_fp16):
     assert np.array_equal(r.cpu().numpy(), np.ldexp(r0.cpu().numpy(), k)), "r(A) = Dr r(A0)"
     assert torch.equal(c, c0) and torch.equal(W, W0) and torch.equal(ip, ip0)
     assert st.rcond == st0.rcond and st.rcond_lowp == st0.rcond_lowp and st.anorm == st0.anorm
-    assert _same(berr, berr0)
+    assert H.same(berr, berr0)
     if trans:
-        assert _same(X, np.ldexp(X0.cpu().numpy(), k[:, None]))
+        assert H.same(X, np.ldexp(X0.cpu().numpy(), k[:, None]))
     else:
-        assert _same(X, X0) and _same(ferr, ferr0)
+        assert H.same(X, X0) and H.same(ferr, ferr0)
 
 
 # ---- 3. agreement with mpf_gesvx -----------------------------------------------------------------------------------------------------
@@ -175,7 +141,7 @@ def test_row_scaling_invariance(ctx, n, nrhs, trans, try_fp16):
 def test_same_decisions_and_factors_as_gesvx(ctx, kind, trans, try_fp16):
     import torch
     n, tol = 300, 1e-12
-    A = _badly_scaled(n, 4) if kind == "scaled" else _rand(n, 5, dominant=float(n) ** 0.5)
+    A = _badly_scaled(n, 4) if kind == "scaled" else H.rand(n, 5, dominant=float(n) ** 0.5)
     b_np = (A.T if trans else A) @ np.random.default_rng(8).uniform(-1, 1, n)     # (see _rhs_of: a b the stop rule can reach)
     dA, b = ctx.from_numpy_f(A), torch.from_numpy(b_np).to(ctx.device)
     x1, s1, W1, ip1 = ctx.gesvx(dA, b, nb=NB, trans=trans, try_fp16=try_fp16, tol=tol)
@@ -202,7 +168,7 @@ def test_column_independence(ctx, trans):
     import torch
     n, nrhs = 300, 33
     rng = np.random.default_rng(12)
-    A = np.asfortranarray(np.ldexp(_rand(n, 13, dominant=float(n) ** 0.5), rng.integers(-20, 21, n)[:, None]))
+    A = np.asfortranarray(np.ldexp(H.rand(n, 13, dominant=float(n) ** 0.5), rng.integers(-20, 21, n)[:, None]))
     B_np = _rhs_of(A, trans, rng.uniform(-1, 1, (n, nrhs)) * np.logspace(-3, 3, nrhs))
     dA = ctx.from_numpy_f(A)
     kw = dict(nb=NB, trans=trans, try_fp16=1, itmax=10)
@@ -227,9 +193,9 @@ def test_column_independence(ctx, trans):
 def test_ill_conditioned_goes_to_fp64_without_refining(ctx, mpf):
     import torch
     n, nrhs = 300, 33
-    A = _ill(n, 1e8, 7)
+    A = H.ill(n, 1e8, 7)
     B_np = _rhs_of(A, 0, np.random.default_rng(7).uniform(-1, 1, (n, nrhs)))     # (a random B has ||x|| ~ kappa ||b|| / ||A||: no 1e-12)
-    dA, (B, _), (X, _) = ctx.from_numpy_f(A), _dev(ctx, B_np), _dev(ctx, np.zeros((n, nrhs)))
+    dA, (B, _), (X, _) = ctx.from_numpy_f(A), H.dev(ctx, B_np), H.dev(ctx, np.zeros((n, nrhs)))
     work, ipiv = ctx.colmajor(n, n), torch.zeros(n, dtype=torch.int32, device=ctx.device)
     rc, ferr, berr, st, ir, rfs = _raw(ctx, mpf, dA, n, nrhs, B, n, X, n, work, ipiv, try_fp16=1)
     print("rcond_lowp", st.rcond_lowp, "rcond", st.rcond, "ferr max", ferr.max(), "berr/eps", berr.max() / EPS)
@@ -243,9 +209,9 @@ def test_fallback_rule(ctx, mpf, kappa):
     did not converge the call is on path 2 (all columns solved again on fp64 factors); on path 1 every column converged."""
     import torch
     n, nrhs = 300, 33
-    A = _ill(n, kappa, 8)
+    A = H.ill(n, kappa, 8)
     B_np = np.random.default_rng(9).uniform(-1, 1, (n, nrhs))
-    dA, (B, _), (X, _) = ctx.from_numpy_f(A), _dev(ctx, B_np), _dev(ctx, np.zeros((n, nrhs)))
+    dA, (B, _), (X, _) = ctx.from_numpy_f(A), H.dev(ctx, B_np), H.dev(ctx, np.zeros((n, nrhs)))
     work, ipiv = ctx.colmajor(n, n), torch.zeros(n, dtype=torch.int32, device=ctx.device)
     rc, ferr, berr, st, ir, rfs = _raw(ctx, mpf, dA, n, nrhs, B, n, X, n, work, ipiv, try_fp16=1, kappa_max=1e7, max_iter=1)
     print("kappa", kappa, "1/rcond_lowp", 1 / st.rcond_lowp, "lowp worst", st.ir_lowp.rel_residual, st.ir_lowp.converged, "path", st.path, "rc", rc)
@@ -290,10 +256,10 @@ def test_arguments(ctx, mpf):
     without berr -> -1; a null pointer -> -1."""
     import torch
     n, ld = 64, 80
-    A = _rand(n, 9)
+    A = H.rand(n, 9)
     dA = ctx.from_numpy_f(A)
-    B, Bbuf = _dev(ctx, np.ones((n, 2)), ld)
-    X, Xbuf = _dev(ctx, np.zeros((n, 2)), ld)
+    B, Bbuf = H.dev(ctx, np.ones((n, 2)), ld)
+    X, Xbuf = H.dev(ctx, np.zeros((n, 2)), ld)
     work = ctx.colmajor(n, n)
     work.fill_(3.25)
     ipiv = torch.zeros(n, dtype=torch.int32, device=ctx.device)

@@ -4,35 +4,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import blk_helpers as H
+
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(np.float64).eps
 IRS = ("iterations", "converged", "rel_residual", "stalled")
 
 
-def _rand(n, seed, dominant=2.0):
-    A = np.random.default_rng(seed).uniform(-1, 1, (n, n))
-    A[np.arange(n), np.arange(n)] += dominant if n > 1 else 0.5
-    return np.asfortranarray(A)
-
-
-def _factor(ctx, A_np, ld=None, nb=128, trailing=0):
-    """Device copy of A and its factors (LU stored with leading dimension ld)."""
-    n = A_np.shape[0]
-    dA = ctx.from_numpy_f(A_np)
-    buf = ctx.colmajor(ld or n, n)
-    W = buf[:n]
-    W.copy_(dA)
-    ipiv, info = ctx.factor(W, nb, trailing=trailing)
-    ctx.synchronize()
-    return dA, W, ipiv, info
-
-
 def _kappa(A):
     return np.linalg.norm(A, 1) * np.linalg.norm(np.linalg.inv(A), 1)
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint64)
 
 
 def _st(s):
@@ -45,8 +25,8 @@ def test_getrs_accuracy(ctx, n, trans):
     """getrs of fp64 factors is within 10 N kappa eps of numpy for every column; rows beyond N of B stay untouched."""
     import torch
     ld = 800 if n == 777 else n
-    A = _rand(n, 300 + n)
-    dA, W, ipiv, info = _factor(ctx, A, ld=ld)
+    A = H.rand(n, 300 + n)
+    dA, W, ipiv, info = H.factor(ctx, A, ld=ld)
     assert info == 0
     kappa = _kappa(A)
     Aop = A.T if trans else A
@@ -66,12 +46,31 @@ def test_getrs_accuracy(ctx, n, trans):
             assert bool((buf[n:] == 7.5).all()), "padding rows of B were written"
 
 
+@pytest.mark.parametrize("trans", [0, 1])
+def test_getrs_group_seam(ctx, trans):
+    """513 right-hand sides are two groups (512 + 1 columns): the columns at the tile seam (31, 32) and at the group seam (511, 512)
+    have the bits of the same column solved alone, and with ldb = N + 3 the rows beyond N of B stay untouched."""
+    import torch
+    n, nrhs, ldb = 64, 513, 67
+    dA, W, ipiv, _ = H.factor(ctx, H.rand(n, 17), nb=32)
+    B_np = np.random.default_rng(8).uniform(-1, 1, (n, nrhs))
+    B, buf = H.dev(ctx, B_np, ldb)
+    X = ctx.getrs(W, ipiv, B, trans=trans, overwrite=True)
+    ctx.synchronize()
+    assert X.data_ptr() == B.data_ptr()
+    assert bool((buf[n:] == 7.5).all()), "padding rows of B were written"
+    for j in (0, 31, 32, 511, 512):
+        bj = torch.from_numpy(B_np[:, j:j + 1].copy()).to(ctx.device)
+        x1 = ctx.getrs(W, ipiv, bj, trans=trans)
+        assert np.array_equal(H.tensor_bits(x1)[:, 0], H.tensor_bits(X)[:, j]), j
+
+
 def test_getrs_keeps_b(ctx):
     """Without overwrite, getrs returns a new X and leaves B as it was."""
     import torch
     n = 300
-    A = _rand(n, 5)
-    dA, W, ipiv, _ = _factor(ctx, A)
+    A = H.rand(n, 5)
+    dA, W, ipiv, _ = H.factor(ctx, A, check=False)
     B = torch.from_numpy(np.random.default_rng(1).uniform(-1, 1, (n, 3))).to(ctx.device)
     B0 = B.clone()
     X = ctx.getrs(W, ipiv, B)
@@ -85,8 +84,8 @@ def test_getrs_agrees_with_column_solves(ctx, trans):
     """N = 8192, 64 columns: getrs agrees with solve_ir_nrhs / solve_ir_trans at max_iter = 0 within 10 N kappa eps."""
     import torch
     n, nrhs = 8192, 64
-    A = _rand(n, 77, dominant=float(n) ** 0.5)
-    dA, W, ipiv, info = _factor(ctx, A, nb=256)
+    A = H.rand(n, 77, dominant=float(n) ** 0.5)
+    dA, W, ipiv, info = H.factor(ctx, A, nb=256)
     assert info == 0
     B = torch.from_numpy(np.random.default_rng(2).uniform(-1, 1, (n, nrhs))).to(ctx.device).t().contiguous().t()
     X = ctx.getrs(W, ipiv, B, trans=trans).cpu().numpy()
@@ -106,8 +105,8 @@ def test_column_independence(ctx, trans):
     For getrs and for solve_ir_block (X and every stats field but ms_total)."""
     import torch
     n, nrhs = 1000, 37
-    A = _rand(n, 11)
-    dA, W16, ipiv16, _ = _factor(ctx, A, trailing=1)
+    A = H.rand(n, 11)
+    dA, W16, ipiv16, _ = H.factor(ctx, A, trailing=1, check=False)
     B = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, (n, nrhs)) * np.logspace(-3, 3, nrhs)).to(ctx.device)
     B = B.t().contiguous().t()
     perm = np.random.default_rng(4).permutation(nrhs)
@@ -115,22 +114,22 @@ def test_column_independence(ctx, trans):
     X = ctx.getrs(W16, ipiv16, B, trans=trans)
     Xr = ctx.getrs(W16, ipiv16, B, trans=trans)
     Xp = ctx.getrs(W16, ipiv16, Bp, trans=trans)
-    assert np.array_equal(_bits(X), _bits(Xr))
+    assert np.array_equal(H.tensor_bits(X), H.tensor_bits(Xr))
     Y, S = ctx.solve_ir_block(dA, W16, ipiv16, B, trans=trans, max_iter=10, tol=1e-12)
     Yr, Sr = ctx.solve_ir_block(dA, W16, ipiv16, B, trans=trans, max_iter=10, tol=1e-12)
     Yp, Sp = ctx.solve_ir_block(dA, W16, ipiv16, Bp, trans=trans, max_iter=10, tol=1e-12)
-    assert np.array_equal(_bits(Y), _bits(Yr))
+    assert np.array_equal(H.tensor_bits(Y), H.tensor_bits(Yr))
     assert [_st(s) for s in S] == [_st(s) for s in Sr]
     assert all(s.ms_total == S[0].ms_total for s in S)
     where = {int(j): i for i, j in enumerate(perm)}
     for j in (0, 16, 36):
         bj = B[:, j:j + 1].contiguous()
         x1 = ctx.getrs(W16, ipiv16, bj, trans=trans)
-        assert np.array_equal(_bits(x1)[:, 0], _bits(X)[:, j]), j
-        assert np.array_equal(_bits(Xp)[:, where[j]], _bits(X)[:, j]), j
+        assert np.array_equal(H.tensor_bits(x1)[:, 0], H.tensor_bits(X)[:, j]), j
+        assert np.array_equal(H.tensor_bits(Xp)[:, where[j]], H.tensor_bits(X)[:, j]), j
         y1, s1 = ctx.solve_ir_block(dA, W16, ipiv16, bj, trans=trans, max_iter=10, tol=1e-12)
-        assert np.array_equal(_bits(y1)[:, 0], _bits(Y)[:, j]), j
-        assert np.array_equal(_bits(Yp)[:, where[j]], _bits(Y)[:, j]), j
+        assert np.array_equal(H.tensor_bits(y1)[:, 0], H.tensor_bits(Y)[:, j]), j
+        assert np.array_equal(H.tensor_bits(Yp)[:, where[j]], H.tensor_bits(Y)[:, j]), j
         assert _st(s1[0]) == _st(S[j]) == _st(Sp[where[j]]), j
 
 
@@ -140,8 +139,8 @@ def test_block_refinement_fp16(ctx, trans):
     converges to 1e-12, the numpy residual is <= 1e-11 ||b||, iteration counts are within 1 of the per-column solve's."""
     import torch
     n, nrhs = 4096, 40
-    A = _rand(n, 21, dominant=float(n) ** 0.5)
-    dA, W, ipiv, info = _factor(ctx, A, nb=256, trailing=1)
+    A = H.rand(n, 21, dominant=float(n) ** 0.5)
+    dA, W, ipiv, info = H.factor(ctx, A, nb=256, trailing=1)
     assert info == 0
     B_np = np.random.default_rng(5).uniform(-1, 1, (n, nrhs)) * np.logspace(-6, 6, nrhs)
     B_np[:, 7] = 0.0
@@ -161,14 +160,6 @@ def test_block_refinement_fp16(ctx, trans):
     assert not Xn[:, 7].any() and S[7].converged == 1
 
 
-def _ill(n, kappa, seed):
-    rng = np.random.default_rng(seed)
-    U, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    V, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    s = np.logspace(0, -np.log10(kappa), n)
-    return np.asfortranarray((U * s) @ V.T)
-
-
 def _stopped_as_ir_core(s, max_iter):
     h = s.history[s.iterations]
     return s.stalled == 1 or s.iterations == max_iter or h != h
@@ -180,8 +171,8 @@ def test_block_refinement_ill_conditioned(ctx, trans):
     is finite up to the stop wherever the per-column solve's is."""
     import torch
     n, nrhs, mi = 1024, 8, 10
-    A = _ill(n, 1e9, 31)
-    dA, W, ipiv, _ = _factor(ctx, A, nb=256, trailing=1)
+    A = H.ill(n, 1e9, 31)
+    dA, W, ipiv, _ = H.factor(ctx, A, nb=256, trailing=1, check=False)
     B = torch.from_numpy(np.random.default_rng(6).uniform(-1, 1, (n, nrhs))).to(ctx.device).t().contiguous().t()
     X, S = ctx.solve_ir_block(dA, W, ipiv, B, trans=trans, max_iter=mi, tol=1e-12)
     if trans:
@@ -200,8 +191,8 @@ def test_arguments(ctx, mpf):
     """nrhs = 0 -> 0; N <= 0, ldb / ldx / ldlu < N -> -1 with the error set; a bad ipiv entry -> -1."""
     import torch
     n = 64
-    A = _rand(n, 9)
-    dA, W, ipiv, _ = _factor(ctx, A)
+    A = H.rand(n, 9)
+    dA, W, ipiv, _ = H.factor(ctx, A, check=False)
     B = ctx.from_numpy_f(np.ones((n, 2)))
     X = ctx.colmajor(n, 2)
     L, h = ctx.L, ctx.h

@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import blk_helpers as H
 import gmres_block_model as G
 
 pytestmark = pytest.mark.gpu
@@ -30,27 +31,11 @@ KAPPA = {33: 1e6, 300: 1e5}
 SHAPES = [(33, 5), (300, 5), (300, 33)]
 
 
-def _rand(n, seed, dominant=2.0):
-    A = np.random.default_rng(seed).uniform(-1, 1, (n, n))
-    A[np.arange(n), np.arange(n)] += dominant if n > 1 else 0.5
-    return np.asfortranarray(A)
-
-
-def _bits(a):
-    if hasattr(a, "cpu"):
-        a = a.cpu().numpy()
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
 def _key(X, st, j):
     """Everything of column j that must not depend on its neighbours."""
     s = st[j]
-    return (_bits(X[:, j]).tolist(), _bits(np.array(s.history[:s.outer_iterations + 1])).tolist(), s.outer_iterations,
-            s.inner_iterations, s.converged, _bits(np.array([s.rel_residual]))[0])
+    return (H.bits(X[:, j]).tolist(), H.bits(np.array(s.history[:s.outer_iterations + 1])).tolist(), s.outer_iterations,
+            s.inner_iterations, s.converged, H.bits(np.array([s.rel_residual]))[0])
 
 
 _cache = {}
@@ -201,7 +186,7 @@ def test_returns_1_when_a_column_does_not_converge(ctx, trans):
 # ---- 5. edges ------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nrhs", [1, 33])
 def test_n_equals_1(ctx, nrhs):
-    A = _rand(1, 3)
+    A = H.rand(1, 3)
     dA = ctx.from_numpy_f(A)
     W = dA.clone()
     ipiv, info = ctx.factor(W, NB, trailing=0)
@@ -237,7 +222,7 @@ def test_arguments_and_padding(ctx, mpf):
     assert torch.equal(bufB, B0), "B was changed"
     assert bool((bufX[n:] == -3.25).all()), "rows beyond N of X were written"
     rc, X, st0 = _solve(ctx, n, nrhs, 0)
-    assert _same(bufX[:n], X), "a padded leading dimension changed the result"
+    assert H.same(bufX[:n], X), "a padded leading dimension changed the result"
     for args in ((2, n, n, nrhs, p(bufB), n + 3, p(bufX), n + 3), (0, n - 1, n, nrhs, p(bufB), n + 3, p(bufX), n + 3),
                  (0, n, n - 1, nrhs, p(bufB), n + 3, p(bufX), n + 3), (0, n, n, nrhs, p(bufB), n - 1, p(bufX), n + 3),
                  (0, n, n, nrhs, p(bufB), n + 3, p(bufX), n - 1), (0, n, n, nrhs, None, n + 3, p(bufX), n + 3),
@@ -267,7 +252,7 @@ def test_restart_is_clamped(ctx):
 
 @pytest.mark.parametrize("n,nrhs", [(33, 5), (300, 33)])
 def test_exact_factors_converge_at_once(ctx, n, nrhs):
-    A = _rand(n, 11)
+    A = H.rand(n, 11)
     dA = ctx.from_numpy_f(A)
     W = dA.clone()
     ipiv, info = ctx.factor(W, NB, trailing=0)
