@@ -506,8 +506,8 @@ int mpf_residual_x(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, 
  * read-back and one masked update per step; a column that has stopped is frozen.  A column's arithmetic depends on nothing but its own
  * data: X[:, j], both bounds and the stats (but ms_total) have the same bits whatever the other columns, nrhs, j's position or the
  * group, and two calls return the same bits.
- * What it is not: it computes no berr (mpf_gerfs does), keeps no doubled-precision x (LAPACK's last escalation stage), takes no scale
- * vectors and is not wired into mpf_gesvx_block or mpf_gesv.
+ * What it is not: it keeps no doubled-precision x (LAPACK's last escalation stage) and is not wired into mpf_gesvx_block or mpf_gesv;
+ * berr and scale vectors are mpf_gerfsx_scaled's, the driver around both is mpf_gesvxx_block (below).
  * Returns 0 when every column ended with x_state = CONV, 1 otherwise (the stats say which), < 0 on error.  nrhs = 0: returns 0, no
  * work.  Rows N .. ldx - 1 of d_X are not touched; d_B is preserved.  Synchronises; -4 as the other solves. */
 typedef struct mpf_gerfsx_stats {
@@ -554,6 +554,79 @@ int mpf_gesvx_block(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t N, int
                     double *ferr, double *berr,             /* host, nrhs each; both NULL: no bounds stage */
                     mpf_gesvx_stats *stats,                 /* the call: path, equed, rcond, rcond_lowp, times */
                     mpf_ir_stats *ir, mpf_gerfs_stats *rfs  /* host, nrhs each, optional */);
+
+/* ---- extra-precise expert solve (build extension; LAPACK dgesvxx's driver, dla_gerpvgrw and dgerfsx on equilibrated factors) ---------
+ * Three entry points; the third is a composition of public operators, so that it can be compared bit for bit with them. */
+
+/* Reciprocal pivot growth, LAPACK dla_gerpvgrw: d_LU (N x N, ldlu >= N) holds the factors of Dr A Dc, d_r / d_c (device, N doubles each,
+ * optional) the diagonals of Dr / Dc; NULL means the identity.  Per column j
+ *   amax_j = max_i (|a_ij| r_i) c_j,   umax_j = max_{i <= j} |u_ij|,
+ *   *rpvgrw = min(1, min over the j with umax_j != 0 of amax_j / umax_j)          (the initial value 1 is LAPACK's).
+ * A value well below 1 says that the factorization grew: the default pivot rule takes its pivots from an fp16 image and
+ * pivot_search = 2 does not promise |l_ij| <= 1, so neither bounds the growth by itself.  A NaN in A's or U's part of a column makes the
+ * result NaN.  Maxima have no order to fix and the quotient is one division: the result equals the formula above evaluated in fp64 in
+ * any order, and two calls return the same bits.  One pass over A and half a pass over LU: 8 N^2 + 4 N (N + 1) bytes (12.9 GB at
+ * N = 32768), each column read once, coalesced.  *rpvgrw on the host.  Returns 0, < 0 on error.  Synchronises. */
+int mpf_gerpvgrw(mpf_ctx *ctx, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N,
+                 const double *d_r, const double *d_c /* device, N each, optional */, double *rpvgrw /* host */);
+
+/* mpf_gerfsx on the factors of an equilibrated copy, with berr.  d_LU / d_ipiv are the factors of Dr A Dc (d_r, d_c: device, N doubles
+ * each, exact powers of two as mpf_geequ returns them; NULL: the identity).  The rule, the three measures and the residual are
+ * mpf_gerfsx's, taken on the ORIGINAL A, B and X; only the correction changes:
+ *   d = Dc (L U)^-1 P Dr r      (trans = 1:  d = Dr P^T (L U)^-T Dc r),
+ * the scale vectors riding on the tile loads and stores of the solve as in mpf_gesvx_block, so a correction costs what mpf_getrs costs.
+ * err_norm and err_comp (host, nrhs each, required) therefore bound the error of the caller's X in the original system.
+ * berr (host, nrhs doubles, optional): the componentwise backward error of the X that is returned, taken once after the loop:
+ *   r = b - op(A) x as mpf_residual_x forms it (one more pair residual), w = |b| + |op(A)| |x| from mpf_gerfs's fp64 MFMA pass,
+ *   berr = max_i (w_i > safe2 ? |r_i| / w_i : (|r_i| + safe1) / (w_i + safe1)),  safe1 = (N + 1) DBL_MIN, safe2 = safe1 / 2^-53
+ * (mpf_gerfs's quotient and constants); a NaN is kept.  It is within (N + 2) 2^-53 relative + 8 (N + 1) 2^-106 of the exact quotient
+ * (w is a sum of N + 1 non-negative terms; r has the pair residual's error).  The cost is one pair residual and one MFMA pass per group
+ * of 512 columns, after the loop only; with berr NULL neither runs.
+ * With d_r, d_c and berr all NULL the call returns mpf_gerfsx's bits in X, both bounds and the stats.  Column independence as
+ * mpf_gerfsx: X[:, j], both bounds, berr[j] and the stats (but ms_total) have the same bits whatever stands beside column j and at any
+ * position.  Return value, nrhs = 0, ithresh, stats and the untouched rows as mpf_gerfsx.  Synchronises; -4 as the other solves. */
+int mpf_gerfsx_scaled(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu,
+                      const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                      int32_t ithresh, const double *d_r, const double *d_c,   /* device, optional: LU = factors of Dr A Dc */
+                      double *err_norm, double *err_comp, double *berr /* host, nrhs, optional */, mpf_gerfsx_stats *stats);
+
+/* The extra-precise expert driver for many right-hand sides (LAPACK dgesvxx's shape): mpf_gesvx_block with mpf_gerfsx's refinement and
+ * bounds in place of dgerfs's, and the pivot growth.
+ *   Steps 1 .. 4 are mpf_gesvx's / mpf_gesvx_block's, from the same code: equilibrate, factor d_work in the mode try_fp16 asks for
+ *   (option pivot_fp64 applies as there), rcond of those factors, the kappa_max gate.  For the same A and arguments equed, rcond_lowp,
+ *   skipped_by_rcond, anorm, the scale vectors and the low-precision factors are theirs, bit for bit.
+ *   One attempt on the factors in d_work has two stages:
+ *     (a) mpf_solve_ir_block's refinement (x0 from the factors, the fp64 MFMA residual, max_iter, tol, the stall rule), exactly as
+ *         mpf_gesvx_block's step 5.  Its `converged` flags decide nothing here: the stage is a warm start that takes the cheap steps
+ *         with the cheap residual (several times cheaper than the pair residual).
+ *     (b) mpf_gerfsx_scaled's loop (ithresh, a fresh rule state, berr when asked) on that X, with the same scale vectors.
+ *   The attempt stands iff EVERY column ends stage (b) with x_state = CONV.  A low-precision attempt that does not stand sends ALL
+ *   columns to fp64 factors of the same equilibrated matrix (path = 2), for mpf_gesvx_block's reason: a column's bits depend on A, on
+ *   its own b and on the path only.  There is no per-column fall-back.
+ * With equilibrate = 0 and try_fp16 = 0 the call returns, bit for bit, mpf_factor_dev, then mpf_solve_ir_block, then mpf_gerfsx_scaled
+ * with NULL scales; with scales the same holds with the driver's d_r / d_c and the factors it leaves in d_work.
+ * err_norm, err_comp (host, nrhs each, required), berr (host, nrhs, optional): mpf_gerfsx_scaled's, of the ORIGINAL system and the
+ * caller's X (the argument of mpf_gesvx_block's step 7 holds: the scale factors are exact powers of two).  rpvgrw (host, one double,
+ * optional): mpf_gerpvgrw on A, the factors in d_work and the scales equed says were applied.  stats as mpf_gesvx_block's: ir_lowp /
+ * ir_final hold the worst column of stage (a) of the respective attempt, ms_ir includes stage (b).  ir, xr (host, nrhs each, optional):
+ * the per-column stats of stages (a) and (b) of the attempt that produced X; ir[j].ms_total is the attempt's time, xr[j].ms_total
+ * stage (b)'s.  d_A, d_B, d_work, d_ipiv, d_r, d_c, the untouched rows of d_X and the argument checks as mpf_gesvx_block.
+ * The measures are taken on the caller's x = post .* y (y: the equilibrated system's solution).  The blocked solves are stable normwise
+ * in y, not per component, so with scale vectors spread over many orders of magnitude the loop contracts to 2^-53 where x's large
+ * components are those with a large scale (a solution that follows the column scaling) and ends NOPROG, return value 1, where a
+ * solution of uniform size meets such scales (measured: errors of 3 .. 16 x 2^-53 at a spread of 2^60).
+ * What it is not: no Skeel condition numbers and no trust flags (dgesvxx's err_bnds(:, 1) and (:, 3)); no doubled-precision x (on a
+ * host model of LAPACK's y_tail stage it changed no final state and no error by more than one ulp up to kappa = 3e15); no per-column
+ * fall-back; not used by mpf_gesv or the distributed path.
+ * Returns 0 when every column ended with x_state = CONV, 1 otherwise (xr says which), < 0 on error; nrhs = 0 returns 0 and does no
+ * work, not even the factorization.  Synchronises. */
+int mpf_gesvxx_block(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t N, int32_t nb, double *d_work, int32_t *d_ipiv,
+                     int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                     int32_t trans, int32_t equilibrate, int32_t try_fp16, double kappa_max, int32_t max_iter, double tol,
+                     int32_t ithresh, double *d_r, double *d_c,
+                     double *err_norm, double *err_comp,   /* host, nrhs each, required */
+                     double *berr, double *rpvgrw,         /* host, nrhs / 1, optional */
+                     mpf_gesvx_stats *stats, mpf_ir_stats *ir, mpf_gerfsx_stats *xr /* host, optional */);
 
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block

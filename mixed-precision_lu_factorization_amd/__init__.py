@@ -35,6 +35,7 @@ C_ABI_SYMBOLS = [
     "mpf_getrs", "mpf_solve_ir_block", "mpf_gerfs", "mpf_gesvx_block",
     "mpf_dgetf2_piv", "mpf_solve_gmres_ir_block", "mpf_dgetf2_tp",
     "mpf_residual_x", "mpf_gerfsx",
+    "mpf_gerpvgrw", "mpf_gerfsx_scaled", "mpf_gesvxx_block",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -193,6 +194,12 @@ def load_library(probe=False):
                              C.POINTER(MpfGerfsxStats)]
     L.mpf_gesvx_block.argtypes = [vp, vp, i64, i64, i32, vp, vp, i32, vp, i64, vp, i64, i32, i32, i32, dbl, i32, dbl, i32, vp, vp,
                                   C.POINTER(dbl), C.POINTER(dbl), C.POINTER(MpfGesvxStats), C.POINTER(MpfIrStats), C.POINTER(MpfGerfsStats)]
+    L.mpf_gerpvgrw.argtypes = [vp, vp, i64, vp, i64, i64, vp, vp, C.POINTER(dbl)]
+    L.mpf_gerfsx_scaled.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, C.POINTER(dbl), C.POINTER(dbl),
+                                    C.POINTER(dbl), C.POINTER(MpfGerfsxStats)]
+    L.mpf_gesvxx_block.argtypes = [vp, vp, i64, i64, i32, vp, vp, i32, vp, i64, vp, i64, i32, i32, i32, dbl, i32, dbl, i32, vp, vp,
+                                   C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(MpfGesvxStats),
+                                   C.POINTER(MpfIrStats), C.POINTER(MpfGerfsxStats)]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -383,7 +390,7 @@ class MPFContext:
                no_lookahead=False, superpanel=0, pivot_path=0, pivot_search=0):
         """mpf_factor_dev: in-place MPF of the column-major device matrix A (N x N).
         pivot_search: 0 = the reference's fp16 pre-pivoting, 1 = LAPACK's partial pivoting, searched in fp64, 2 = tournament pivoting
-        in fp64 (mpf_dgetf2_tp's rule); also context option pivot_fp64 = 1 or 2, which gesv, gesvx, gesvx_block and factor_host follow.
+        in fp64 (mpf_dgetf2_tp's rule); also context option pivot_fp64 = 1 or 2, which gesv, gesvx, gesvx_block, gesvxx_block and factor_host follow.
         Returns (ipiv int32 device tensor, info)."""
         self._bind()
         t = self.torch
@@ -871,4 +878,66 @@ class MPFContext:
         self._check(rc, "mpf_gesvx_block")
         out = (X, ferr[:nrhs] if bounds else None, berr[:nrhs] if bounds else None, st, list(ist)[:nrhs],
                list(rst)[:nrhs] if bounds else None, work, ipiv)
+        return out + (r, c) if want_scales else out
+
+    # ---- extra-precise expert solve (include/mpf_c.h: mpf_gerpvgrw, mpf_gerfsx_scaled, mpf_gesvxx_block) --------------------------------
+    def gerpvgrw(self, A, LU, r=None, c=None):
+        """mpf_gerpvgrw (LAPACK dla_gerpvgrw): the reciprocal pivot growth min(1, min_j max_i |a_ij r_i c_j| / max_{i <= j} |u_ij|) of
+        the factors LU of Dr A Dc; r, c: the scale vectors as device tensors, or None for the identity.  Returns a float."""
+        self._bind()
+        out = C.c_double(0)
+        rc = self.L.mpf_gerpvgrw(self.h, _ptr(A), _colmajor_ld(A), _ptr(LU), _colmajor_ld(LU), A.shape[0], _ptr(r), _ptr(c), C.byref(out))
+        self._check(rc, "mpf_gerpvgrw")
+        return out.value
+
+    def gerfsx_scaled(self, A, LU, ipiv, B, X, trans=False, ithresh=0, r=None, c=None, want_berr=True, overwrite=False):
+        """mpf_gerfsx_scaled: gerfsx with LU the factors of Dr A Dc (r, c: device tensors or None) and, with want_berr, the componentwise
+        backward error of the returned X.  Returns (X, err_norm, err_comp, berr, stats); berr is None without want_berr.  X, B and
+        overwrite as gerfsx."""
+        import numpy as np
+        self._bind()
+        n = A.shape[0]
+        Xr = self._inout(n, X, overwrite)
+        _, nrhs, ldb = self._rhs(B)
+        _, nx, ldx = self._rhs(Xr)
+        assert nx == nrhs, "gerfsx_scaled: B and X need the same number of columns"
+        en, ec, be = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+        st = (MpfGerfsxStats * max(nrhs, 1))()
+        dp = C.POINTER(C.c_double)
+        rc = self.L.mpf_gerfsx_scaled(self.h, int(bool(trans)), _ptr(A), _colmajor_ld(A), _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n, nrhs,
+                                      _ptr(B), ldb, _ptr(Xr), ldx, int(ithresh), _ptr(r), _ptr(c), en.ctypes.data_as(dp),
+                                      ec.ctypes.data_as(dp), be.ctypes.data_as(dp) if want_berr else None, st)
+        self._check(rc, "mpf_gerfsx_scaled")
+        return Xr, en[:nrhs], ec[:nrhs], be[:nrhs] if want_berr else None, list(st)[:nrhs]
+
+    def gesvxx_block(self, A, B, nb=256, trans=False, equilibrate=1, try_fp16=1, kappa_max=0.0, max_iter=10, tol=1e-12, ithresh=0,
+                     want_berr=True, want_rpvgrw=True, work=None, want_scales=False):
+        """mpf_gesvxx_block: gesvx_block's steps with the extra-precise refinement after the plain one, gerfsx's two forward error
+        bounds of the original system, berr and the reciprocal pivot growth.  Returns (X, err_norm, err_comp, berr, rpvgrw, stats,
+        ir_stats, gerfsx_stats, work, ipiv) and, with want_scales, (r, c) as well; berr / rpvgrw are None when not asked for.  X is a
+        vector when B is.  A column that did not converge does not raise: gerfsx_stats say so (x_state 2 = converged)."""
+        import numpy as np
+        self._bind()
+        t = self.torch
+        n = A.shape[0]
+        _, nrhs, ldb = self._rhs(B)
+        if work is None:
+            work = self.colmajor(n, n)
+        ipiv = t.empty(n, dtype=t.int32, device=self.device)
+        X, ldx = self._out_like(n, B)
+        r = t.empty(n, dtype=t.float64, device=self.device) if want_scales else None
+        c = t.empty(n, dtype=t.float64, device=self.device) if want_scales else None
+        st = MpfGesvxStats()
+        ist = (MpfIrStats * max(nrhs, 1))()
+        xst = (MpfGerfsxStats * max(nrhs, 1))()
+        dp = C.POINTER(C.c_double)
+        en, ec, be = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+        pg = C.c_double(0)
+        rc = self.L.mpf_gesvxx_block(self.h, _ptr(A), _colmajor_ld(A), n, nb, _ptr(work), _ptr(ipiv), nrhs, _ptr(B), ldb, _ptr(X), ldx,
+                                     int(bool(trans)), int(equilibrate), int(try_fp16), float(kappa_max), max_iter, tol, int(ithresh),
+                                     _ptr(r), _ptr(c), en.ctypes.data_as(dp), ec.ctypes.data_as(dp),
+                                     be.ctypes.data_as(dp) if want_berr else None, C.byref(pg) if want_rpvgrw else None, C.byref(st), ist, xst)
+        self._check(rc, "mpf_gesvxx_block")
+        out = (X, en[:nrhs], ec[:nrhs], be[:nrhs] if want_berr else None, pg.value if want_rpvgrw else None, st, list(ist)[:nrhs],
+               list(xst)[:nrhs], work, ipiv)
         return out + (r, c) if want_scales else out

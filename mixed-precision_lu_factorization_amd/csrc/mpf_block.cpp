@@ -4,9 +4,11 @@
 //   mpf_gerfs            LAPACK dgerfs: refinement by the componentwise backward error, berr and the forward bound ferr per column
 //   mpf_solve_gmres_ir_block   GMRES-IR (mpf_solve_gmres_ir's method) on all columns of a group in lock-step, op(A) = A or A^T
 //   mpf_residual_x, mpf_gerfsx   LAPACK dgerfsx: the residual in pairs of doubles, refinement steered by the corrections' size
+//   mpf_gerfsx_scaled    the same on the factors of an equilibrated copy Dr A Dc, with dgerfs's berr of the returned X
 // Each of the four refinements is a core (blk_refine_core, blk_bounds_core, blk_xrefine_core, blk_gmres_core) on a system (BlkSys:
 // A, its prepared factors, optional scale vectors for the factors of an equilibrated copy Dr A Dc) and its right-hand sides (BlkRhs);
-// mpf_gesvx_block (mpf_expert.cpp) calls the first two with its scales, the public functions here with none, through solve_entry.
+// mpf_gesvx_block and mpf_gesvxx_block (mpf_expert.cpp) call the first three with their scales, the public functions here with none
+// (mpf_gerfsx_scaled: the caller's), through solve_entry.
 // Around the per-column rules of solve_rules.h every core has the same three frames, each written once:
 //   for_groups / for_rhs_groups   the right-hand sides go through the device in groups of at most GROUP_TILES tiles of BLK_T columns
 //                                 (solve_block.hip); every triangular step and every residual is one pass over the factor block / over
@@ -330,8 +332,10 @@ int blk_bounds_core(const BlkSys &s, const BlkRhs &r, int32_t itmax, double *fer
 // The body of mpf_gerfsx (mpf_internal.h): dla_gerfsx_extended's loop on all columns of a group in lock-step.  Per step one residual in
 // pairs of doubles (launch_blk_residual_x), one tile_getrs, one launch and one read-back of the three measures, XrCol's decision per
 // column (solve_rules.h) and one masked update; a column that has stopped is frozen.  Tile sets: B, X, R (then in place d) and
-// tile_getrs's two.
-int blk_xrefine_core(const BlkSys &s, const BlkRhs &r, int32_t ithresh, double *err_norm, double *err_comp, mpf_gerfsx_stats *st) {
+// tile_getrs's two.  With `berr`, after the loop and for the X that is returned: w = |b| + |op(A)| |x| from mpf_gerfs's ABS pass (its
+// plain residual and quotient land in scratch and are dropped), r once more in pairs, dgerfs's quotient and its column maximum.
+int blk_xrefine_core(const BlkSys &s, const BlkRhs &r, int32_t ithresh, double *err_norm, double *err_comp, mpf_gerfsx_stats *st,
+                     double *berr) {
     mpf_ctx *c = s.c;
     const int64_t N = s.N;
     return for_rhs_groups(s, r, GROUP_TILES, 5, LOAD_B | LOAD_X | STORE_X, [&](const Group &g, int32_t j0, int64_t ncols) {
@@ -358,6 +362,14 @@ int blk_xrefine_core(const BlkSys &s, const BlkRhs &r, int32_t ithresh, double *
         }
         // out of steps with columns still going: the one way out of a lock-step loop that has no read-back behind the last upload
         if (cnt == ithresh) MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (berr) {   // (W and Z are free: no solve follows)
+            const double safe1 = gerfs_safe1(N), safe2 = gerfs_safe2(N);
+            int rc = launch_blk_residual_bound(c, s.A, s.lda, N, s.tr, Xt, Bt, R, W, Z, g.ldt, g.ntiles, safe1, safe2);
+            if (!rc) rc = launch_blk_residual_x(c, s.A, s.lda, N, s.tr, Xt, Bt, R, g.ldt, g.ntiles);
+            if (!rc) rc = launch_blk_xr_berr(c, R, W, g.ldt, N, ncols, safe1, safe2);
+            if (!rc) rc = read_back(c, c->blk_red, (size_t)ncols, berr + j0);
+            if (rc) return rc;
+        }
         for (int64_t j = 0; j < ncols; ++j) {
             XrCol &cj = col[(size_t)j];
             cj.finish(N, err_norm[j0 + j], err_comp[j0 + j]);
@@ -568,16 +580,34 @@ int mpf_residual_x(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, in
     return 0;
 }
 
+// mpf_gerfsx and mpf_gerfsx_scaled: d_r / d_c (the scales of the factored matrix Dr A Dc, or null) become tile_getrs's pre / post as
+// gesvx_steps maps them (mpf_expert.cpp)
+static int gerfsx_entry(const char *who, mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu,
+                        const int32_t *d_ipiv, int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                        int32_t ithresh, const double *d_r, const double *d_c, double *err_norm, double *err_comp, double *berr,
+                        mpf_gerfsx_stats *stats) {
+    if (ithresh <= 0) ithresh = 10;
+    if (ithresh > 31) ithresh = 31;
+    const bool tr = trans == 1;
+    const BlkSys s{c, tr, d_A, lda, d_LU, ldlu, N, tr ? d_c : d_r, tr ? d_r : d_c};
+    const BlkRhs r{nrhs, d_B, ldb, d_X, ldx};
+    return solve_entry(who, trans, s, r, d_ipiv, {err_norm, err_comp}, stats,
+                       [&](mpf_gerfsx_stats *st) { return blk_xrefine_core(s, r, ithresh, err_norm, err_comp, st, berr); },
+                       [](const mpf_gerfsx_stats &q) { return q.x_state == XrCol::X_CONV; });
+}
+
 int mpf_gerfsx(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
                int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t ithresh, double *err_norm,
                double *err_comp, mpf_gerfsx_stats *stats) {
-    if (ithresh <= 0) ithresh = 10;
-    if (ithresh > 31) ithresh = 31;
-    const BlkSys s{c, trans == 1, d_A, lda, d_LU, ldlu, N};
-    const BlkRhs r{nrhs, d_B, ldb, d_X, ldx};
-    return solve_entry("gerfsx", trans, s, r, d_ipiv, {err_norm, err_comp}, stats,
-                       [&](mpf_gerfsx_stats *st) { return blk_xrefine_core(s, r, ithresh, err_norm, err_comp, st); },
-                       [](const mpf_gerfsx_stats &q) { return q.x_state == XrCol::X_CONV; });
+    return gerfsx_entry("gerfsx", c, trans, d_A, lda, d_LU, ldlu, d_ipiv, N, nrhs, d_B, ldb, d_X, ldx, ithresh, nullptr, nullptr, err_norm,
+                        err_comp, nullptr, stats);
+}
+
+int mpf_gerfsx_scaled(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv,
+                      int64_t N, int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t ithresh, const double *d_r,
+                      const double *d_c, double *err_norm, double *err_comp, double *berr, mpf_gerfsx_stats *stats) {
+    return gerfsx_entry("gerfsx_scaled", c, trans, d_A, lda, d_LU, ldlu, d_ipiv, N, nrhs, d_B, ldb, d_X, ldx, ithresh, d_r, d_c, err_norm,
+                        err_comp, berr, stats);
 }
 
 int mpf_solve_gmres_ir_block(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu,

@@ -5,6 +5,8 @@
 //   mpf_gecon            reciprocal condition number of the factors (dlacn2 on the device's solves)
 //   mpf_gesvx            equilibrate, factor, estimate rcond, refine against the original matrix, fall back to fp64
 //   mpf_gesvx_block      the same steps for many right-hand sides: blocked refinement and dgerfs's bounds on the scaled factors
+//   mpf_gerpvgrw         reciprocal pivot growth of the factors (dla_gerpvgrw)
+//   mpf_gesvxx_block     the same steps with the extra-precise refinement and its bounds (dgesvxx's shape), berr and pivot growth
 // Kernels in solve_ext.hip; the device only ever hands scalars back to the host.
 #include "solve_common.h"
 #include <cfloat>
@@ -137,6 +139,14 @@ int gecon_core(mpf_ctx *c, const Ext &e, const double *LU, int64_t ld, int64_t N
     ainvnm = col.est;
     return 0;
 }
+// dla_gerpvgrw: min(1, min_j amax_j / umax_j) of A (scaled by r / cs where given) against the factors' U, through V_X and one scalar
+int gerpvgrw_core(mpf_ctx *c, const Ext &e, const double *A, int64_t lda, const double *LU, int64_t ldlu, int64_t N, const double *r,
+                  const double *cs, double &out) {
+    int rc = launch_pivot_growth_cols(c, A, lda, LU, ldlu, N, r, cs, e.v(V_X));
+    if (!rc) rc = launch_vec_min1(c, e.v(V_X), N, e.scal());
+    return rc ? rc : read_scalars(c, e.scal(), &out, 1);
+}
+
 // rcond from anorm and the factors; checks U's diagonal first.  The factors must be prepared.
 int gecon_full(mpf_ctx *c, const Ext &e, const double *LU, int64_t ld, int64_t N, bool onenorm, double anorm, double &rcond, mpf_gecon_stats &st) {
     rcond = 0;
@@ -170,12 +180,12 @@ int refine_on_factors(mpf_ctx *c, const IrScratch &w, const double *A, int64_t l
                          [&](const double *xx, double *r) { return trans ? launch_residual_t(c, A, lda, xx, b, r, N) : launch_residual(c, A, lda, xx, b, r, N); });
 }
 
-// Steps 1 .. 6 of the expert drivers (mpf_gesvx, mpf_gesvx_block): equilibrate, factor d_work, rcond, the kappa_max gate, one
-// refinement attempt on the low-precision factors and, where that did not converge, fp64 factors of the same equilibrated matrix
-// and a second attempt.  Everything up to the gate depends on A alone, so both drivers take the same decisions and leave the same
-// factors.  `refine(pre, post, ir)` runs one attempt on the factors in d_work (prepared by solve_setup) and fills `ir`: its
-// `converged` decides whether the attempt stands; its ms_total is set here.  Fills `gs` except ms_total; pre / post are the scale
-// vectors of the preconditioner (null where equed says none), valid while `e`, d_r and d_c are.
+// Steps 1 .. 6 of the expert drivers (mpf_gesvx, mpf_gesvx_block, mpf_gesvxx_block): equilibrate, factor d_work, rcond, the kappa_max
+// gate, one refinement attempt on the low-precision factors and, where that does not stand, fp64 factors of the same equilibrated
+// matrix and a second attempt.  Everything up to the gate depends on A alone, so the drivers take the same decisions and leave the
+// same factors.  `refine(pre, post, ir, stands)` runs one attempt on the factors in d_work (prepared by solve_setup), fills `ir` and
+// says whether the attempt stands (the plain drivers: ir.converged); ir's ms_total is set here.  Fills `gs` except ms_total;
+// pre / post are the scale vectors of the preconditioner (null where equed says none), valid while `e`, d_r and d_c are.
 template <class Refine>
 int gesvx_steps(mpf_ctx *c, const Ext &e, const double *d_A, int64_t lda, int64_t N, int32_t nb, double *d_work, int32_t *d_ipiv, bool tr,
                 int32_t equilibrate, int32_t try_fp16, double kappa_max, double *d_r, double *d_c, mpf_gesvx_stats &gs, const double *&pre,
@@ -249,9 +259,9 @@ int gesvx_steps(mpf_ctx *c, const Ext &e, const double *d_A, int64_t lda, int64_
         gs.ms_gecon += ms_since(t1);
         return 0;
     };
-    auto refine = [&](mpf_ir_stats &ir) -> int {
+    auto refine = [&](mpf_ir_stats &ir, bool &stands) -> int {
         const auto t1 = std::chrono::steady_clock::now();
-        int r2 = refine_attempt(pre, post, ir);
+        int r2 = refine_attempt(pre, post, ir, stands);
         if (!r2) MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
         ir.ms_total = ms_since(t1);
         gs.ms_ir += ir.ms_total;
@@ -266,16 +276,18 @@ int gesvx_steps(mpf_ctx *c, const Ext &e, const double *d_A, int64_t lda, int64_
         if (rc) return rc;
         if (!(gs.rcond_lowp > 0) || 1.0 / gs.rcond_lowp > gs.kappa_max) gs.skipped_by_rcond = 1;
         else {
-            rc = refine(gs.ir_lowp);
+            bool stands = false;
+            rc = refine(gs.ir_lowp, stands);
             if (!rc) rc = solve_check_waits(c);   // (the fp64 attempt's set-up clears the give-up flag)
             if (rc) return rc;
-            if (gs.ir_lowp.converged) { gs.path = 1; gs.rcond = gs.rcond_lowp; gs.ir_final = gs.ir_lowp; done = true; }
+            if (stands) { gs.path = 1; gs.rcond = gs.rcond_lowp; gs.ir_final = gs.ir_lowp; done = true; }
         }
         if (!done) { rc = scaled_copy(); if (rc) return rc; }   // the low-precision factors overwrote the copy
     }
     if (!done) {
+        bool stands = false;   // (the last attempt: whatever it says, its answer is returned)
         rc = factor_and_rcond(MPF_TRAIL_FP64, gs.rcond);
-        if (!rc) rc = refine(gs.ir_final);
+        if (!rc) rc = refine(gs.ir_final, stands);
         if (rc) return rc;
         gs.path = 2;
     }
@@ -411,8 +423,10 @@ int mpf_gesvx(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32_t nb,
     const bool tr = trans == 1;
     const double *pre = nullptr, *post = nullptr;
     rc = gesvx_steps(c, e, d_A, lda, N, nb, d_work, d_ipiv, tr, equilibrate, try_fp16, kappa_max, d_r, d_c, gs, pre, post,
-                     [&](const double *pr, const double *po, mpf_ir_stats &ir) {
-                         return refine_on_factors(c, ir_scratch(e), d_A, lda, d_work, N, N, tr, pr, po, d_b, d_x, max_iter, tol, ir);
+                     [&](const double *pr, const double *po, mpf_ir_stats &ir, bool &stands) {
+                         int r2 = refine_on_factors(c, ir_scratch(e), d_A, lda, d_work, N, N, tr, pr, po, d_b, d_x, max_iter, tol, ir);
+                         stands = ir.converged != 0;
+                         return r2;
                      });
     if (rc) return rc;
     MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -450,11 +464,12 @@ int mpf_gesvx_block(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32
     const BlkRhs rhs{nrhs, d_B, ldb, d_X, ldx};
     // one attempt: all columns on the factors in d_work; the attempt's summary is its worst column
     rc = gesvx_steps(c, e, d_A, lda, N, nb, d_work, d_ipiv, tr, equilibrate, try_fp16, kappa_max, d_r, d_c, gs, pre, post,
-                     [&](const double *pr, const double *po, mpf_ir_stats &worst) {
+                     [&](const double *pr, const double *po, mpf_ir_stats &worst, bool &stands) {
                          std::fill(cols.begin(), cols.end(), mpf_ir_stats{});
                          int r2 = blk_refine_core(BlkSys{c, tr, d_A, lda, d_work, N, N, pr, po}, rhs, max_iter, tol, cols.data());
                          if (r2) return r2;
                          worst = cols[worst_column(cols.data(), cols.size())];
+                         stands = worst.converged != 0;
                          return 0;
                      });
     if (rc) return rc;
@@ -479,6 +494,84 @@ int mpf_gesvx_block(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32
     rc = solve_check_waits(c);
     if (rc) return rc;
     return gs.ir_final.converged ? 0 : 1;
+}
+
+int mpf_gerpvgrw(mpf_ctx *c, const double *d_A, int64_t lda, const double *d_LU, int64_t ldlu, int64_t N, const double *d_r,
+                 const double *d_c, double *rpvgrw) {
+    if (!c) return -1;
+    if (N <= 0 || lda < N || ldlu < N) { c->err = "gerpvgrw: bad N / lda / ldlu"; return -1; }
+    if (!d_A || !d_LU || !rpvgrw) { c->err = "gerpvgrw: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    Ext e;
+    int rc = ext_vectors(c, N, e);
+    return rc ? rc : gerpvgrw_core(c, e, d_A, lda, d_LU, ldlu, N, d_r, d_c, *rpvgrw);
+}
+
+int mpf_gesvxx_block(mpf_ctx *c, const double *d_A, int64_t lda, int64_t N, int32_t nb, double *d_work, int32_t *d_ipiv, int32_t nrhs,
+                     const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t trans, int32_t equilibrate, int32_t try_fp16,
+                     double kappa_max, int32_t max_iter, double tol, int32_t ithresh, double *d_r, double *d_c, double *err_norm,
+                     double *err_comp, double *berr, double *rpvgrw, mpf_gesvx_stats *stats, mpf_ir_stats *ir, mpf_gerfsx_stats *xr) {
+    if (!c) return -1;
+    if (N <= 0 || nrhs < 0) { c->err = "gesvxx_block: N must be positive, nrhs >= 0"; return -1; }
+    if (lda < N || ldb < N || ldx < N) { c->err = "gesvxx_block: leading dimension < N"; return -1; }
+    if (trans < 0 || trans > 1 || equilibrate < 0 || equilibrate > 2 || try_fp16 < 0 || try_fp16 > 2) {
+        c->err = "gesvxx_block: trans must be 0 / 1, equilibrate 0 / 1 / 2, try_fp16 0 / 1 / 2";
+        return -1;
+    }
+    if (nrhs == 0) return 0;
+    if (!d_A || !d_work || !d_ipiv || !d_B || !d_X || !err_norm || !err_comp) { c->err = "gesvxx_block: null pointer"; return -1; }
+    if (max_iter > 31) max_iter = 31;
+    if (ithresh <= 0) ithresh = 10;
+    if (ithresh > 31) ithresh = 31;
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const auto t_all = std::chrono::steady_clock::now();
+    mpf_gesvx_stats gs{};
+    Ext e;
+    int rc = ext_vectors(c, N, e);
+    if (rc) return rc;
+    const bool tr = trans == 1;
+    const double *pre = nullptr, *post = nullptr;
+    std::vector<mpf_ir_stats> cols((size_t)nrhs);
+    std::vector<mpf_gerfsx_stats> xcols((size_t)nrhs);
+    const BlkRhs rhs{nrhs, d_B, ldb, d_X, ldx};
+    double ms_x = 0;
+    // one attempt: (a) the plain refinement of all columns on the factors in d_work, its summary the worst column; (b) the
+    // extra-precise loop on that X with a fresh rule state.  It stands iff every column ends (b) converged.
+    rc = gesvx_steps(c, e, d_A, lda, N, nb, d_work, d_ipiv, tr, equilibrate, try_fp16, kappa_max, d_r, d_c, gs, pre, post,
+                     [&](const double *pr, const double *po, mpf_ir_stats &worst, bool &stands) {
+                         const BlkSys sys{c, tr, d_A, lda, d_work, N, N, pr, po};
+                         std::fill(cols.begin(), cols.end(), mpf_ir_stats{});
+                         std::fill(xcols.begin(), xcols.end(), mpf_gerfsx_stats{});
+                         int r2 = blk_refine_core(sys, rhs, max_iter, tol, cols.data());
+                         if (r2) return r2;
+                         worst = cols[worst_column(cols.data(), cols.size())];
+                         MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));   // (stage (b)'s own time)
+                         const auto t1 = std::chrono::steady_clock::now();
+                         r2 = blk_xrefine_core(sys, rhs, ithresh, err_norm, err_comp, xcols.data(), berr);
+                         if (r2) return r2;
+                         MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+                         ms_x = ms_since(t1);
+                         stands = true;
+                         for (const auto &q : xcols) stands = stands && q.x_state == XrCol::X_CONV;
+                         return 0;
+                     });
+    if (rc) return rc;
+    for (auto &s : cols) s.ms_total = gs.ir_final.ms_total;
+    bool all = true;
+    for (auto &q : xcols) { q.ms_total = ms_x; all = all && q.x_state == XrCol::X_CONV; }
+    if (rpvgrw) {   // of the factors in d_work against A with the scales that were applied
+        const double *r = tr ? post : pre, *cs = tr ? pre : post;
+        rc = gerpvgrw_core(c, e, d_A, lda, d_work, N, N, r, cs, *rpvgrw);
+        if (rc) return rc;
+    }
+    MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    gs.ms_total = ms_since(t_all);
+    if (stats) *stats = gs;
+    if (ir) std::copy(cols.begin(), cols.end(), ir);
+    if (xr) std::copy(xcols.begin(), xcols.end(), xr);
+    rc = solve_check_waits(c);
+    if (rc) return rc;
+    return all ? 0 : 1;
 }
 
 } // extern "C"

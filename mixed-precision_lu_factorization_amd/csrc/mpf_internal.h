@@ -422,6 +422,12 @@ int launch_diag_zero(mpf_ctx *c, const double *LU, int64_t ld, int64_t n, double
 int launch_pow2_scale(mpf_ctx *c, const double *m, int64_t n, double *s, double *d_stats);
 int launch_scaled_copy(mpf_ctx *c, const double *A, int64_t lda, const double *r, const double *cs, double *W, int64_t ldw, int64_t m, int64_t n);
 int launch_vscale(mpf_ctx *c, const double *x, const double *s, double alpha, double *y, int64_t n);
+// reciprocal pivot growth (mpf_gerpvgrw).  launch_pivot_growth_cols: q[j] = amax_j / umax_j with amax_j = max_i (|a_ij| r_i) c_j (r / cs
+// null: 1) and umax_j = max_{i <= j} |lu_ij|; 1 where umax_j = 0 (the column is skipped), NaN where either maximum is.
+// launch_vec_min1: d_out[0] = min(1, min_j q[j]), a NaN kept
+int launch_pivot_growth_cols(mpf_ctx *c, const double *A, int64_t lda, const double *LU, int64_t ldlu, int64_t n, const double *r,
+                             const double *cs, double *q);
+int launch_vec_min1(mpf_ctx *c, const double *q, int64_t n, double *d_out);
 // blocked multi-right-hand-side solve (solve_block.hip).  Tiles: BLK_T columns each, column-major with ld = N rounded up to 256, rows
 // beyond N zero.  launch_blk_tri: which 0 = L, 1 = U, 2 = U^T, 3 = L^T on x (consumed) -> y, factors prepared by launch_trsv_prepare
 constexpr int BLK_T = 32;
@@ -451,17 +457,23 @@ int launch_blk_lacn2_sign(mpf_ctx *c, double *v, double *isgn, int64_t n, int64_
 int launch_blk_residual_x(mpf_ctx *c, const double *A, int64_t lda, int64_t n, bool trans, const double *X, const double *B, double *R,
                           int64_t ldt, int ntiles);
 int launch_blk_xr_measure(mpf_ctx *c, const double *X, const double *D, int64_t ldt, int64_t n, int64_t ncols);
+// launch_blk_xr_berr: dgerfs's componentwise backward error per column of the tiles R (residual) and W (|b| + |op(A)| |x|):
+// max_i (w_i > safe2 ? |r_i| / w_i : (|r_i| + safe1) / (w_i + safe1)), a NaN kept, one launch, into c->blk_red (ncols doubles)
+int launch_blk_xr_berr(mpf_ctx *c, const double *R, const double *W, int64_t ldt, int64_t n, int64_t ncols, double safe1, double safe2);
 // mpf_block.cpp: what every core of the blocked solve layer receives.  BlkSys: op(A) = A or A^T (tr), the ORIGINAL matrix and its
 // prepared factors (solve_setup) with the preconditioner
 //     op(A)^-1 v ~ post .* op(L U, P)^-1 (pre .* v)        (pre / post: scale vectors of the factored matrix Dr A Dc, or null)
 // tr = 0: pre = Dr, post = Dc; tr = 1: pre = Dc, post = Dr.  BlkRhs: the right-hand sides and the solutions, column-major.
 struct BlkSys { mpf_ctx *c; bool tr; const double *A; int64_t lda; const double *LU; int64_t ldlu; int64_t N; const double *pre, *post; };
 struct BlkRhs { int32_t nrhs; const double *B; int64_t ldb; double *X; int64_t ldx; };
-// The bodies of mpf_solve_ir_block, mpf_gerfs and mpf_gerfsx (ithresh clamped by the caller; no scales) after the argument checks and
-// solve_setup; `st` holds nrhs zeroed entries; no core synchronises at its end or sets ms_total.
+// The bodies of mpf_solve_ir_block, mpf_gerfs and mpf_gerfsx / mpf_gerfsx_scaled (ithresh clamped by the caller) after the argument
+// checks and solve_setup; `st` holds nrhs zeroed entries; no core synchronises at its end or sets ms_total.  blk_xrefine_core with
+// `berr` (host, nrhs doubles): after the loop, dgerfs's backward error of the X it returns (one more pair residual and one ABS pass
+// per group); without it the core is mpf_gerfsx's, launch for launch.
 int blk_refine_core(const BlkSys &s, const BlkRhs &r, int32_t max_iter, double tol, mpf_ir_stats *st);
 int blk_bounds_core(const BlkSys &s, const BlkRhs &r, int32_t itmax, double *ferr, double *berr, mpf_gerfs_stats *st);
-int blk_xrefine_core(const BlkSys &s, const BlkRhs &r, int32_t ithresh, double *err_norm, double *err_comp, mpf_gerfsx_stats *st);
+int blk_xrefine_core(const BlkSys &s, const BlkRhs &r, int32_t ithresh, double *err_norm, double *err_comp, mpf_gerfsx_stats *st,
+                     double *berr = nullptr);
 // solve_gmres.hip: the orthogonalisation (classical Gram-Schmidt twice) and the vector updates of the blocked GMRES-IR; basis slot i at
 // V + i * vs, tiles as above.  launch_gmres_ortho: W = -W orthogonalised against the slots 0 .. ns - 1 on the columns with live[j] != 0,
 // out = [h (ns x tc) | h' (ns x tc) | ||w||^2 (tc)], tc = BLK_T * ntiles; part: gmres_ortho_chunks(ldt) * max(ns, 4) * tc doubles

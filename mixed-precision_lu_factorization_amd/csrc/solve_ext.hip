@@ -493,3 +493,49 @@ int launch_vscale(mpf_ctx *c, const double *x, const double *s, double alpha, do
     MPF_HIP_TRY(c, hipGetLastError());
     return 0;
 }
+
+// ---- reciprocal pivot growth (mpf_gerpvgrw; LAPACK dla_gerpvgrw) ------------------------------------------------------------------
+// One wave per column, four columns per workgroup: q[j] = amax_j / umax_j with amax_j = max_i (|a_ij| r_i) c_j and umax_j =
+// max_{i <= j} |lu_ij|.  The lanes stride down the column, so A's column and U's part of LU's are each read once, coalesced.  c_j > 0
+// multiplies after the maximum: rounding is monotone, so the product of the maximum is the maximum of the products.  umax_j = 0: the
+// column is skipped (q = 1, the value the minimum starts from); a NaN in either maximum: q = NaN.
+__global__ __launch_bounds__(256) void pivot_growth_cols_kernel(const double *__restrict__ A, long long lda, const double *__restrict__ LU,
+                                                                long long ldlu, long long n, const double *__restrict__ r,
+                                                                const double *__restrict__ cs, double *__restrict__ q) {
+    const long long col = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (col >= n) return;                                         // (wave-uniform; no barrier below)
+    const double *a = A + col * lda, *u = LU + col * ldlu;
+    double am[4] = {0, 0, 0, 0}, um[4] = {0, 0, 0, 0};
+    int k = 0;
+    for (long long i = lane; i < n; i += 64, ++k) {
+        const double e = fabs(a[i]);
+        am[k & 3] = maxn(am[k & 3], r ? e * r[i] : e);
+        if (i <= col) um[k & 3] = maxn(um[k & 3], fabs(u[i]));
+    }
+    double amax = wave_max(maxn(maxn(am[0], am[1]), maxn(am[2], am[3])));
+    const double umax = wave_max(maxn(maxn(um[0], um[1]), maxn(um[2], um[3])));
+    if (cs) amax = amax * cs[col];
+    if (lane == 0) q[col] = (amax != amax || umax != umax) ? (amax != amax ? amax : umax) : (umax != 0 ? amax / umax : 1.0);
+}
+int launch_pivot_growth_cols(mpf_ctx *c, const double *A, int64_t lda, const double *LU, int64_t ldlu, int64_t n, const double *r,
+                             const double *cs, double *q) {
+    pivot_growth_cols_kernel<<<(unsigned)((n + 3) / 4), 256, 0, c->stream>>>(A, lda, LU, ldlu, n, r, cs, q);
+    MPF_HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+// d_out[0] = min(1, min_j q[j]), a NaN kept; one workgroup
+__global__ __launch_bounds__(256) void vec_min1_kernel(const double *__restrict__ q, long long n, double *__restrict__ out) {
+    __shared__ double ws[4];
+    double s = -1.0;                                              // the minimum as a maximum of the negatives: maxn keeps a NaN
+    for (long long i = threadIdx.x; i < n; i += 256) s = maxn(s, -q[i]);
+    s = wave_max(s);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = -maxn(maxn(ws[0], ws[1]), maxn(ws[2], ws[3]));
+}
+int launch_vec_min1(mpf_ctx *c, const double *q, int64_t n, double *d_out) {
+    vec_min1_kernel<<<1, 256, 0, c->stream>>>(q, n, d_out);
+    MPF_HIP_TRY(c, hipGetLastError());
+    return 0;
+}

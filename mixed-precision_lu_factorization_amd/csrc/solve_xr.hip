@@ -1,6 +1,6 @@
 // Kernels of the extra-precise refinement (mpf_block.cpp: mpf_residual_x, mpf_gerfsx; LAPACK dgerfsx with the XBLAS residual) on the
 // tiles of solve_block.hip: the residual R = B - op(A) X accumulated in twice the working precision, and the three per-column
-// reductions a refinement step is steered by.
+// reductions a refinement step is steered by; and the componentwise backward error of mpf_gerfsx_scaled, one more reduction after the loop.
 // The residual is VALU work (no MFMA form): every element is an unevaluated pair (hi, lo) that takes each product exactly,
 //     p = a x,  e = fma(a, x, -p),  (hi, t) = TwoSum(hi, -p),  lo += t - e            (Dekker / Knuth; Ogita, Rump, Oishi's Dot2)
 // which needs the separately rounded operations of -ffp-contract=off; the one fused operation is spelled __builtin_fma.  A workgroup
@@ -178,6 +178,33 @@ int launch_blk_xr_measure(mpf_ctx *c, const double *X, const double *D, int64_t 
     if (ncols <= 0) return 0;
     MPF_HIP_TRY(c, c->blk_red.grow(3 * ncols));
     blk_xr_measure_kernel<<<(unsigned)ncols, 256, 0, c->stream>>>(X, D, ldt, n, ncols, c->blk_red);
+    MPF_HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+// dgerfs's componentwise backward error of mpf_gerfsx_scaled, one workgroup per column: out[j] = max_i of blk_res_abs_reduce_kernel's
+// quotient (solve_block.hip) on the pair residual r and the weights w = |b| + |op(A)| |x|.  A NaN in r or w makes the value NaN.
+__global__ __launch_bounds__(256) void blk_xr_berr_kernel(const double *__restrict__ R, const double *__restrict__ W, long long ldt,
+                                                          long long n, double safe1, double safe2, double *__restrict__ out) {
+    __shared__ double part[4];
+    const long long j = blockIdx.x;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const double *r = R + j * ldt, *wt = W + j * ldt;
+    double m = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 256) {
+        const double rv = fabs(r[i]), wv = wt[i];
+        m = maxn(m, wv > safe2 ? rv / wv : (rv + safe1) / (wv + safe1));
+    }
+    m = wave_max(m);
+    if (lane == 0) part[w] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) out[j] = maxn(maxn(part[0], part[1]), maxn(part[2], part[3]));
+}
+// One launch for all columns of the tiles R and W; the results land in c->blk_red: ncols doubles
+int launch_blk_xr_berr(mpf_ctx *c, const double *R, const double *W, int64_t ldt, int64_t n, int64_t ncols, double safe1, double safe2) {
+    if (ncols <= 0) return 0;
+    MPF_HIP_TRY(c, c->blk_red.grow(ncols));
+    blk_xr_berr_kernel<<<(unsigned)ncols, 256, 0, c->stream>>>(R, W, ldt, n, safe1, safe2, c->blk_red);
     MPF_HIP_TRY(c, hipGetLastError());
     return 0;
 }
