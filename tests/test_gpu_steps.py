@@ -348,13 +348,16 @@ def test_hgemm_minus_big_tiles_and_fp32_copy(ctx, oracle, m, n, k, c32, split):
     assert np.array_equal(got[m:, :], Cm[m:, :])
 
 
-@pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 5])
+# (hgemm_mfma16 = 1, the default, keeps the ids these cases always had; the 32x32x16 family's cases are added beside them)
+@pytest.mark.parametrize("tile,mfma16", [pytest.param(t, 1, id=str(t)) for t in range(6)] + [pytest.param(t, 0, id=f"{t}-mfma16_0") for t in range(6)])
 @pytest.mark.parametrize("m,n,k", [(1100, 1030, 512), (2048, 2304, 1024), (1500, 1300, 320)])
-def test_hgemm_minus_half_tile_variant(mpf, oracle, m, n, k, tile):
+def test_hgemm_minus_half_tile_variant(mpf, oracle, m, n, k, tile, mfma16):
     """Option hgemm_big_tile: the tile forms of the big-K update (0 = 256 x 256, one workgroup per CU; 1 = 128 x 256, ring of
-    four stages; 2 = 128 x 256, ring of three stages, TWO workgroups per CU): same result contract whatever the tile."""
+    four stages; 2 = 128 x 256, ring of three stages, TWO workgroups per CU): same result contract whatever the tile.  With
+    hgemm_mfma16 = 1 (the default) the tile option does not apply to plain operands -- they all go to hgemm16_big_kernel; with 0
+    the tile forms of hgemm_big_kernel are what runs."""
     import torch
-    c2 = mpf.MPFContext(0, options={"hgemm_big_tile": tile})
+    c2 = mpf.MPFContext(0, options={"hgemm_big_tile": tile, "hgemm_mfma16": mfma16})
     rng = np.random.default_rng(m + n + k)
     A = np.asfortranarray(rng.standard_normal((m, k)))
     B = np.asfortranarray(rng.standard_normal((k, n)) * 4.0)
