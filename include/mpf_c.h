@@ -92,6 +92,8 @@ typedef struct mpf_stats {
     int32_t pivot_search;       /* the pivot rule that ran: 0 fp16 image (the reference's), 1 fp64 partial pivoting, 2 fp64 tournament
                                    pivoting -- for 1 and 2 lookahead = 0, superpanel = 1, ms_hpanel = 0 and ms_dpanel is the pivoting panel
                                    (event_timers = 2 for the phase timers) */
+    int32_t fp16_fused;         /* the fp16 pivot panel's elimination that ran: 0 rounded product, rounded difference (contract C2), 1 one fused
+                                   multiply-add (contract C2f, option fp16_fused); 0 under pivot_search 1 and 2, which run no fp16 panel */
 } mpf_stats;
 
 /* ---- lifetime -------------------------------------------------------------------------- */
@@ -109,6 +111,17 @@ int mpf_get_stats(mpf_ctx *ctx, mpf_stats *out);
  * on different host threads are independent.  Names: safe_pivots, chain_pipeline, chain_pipeline_below, fp16_work32,
  * superpanel_fp16, superpanel_fp64, no_lookahead, verbose, timeline, hp_spin_limit, hp_gate_ticks, hp_acq_fence, hgemm_pad,
  * hgemm_split_pad, hgemm_big, hgemm_big_tile, dgemm_dma, generic_fused, pivot_fp64 (0 .. 2: the pivot_search every driver that factors internally uses), fp64_rowmajor, fp64_rowmajor_min_n, dist_instalments, dist_instalment_min_bytes, lazy_gather, dpanel_fused_form, trsm_laswp_fused,
+ * fp16_fused (0 / 1, MPF_FP16_FUSED; default 0.  RESULTS DEPEND ON IT.  The rank-1 step of the fp16 pivot panel, hgetf2_kernel.cu:113
+ * `panel[k*ld+row] -= multiplier * panel[k*ld+j]`: 0 = contract C2, the product rounded to fp16, then the difference rounded to fp16 -- what the
+ * reference computes when nvcc does not contract, as under the `-G -O0` recipe this project's parity is stated for; 1 = contract C2f,
+ * a[row][k] <- fma(-m, a[j][k], a[row][k]) rounded ONCE to fp16, round-to-nearest-even, subnormals kept, zeros / infinities / NaN by IEEE rules --
+ * v_pk_fma_f16 here, CUDA's fma.rn.f16, what an optimised nvcc build may make of that line; negating m is exact.  Nothing else changes: the
+ * conversion (C1), the pivot search and its tie-break, the division (IEEE fp32 quotient rounded once), the interchanges, the fp64 panel
+ * (mpf_opts.fused_panel is independent), the trailing updates.  The fp16 panel's only output is IPIV, so the other setting is another
+ * factorization: other pivots, other bits.  Read at each launch of a pivot kernel: mpf_hgetf2_pivots, mpf_hgetf2, mpf_factor_dev (every schedule
+ * and trailing mode), mpf_factor_host, MPF(), mpf_gesv, mpf_gesvx, mpf_gesvx_block, mpf_gesvxx_block, mpf_factor_dist -- whose ranks MUST all hold
+ * the same value (every rank factors panels with its own context's setting; ranks that disagree produce an inconsistent factorization, and nothing
+ * checks it).  No effect under pivot_search = 1 or 2 (no fp16 panel runs).  mpf_stats.fp16_fused says what ran.),
  * gmres_group_tiles (tiles of 32 columns mpf_solve_gmres_ir_block takes together; 0 = automatic; same bits).  mpf_option_name enumerates them (returns the count). */
 /* Rows of the tallest panel the LDS-resident pivot kernel takes -- all its workgroups must be resident at once -- beside `waiters`
  * workgroups of kernels that wait for its progress (0: alone; a negative value -w: beside the pipelined chain's gated interchange

@@ -55,7 +55,7 @@ class MpfStats(C.Structure):
                 ("pivot_path", C.c_int32), ("gemm_flops", C.c_double), ("gemm_bytes", C.c_double),
                 ("ms_gemm_big", C.c_double), ("gemm_big_flops", C.c_double), ("gemm_big_bytes", C.c_double),
                 ("ms_cvt", C.c_double), ("ms_blockrow", C.c_double), ("gemm_big_launches", C.c_int32), ("host_rows_streamed", C.c_int32),
-                ("host_late_segments", C.c_int32), ("pivot_search", C.c_int32)]
+                ("host_late_segments", C.c_int32), ("pivot_search", C.c_int32), ("fp16_fused", C.c_int32)]
 
 
 class MpfIrStats(C.Structure):
@@ -387,8 +387,10 @@ class MPFContext:
 
     # ---- whole path ------------------------------------------------------------------------
     def factor(self, A, nb, ipiv=None, trailing=TRAIL_FP64, fused_panel=False, sync_timing=False, verbose=False,
-               no_lookahead=False, superpanel=0, pivot_path=0, pivot_search=0):
+               no_lookahead=False, superpanel=0, pivot_path=0, pivot_search=0, fp16_fused=None):
         """mpf_factor_dev: in-place MPF of the column-major device matrix A (N x N).
+        fp16_fused: None = the context's option fp16_fused as it stands; 0 / 1 = that option for this call only (put back afterwards):
+        1 = the fp16 pivot panel eliminates with one fused multiply-add per element (contract C2f: other pivots and factors).
         pivot_search: 0 = the reference's fp16 pre-pivoting, 1 = LAPACK's partial pivoting, searched in fp64, 2 = tournament pivoting
         in fp64 (mpf_dgetf2_tp's rule); also context option pivot_fp64 = 1 or 2, which gesv, gesvx, gesvx_block, gesvxx_block and factor_host follow.
         Returns (ipiv int32 device tensor, info)."""
@@ -401,7 +403,15 @@ class MPFContext:
         o = MpfOpts(trailing=trailing, verbose=int(verbose), fused_panel=int(fused_panel), sync_timing=int(sync_timing),
                     no_lookahead=int(no_lookahead), superpanel=int(superpanel), pivot_path=int(pivot_path),
                     pivot_search=int(pivot_search))
-        rc = self.L.mpf_factor_dev(self.h, _ptr(A), _colmajor_ld(A), n, nb, _ptr(ipiv), C.byref(o))
+        if fp16_fused is None:
+            rc = self.L.mpf_factor_dev(self.h, _ptr(A), _colmajor_ld(A), n, nb, _ptr(ipiv), C.byref(o))
+        else:
+            before = self.get_option("fp16_fused")
+            self.set_option("fp16_fused", int(fp16_fused))
+            try:
+                rc = self.L.mpf_factor_dev(self.h, _ptr(A), _colmajor_ld(A), n, nb, _ptr(ipiv), C.byref(o))
+            finally:
+                self.set_option("fp16_fused", before)
         return ipiv, self._check(rc, "mpf_factor_dev")
 
     def trim(self):

@@ -22,20 +22,28 @@
 //     candidate granules, picks the same winner and reads the winner's row granules (sc1 loads),
 //     re-reading until every tag matches.
 //   * Arithmetic is contract C2: v_pk_mul_f16 then v_pk_add_f16 (never fma), division = IEEE fp32
-//     quotient rounded once to fp16.
+//     quotient rounded once to fp16.  Option fp16_fused = 1 (contract C2f) runs the same kernels with the
+//     rank-1 step as ONE v_pk_fma_f16, fma(-m, u, x) rounded once -- what an optimised build of the
+//     reference may contract hgetf2_kernel.cu:113 into; a compile-time parameter of every form, chosen at
+//     the launch.  Conversion, search, tie-break, division, interchanges and the hand-off are the same.
 //   * On exit the kernel also leaves the list of rows that moved (src -> dst) for the fp64 row
 //     interchange kernel: the sequential swap chain of LASWP_kernel (MPF.cu:47-57) is already resolved
 //     by the position bookkeeping.
 #include "mpf_internal.h"
 #include <mutex>
+#include <type_traits>
 #include "fp16_device.h"
 
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u4_t __attribute__((ext_vector_type(4)));
 
-// one rank-1 step on a packed row pair: x - m*u with separately rounded product and difference
+// one rank-1 step on a packed row pair: x - m*u with separately rounded product and difference (contract C2), or -- FUSED,
+// contract C2f, option fp16_fused -- fma(-m, u, x) rounded once.  The file is built with -ffp-contract=off: the fused form is
+// spelled out (one v_pk_fma_f16 with neg_lo / neg_hi on the multiplier), the compiler never makes it from the other one.
+template <bool FUSED>
 __device__ __forceinline__ unsigned pk_elim(unsigned xw, h2_t m2, unsigned u2w) {
     const h2_t x = __builtin_bit_cast(h2_t, xw), u2 = __builtin_bit_cast(h2_t, u2w);
+    if (FUSED) return __builtin_bit_cast(unsigned, __builtin_elementwise_fma(-m2, u2, x));   // v_pk_fma_f16
     const h2_t t = m2 * u2; // v_pk_mul_f16   (hgetf2_kernel.cu:113, no fma)
     const h2_t y = x - t;   // v_pk_add_f16 neg
     return __builtin_bit_cast(unsigned, y);
@@ -130,7 +138,7 @@ __device__ __forceinline__ void hp_store_plain(unsigned long long *p, unsigned l
 // out as PLAIN stores (237 ns to the other workgroup's sc1 poll against 387 ns for a write-through store across XCDs,
 // profiles/r05_xcd_flag_probe.log); a plain store is never seen on another XCD, so the roles are only given to that XCD's own.
 // Fewer than G arrivals (a dispatch that is not round-robin) end in the bounded waits giving up (-4), like any missing workgroup.
-template <int R, bool STAMP = false, bool LOCAL = false>
+template <int R, bool STAMP = false, bool LOCAL = false, bool FUSED = false>
 __global__ __launch_bounds__(HP_T) void hgetf2_lds_kernel(HpArgs a) {
     constexpr int HP_PAIRS = R / 2;            // row pairs per workgroup
     constexpr int NW1 = HP_PAIRS / 64;         // waves that run the critical part (one row pair per lane)
@@ -253,7 +261,7 @@ __global__ __launch_bounds__(HP_T) void hgetf2_lds_kernel(HpArgs a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int c = 4 * lane + e;
-                        const unsigned y = pk_elim(xv[e], m2, uv[e]);
+                        const unsigned y = pk_elim<FUSED>(xv[e], m2, uv[e]);
                         const unsigned keep = (c >= j + 1) ? rmask : 0u;
                         xv[e] = (y & keep) | (xv[e] & ~keep);
                     }
@@ -324,7 +332,7 @@ __global__ __launch_bounds__(HP_T) void hgetf2_lds_kernel(HpArgs a) {
                     const u4_t uv = *(const u4_t *)(uprev + 4 * q);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const unsigned y = pk_elim(xv[e], m2, uv[e]);
+                        const unsigned y = pk_elim<FUSED>(xv[e], m2, uv[e]);
                         const unsigned keep = (4 * q + e >= j + 1) ? rmask : 0u;
                         xv[e] = (y & keep) | (xv[e] & ~keep);
                     }
@@ -344,7 +352,7 @@ __global__ __launch_bounds__(HP_T) void hgetf2_lds_kernel(HpArgs a) {
                     for (int b = 0; b < 4; ++b)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const unsigned y = pk_elim(xv[b][e], m2, uv[b][e]);
+                            const unsigned y = pk_elim<FUSED>(xv[b][e], m2, uv[b][e]);
                             xv[b][e] = (y & rmask) | (xv[b][e] & ~rmask);
                         }
 #pragma unroll
@@ -355,7 +363,7 @@ __global__ __launch_bounds__(HP_T) void hgetf2_lds_kernel(HpArgs a) {
                     const u4_t uv = *(const u4_t *)(uprev + 4 * q);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const unsigned y = pk_elim(xv[e], m2, uv[e]);
+                        const unsigned y = pk_elim<FUSED>(xv[e], m2, uv[e]);
                         xv[e] = (y & rmask) | (xv[e] & ~rmask);
                     }
                     *(u4_t *)(row + 4 * q) = xv;
@@ -469,7 +477,7 @@ __global__ __launch_bounds__(HP_T) void hgetf2_lds_kernel(HpArgs a) {
                 slab[tp * HP_RS + j] = (mw & rmask) | (dw & ~rmask); // :109
                 if (j + 1 < cols) {
                     const unsigned xw = xw0;
-                    const unsigned y = pk_elim(xw, m2, ujn);
+                    const unsigned y = pk_elim<FUSED>(xw, m2, ujn);
                     const unsigned nw = (y & rmask) | (xw & ~rmask);
                     slab[tp * HP_RS + j + 1] = nw;
                     if (pa > j) k0 = row_key32(nw & 0xFFFFu, pa, j + 1);
@@ -546,6 +554,7 @@ struct HwCarve {
     static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 };
 
+template <bool FUSED>
 __global__ __launch_bounds__(HP_T, 4) void hgetf2_win_kernel(HpArgs a) {   // 4 waves per SIMD: two of these workgroups on a CU
     constexpr int R = HP_R, HP_PAIRS = R / 2, NCG = HP_T / HP_PAIRS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -643,7 +652,7 @@ __global__ __launch_bounds__(HP_T, 4) void hgetf2_win_kernel(HpArgs a) {   // 4 
                         const u4_t uv = *(const u4_t *)(uprev + c0);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const unsigned y = pk_elim(xv[e], m2, uv[e]);
+                            const unsigned y = pk_elim<FUSED>(xv[e], m2, uv[e]);
                             const unsigned keep = (c0 + e >= j + 1) ? rmask : 0u;
                             xv[e] = (y & keep) | (xv[e] & ~keep);
                         }
@@ -682,7 +691,7 @@ __global__ __launch_bounds__(HP_T, 4) void hgetf2_win_kernel(HpArgs a) {   // 4 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const unsigned x = rc[4 * s + e];
-                    const unsigned y = pk_elim(x, m2, uv[e]);          // every register column is right of j+1
+                    const unsigned y = pk_elim<FUSED>(x, m2, uv[e]);          // every register column is right of j+1
                     rc[4 * s + e] = (y & rmask) | (x & ~rmask);
                 }
             }
@@ -725,7 +734,7 @@ __global__ __launch_bounds__(HP_T, 4) void hgetf2_win_kernel(HpArgs a) {   // 4 
                         const u4_t uv = *(const u4_t *)(uprev + 4 * q);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const unsigned y = pk_elim(xv[e], m2, uv[e]);
+                            const unsigned y = pk_elim<FUSED>(xv[e], m2, uv[e]);
                             const unsigned keep = (4 * q + e >= j + 1) ? rmask : 0u;
                             xv[e] = (y & keep) | (xv[e] & ~keep);
                         }
@@ -743,7 +752,7 @@ __global__ __launch_bounds__(HP_T, 4) void hgetf2_win_kernel(HpArgs a) {   // 4 
                         for (int b = 0; b < 4; ++b)
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
-                                const unsigned y = pk_elim(xv[b][e], m2, uv[b][e]);
+                                const unsigned y = pk_elim<FUSED>(xv[b][e], m2, uv[b][e]);
                                 xv[b][e] = (y & rmask) | (xv[b][e] & ~rmask);
                             }
 #pragma unroll
@@ -754,7 +763,7 @@ __global__ __launch_bounds__(HP_T, 4) void hgetf2_win_kernel(HpArgs a) {   // 4 
                         const u4_t uv = *(const u4_t *)(uprev + 4 * q);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const unsigned y = pk_elim(xv[e], m2, uv[e]);
+                            const unsigned y = pk_elim<FUSED>(xv[e], m2, uv[e]);
                             xv[e] = (y & rmask) | (xv[e] & ~rmask);
                         }
                         *(u4_t *)(row + 4 * q) = xv;
@@ -768,7 +777,7 @@ __global__ __launch_bounds__(HP_T, 4) void hgetf2_win_kernel(HpArgs a) {   // 4 
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const unsigned x = rc[4 * s + e];
-                            const unsigned y = pk_elim(x, m2, uv[e]);
+                            const unsigned y = pk_elim<FUSED>(x, m2, uv[e]);
                             rc[4 * s + e] = (y & rmask) | (x & ~rmask);
                         }
                     }
@@ -877,7 +886,7 @@ __global__ __launch_bounds__(HP_T, 4) void hgetf2_win_kernel(HpArgs a) {   // 4 
                 row[j] = (mw & rmask) | (dw & ~rmask); // :109
                 if (j + 1 < cols) {
                     const unsigned xw = xw0;
-                    const unsigned y = pk_elim(xw, m2, ujn);
+                    const unsigned y = pk_elim<FUSED>(xw, m2, ujn);
                     const unsigned nw = (y & rmask) | (xw & ~rmask);
                     row[j + 1] = nw;
                     if (pa > j) k0 = row_key32(nw & 0xFFFFu, pa, j + 1);
@@ -965,19 +974,25 @@ int launch_hdiv(mpf_ctx *c, const uint16_t *a, const uint16_t *b, uint16_t *q, i
 static int hp_setup(mpf_ctx *c) {
     if (c->hp_resident_per_cu >= 0 && (c->attr_done & ATTR_HP)) return 0;
     MPF_HIP_TRY(c, hipSetDevice(c->device));   // function attributes belong to the device they were set on
-    MPF_HIP_TRY(c, hipFuncSetAttribute((const void *)hgetf2_lds_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MPF_HIP_TRY(c, hipFuncSetAttribute((const void *)hgetf2_lds_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    // (both arithmetic contracts of every form: option fp16_fused picks the instantiation at each launch.  The residency figures
+    //  below are asked for the C2 forms and hold for the C2f ones: the same LDS, and no more registers -- 96 against 112 in the
+    //  full-slab forms, 127 against 126 in the window form, whose launch bound caps both at 128)
+    const void *const forms[] = {
+        (const void *)hgetf2_lds_kernel<256>, (const void *)hgetf2_lds_kernel<256, false, false, true>,
+        (const void *)hgetf2_lds_kernel<128>, (const void *)hgetf2_lds_kernel<128, false, false, true>,
+        (const void *)hgetf2_lds_kernel<256, false, true>, (const void *)hgetf2_lds_kernel<256, false, true, true>,
+        (const void *)hgetf2_win_kernel<false>, (const void *)hgetf2_win_kernel<true>,
 #ifdef MPF_PROBE
-    MPF_HIP_TRY(c, hipFuncSetAttribute((const void *)hgetf2_lds_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        (const void *)hgetf2_lds_kernel<256, true>, (const void *)hgetf2_lds_kernel<256, true, false, true>,
 #endif
-    MPF_HIP_TRY(c, hipFuncSetAttribute((const void *)hgetf2_win_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MPF_HIP_TRY(c, hipFuncSetAttribute((const void *)hgetf2_lds_kernel<256, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    };
+    for (const void *f : forms) MPF_HIP_TRY(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)hgetf2_lds_kernel<256>, HP_T, HpCarve<256>::LDS_BYTES) != hipSuccess)
         per_cu = 0;
     c->hp_resident_per_cu = per_cu;
     int win_per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&win_per_cu, (const void *)hgetf2_win_kernel, HP_T, HwCarve::LDS_BYTES) != hipSuccess)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&win_per_cu, (const void *)hgetf2_win_kernel<false>, HP_T, HwCarve::LDS_BYTES) != hipSuccess)
         win_per_cu = 0;
     c->hp_win_per_cu = win_per_cu;
     // What a workgroup of the gated interchange kernel leaves of its CU (the room is derived, not a measured
@@ -992,7 +1007,7 @@ static int hp_setup(mpf_ctx *c) {
         hipFuncAttributes ff, fw;
         int wl = 0, wv = 0, wt = 0;
         if (laswp_gated_footprint(&wl, &wv, &wt) == 0 && hipFuncGetAttributes(&ff, (const void *)hgetf2_lds_kernel<256>) == hipSuccess &&
-            hipFuncGetAttributes(&fw, (const void *)hgetf2_win_kernel) == hipSuccess) {
+            hipFuncGetAttributes(&fw, (const void *)hgetf2_win_kernel<false>) == hipSuccess) {
             auto gran = [](int r) { return (r + 7) / 8 * 8; };
             auto fits = [&](int n, int lds_one, int regs_one) {
                 const long long hole = (160 * 1024 - (long long)wl) / 2;                       // worst case: the waiter sits in the middle
@@ -1109,18 +1124,21 @@ int launch_hgetf2(mpf_ctx *c, const double *A64, int64_t lda, uint16_t *P16, int
         const int dv = c->device >= 0 && c->device < 64 ? c->device : 0;
         if (!hp_last[dv]) MPF_HIP_TRY(c, hipEventCreateWithFlags(&hp_last[dv], hipEventDisableTiming));
         else MPF_HIP_TRY(c, hipStreamWaitEvent(c->stream, hp_last[dv], 0));
-#ifdef MPF_PROBE
-        if (c->tune.hp_stamp && R == 256) hgetf2_lds_kernel<256, true><<<G, HP_T, HpCarve<256>::LDS_BYTES, c->stream>>>(a);
-        else
-#endif
-        if (R == 128) hgetf2_lds_kernel<128><<<G, HP_T, HpCarve<128>::LDS_BYTES, c->stream>>>(a);
-        else
         // the column-window form (76 KB of LDS: shares its CU) covers what the factorization chain asks for: an fp64 source,
-        // no fp16 copy of the factored panel
-        if (form == 1) hgetf2_win_kernel<<<G, HP_T, HwCarve::LDS_BYTES, c->stream>>>(a);
-        else if (local) hgetf2_lds_kernel<256, false, true><<<8 * (G + 2), HP_T, HpCarve<256>::LDS_BYTES, c->stream>>>(a);
-        else
-        hgetf2_lds_kernel<256><<<G, HP_T, HpCarve<256>::LDS_BYTES, c->stream>>>(a);
+        // no fp16 copy of the factored panel.  Every form exists for both arithmetic contracts (C2 / C2f): a template
+        // parameter, read from option fp16_fused here, at the launch -- nothing in the column step branches on it.
+        auto go = [&](auto fused) {
+            constexpr bool F = decltype(fused)::value;
+#ifdef MPF_PROBE
+            if (c->tune.hp_stamp && R == 256) hgetf2_lds_kernel<256, true, false, F><<<G, HP_T, HpCarve<256>::LDS_BYTES, c->stream>>>(a);
+            else
+#endif
+            if (R == 128) hgetf2_lds_kernel<128, false, false, F><<<G, HP_T, HpCarve<128>::LDS_BYTES, c->stream>>>(a);
+            else if (form == 1) hgetf2_win_kernel<F><<<G, HP_T, HwCarve::LDS_BYTES, c->stream>>>(a);
+            else if (local) hgetf2_lds_kernel<256, false, true, F><<<8 * (G + 2), HP_T, HpCarve<256>::LDS_BYTES, c->stream>>>(a);
+            else hgetf2_lds_kernel<256, false, false, F><<<G, HP_T, HpCarve<256>::LDS_BYTES, c->stream>>>(a);
+        };
+        if (c->tune.fp16_fused) go(std::true_type{}); else go(std::false_type{});
         MPF_HIP_TRY(c, hipGetLastError());
         MPF_HIP_TRY(c, hipEventRecord(hp_last[dv], c->stream));
     }

@@ -14,7 +14,8 @@
 //              still read the old pivot row and the old row j): their new contents go to two side rows, which the next
 //              search launch reads where it needs them and copies into the panel.
 // It is the slow, always-valid path (the reference itself pays five grid barriers per column); per-element arithmetic and the
-// pivot tie-break are bit-identical to the LDS kernel and the oracle.  Option generic_fused = 0 keeps the four-launch form.
+// pivot tie-break are bit-identical to the LDS kernel and the oracle.  Option generic_fused = 0 keeps the four-launch form
+// (a fusion of LAUNCHES; it has nothing to do with option fp16_fused, the fused multiply-add of contract C2f, which both forms take).
 #include "mpf_internal.h"
 #include "fp16_device.h"
 
@@ -84,7 +85,18 @@ __global__ __launch_bounds__(GP_T) void gp_scale_kernel(unsigned short *P, long 
     cj[r] = h_bits(hdiv_ieee(bits_h(cj[r]), bits_h(cj[j])));
 }
 
-// hgetf2_kernel.cu:112-114: a[row][k] -= m * a[j][k], product and difference rounded separately (no fma: contract C2)
+// hgetf2_kernel.cu:113 on one element: x - m * u with product and difference rounded separately (contract C2; the file is
+// built with -ffp-contract=off: v_mul_f16, v_sub_f16), or -- FUSED, contract C2f, option fp16_fused -- fma(-m, u, x) rounded
+// once (v_fma_f16), written out because the compiler may not contract
+template <bool FUSED>
+__device__ __forceinline__ unsigned short gp_elim(unsigned short x, _Float16 m, unsigned short u) {
+    if (FUSED) return h_bits(__builtin_fmaf16(-m, bits_h(u), bits_h(x)));
+    const _Float16 t = m * bits_h(u);
+    return h_bits(bits_h(x) - t);
+}
+
+// hgetf2_kernel.cu:112-114: a[row][k] -= m * a[j][k]
+template <bool FUSED>
 __global__ __launch_bounds__(GP_T) void gp_update_kernel(unsigned short *P, long long ldp, int rows, int cols, int j) {
     __shared__ unsigned short u[GP_CH];
     const int k0 = j + 1 + blockIdx.y * GP_CH;
@@ -96,8 +108,7 @@ __global__ __launch_bounds__(GP_T) void gp_update_kernel(unsigned short *P, long
     const int kn = (cols - k0) < GP_CH ? (cols - k0) : GP_CH;
     for (int kk = 0; kk < kn; ++kk) {
         unsigned short *x = P + r + (long long)(k0 + kk) * ldp;
-        const _Float16 t = m * bits_h(u[kk]); // v_mul_f16 (file is built with -ffp-contract=off)
-        *x = h_bits(bits_h(*x) - t);           // v_sub_f16
+        *x = gp_elim<FUSED>(*x, m, u[kk]);
     }
 }
 
@@ -127,6 +138,7 @@ __global__ __launch_bounds__(GP_T) void gp_search2_kernel(unsigned short *P, lon
         }
 }
 
+template <bool FUSED>
 __global__ __launch_bounds__(GP_T) void gp_update2_kernel(unsigned short *P, long long ldp, int rows, int cols, int j,
                                                          const unsigned long long *__restrict__ cand, int nblocks, int *ipiv, int ipiv_offset,
                                                          unsigned short *__restrict__ top, unsigned short *__restrict__ piv, int *pinfo) {
@@ -154,7 +166,7 @@ __global__ __launch_bounds__(GP_T) void gp_update2_kernel(unsigned short *P, lon
             const _Float16 mp = hdiv_ieee(bits_h(P[j + (long long)j * ldp]), ujj);
             unsigned short v = jrow[threadIdx.x];
             if (k == j) v = h_bits(mp);
-            else if (k > j) { const _Float16 t = mp * bits_h(u[threadIdx.x]); v = h_bits(bits_h(v) - t); }
+            else if (k > j) v = gp_elim<FUSED>(v, mp, u[threadIdx.x]);
             piv[k] = v;
         }
     }
@@ -174,10 +186,7 @@ __global__ __launch_bounds__(GP_T) void gp_update2_kernel(unsigned short *P, lon
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int k = c0 + kb + i;
-            if (k > j && k < cols) {
-                const _Float16 t = mr * bits_h(u[kb + i]);                    // v_mul_f16 (file is built with -ffp-contract=off)
-                P[r + (long long)k * ldp] = h_bits(bits_h(xv[i]) - t);        // v_sub_f16
-            }
+            if (k > j && k < cols) P[r + (long long)k * ldp] = gp_elim<FUSED>(xv[i], mr, u[kb + i]);
         }
     }
 }
@@ -222,6 +231,7 @@ int launch_hgetf2_generic(mpf_ctx *c, const double *A64, int64_t lda, uint16_t *
         dim3 g((unsigned)nblk0, (unsigned)cols);
         gp_convert_kernel<<<g, GP_T, 0, c->stream>>>(A64, lda, W, ldw, rows);
     }
+    const bool fused = c->tune.fp16_fused != 0;   // contract C2f instead of C2 in the rank-1 step, read at each launch
     if (c->tune.generic_fused) {
         unsigned short *top = (unsigned short *)(c->gcand + nblk0), *piv = top + cols;
         int *pinfo = (int *)(top + 2 * (size_t)cols);   // 4-byte aligned: top is 8-byte aligned, 2 * cols fp16 values in front
@@ -231,7 +241,8 @@ int launch_hgetf2_generic(mpf_ctx *c, const double *A64, int64_t lda, uint16_t *
             if (j == cols) break;
             const int gb = (rows - j - 1 + GP_T - 1) / GP_T > 0 ? (rows - j - 1 + GP_T - 1) / GP_T : 1;
             dim3 g((unsigned)gb, (unsigned)((cols + GP_CH - 1) / GP_CH));
-            gp_update2_kernel<<<g, GP_T, 0, c->stream>>>(W, ldw, rows, cols, j, c->gcand, nblk, d_ipiv, ipiv_offset, top, piv, pinfo);
+            if (fused) gp_update2_kernel<true><<<g, GP_T, 0, c->stream>>>(W, ldw, rows, cols, j, c->gcand, nblk, d_ipiv, ipiv_offset, top, piv, pinfo);
+            else gp_update2_kernel<false><<<g, GP_T, 0, c->stream>>>(W, ldw, rows, cols, j, c->gcand, nblk, d_ipiv, ipiv_offset, top, piv, pinfo);
         }
         MPF_HIP_TRY(c, hipGetLastError());
         return 0;
@@ -247,7 +258,8 @@ int launch_hgetf2_generic(mpf_ctx *c, const double *A64, int64_t lda, uint16_t *
             const int right = cols - j - 1;
             if (right > 0) {
                 dim3 g((unsigned)gb, (unsigned)((right + GP_CH - 1) / GP_CH));
-                gp_update_kernel<<<g, GP_T, 0, c->stream>>>(W, ldw, rows, cols, j);
+                if (fused) gp_update_kernel<true><<<g, GP_T, 0, c->stream>>>(W, ldw, rows, cols, j);
+                else gp_update_kernel<false><<<g, GP_T, 0, c->stream>>>(W, ldw, rows, cols, j);
             }
         }
     }

@@ -366,6 +366,7 @@ int mpf_factor_dist(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_
         MPF_HIP_TRY(c, hipMemcpyAsync(&c->ws->info, &imax0, sizeof(int), hipMemcpyHostToDevice, c->stream));
         mpf_stats stw{};
         stw.n = N; stw.nb = nb; stw.superpanel = 1;
+        stw.fp16_fused = c->tune.fp16_fused != 0;
         MPF_HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
         rc = factor_dist_wide(c, d_Aloc, ldloc, N, nb, d_ipiv, dist, o, L, bcast_fn, user, stw);
         hipEventRecord(c->ev1, c->stream);
@@ -452,6 +453,7 @@ int mpf_factor_dist(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_
     if (rc) return rc;
     mpf_stats st{};
     st.n = N; st.nb = nb; st.superpanel = sb;
+    st.fp16_fused = c->tune.fp16_fused != 0;   // (every rank's own option: the ranks must agree on it, include/mpf_c.h)
     hipStream_t S = c->stream, P = (o.no_lookahead || !c->pstream) ? c->stream : c->pstream;
     const bool two = P != S;
     EvPool ev(c);

@@ -49,6 +49,7 @@ const OptDesc kOpts[] = {
     OPT_I(dist_instalments, "MPF_DIST_INSTALMENTS", 0, 1),
     OPT_L(dist_instalment_min_bytes, "MPF_DIST_INSTALMENT_MIN_BYTES", 0, 1ll << 40),
     OPT_I(generic_fused, "MPF_GENERIC_FUSED", 0, 1),
+    OPT_I(fp16_fused, "MPF_FP16_FUSED", 0, 1),
     OPT_I(fp64_rowmajor, "MPF_FP64_ROWMAJOR", 0, 1),
     OPT_L(fp64_rowmajor_min_n, "MPF_FP64_ROWMAJOR_MIN_N", 0, 1ll << 40),
     OPT_I(trsm_laswp_fused, "MPF_TRSM_LASWP_FUSED", 0, 1),
@@ -1519,6 +1520,7 @@ int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, 
     mpf_stats st{};
     st.n = N; st.nb = nb; st.superpanel = sb;
     st.pivot_search = piv64;
+    st.fp16_fused = piv64 ? 0 : (c->tune.fp16_fused != 0);   // what ran: the fp64 pivot rules run no fp16 panel
     const bool lookahead = !o.sync_timing && !o.no_lookahead && !c->tune.no_lookahead && c->pstream != nullptr;
     // the row-major working copy of the fp64 mode is allocated BEFORE the clock starts (a context's first call pays hipMalloc
     // of N x N doubles once; ms_total is the factorization)

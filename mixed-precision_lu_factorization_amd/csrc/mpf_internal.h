@@ -81,6 +81,8 @@ struct MpfTuning {
     int dpanel_fused_form = 1;           // MPF_DPANEL_FUSED=0: fp64 panel without the fused update + sub-panel launches
     int dist_instalments = 1;            // MPF_DIST_INSTALMENTS=0: the panel message of mpf_factor_dist always travels in one broadcast
     long long dist_instalment_min_bytes = 8ll << 20; // MPF_DIST_INSTALMENT_MIN_BYTES: panels below this go in one broadcast
+    int fp16_fused = 0;                  // MPF_FP16_FUSED=1: the fp16 pivot panel eliminates with ONE fused multiply-add per element, fma(-m, u, x) rounded once (contract C2f)
+                                         // instead of a rounded product and a rounded difference (C2): other pivots, other factors.  Read at each launch of a pivot kernel
     int generic_fused = 1;               // MPF_GENERIC_FUSED=0: generic pivot path with four launches per column instead of two
     int fp64_rowmajor = 1;               // MPF_FP64_ROWMAJOR=0: fp64 mode updates the column-major matrix in place (no row-major working copy)
     long long fp64_rowmajor_min_n = 8192;// MPF_FP64_ROWMAJOR_MIN_N: smaller matrices stay in place (the copy's extra launches cost more than they save)
