@@ -641,6 +641,42 @@ int mpf_gesvxx_block(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t N, in
                      double *berr, double *rpvgrw,         /* host, nrhs / 1, optional */
                      mpf_gesvx_stats *stats, mpf_ir_stats *ir, mpf_gerfsx_stats *xr /* host, optional */);
 
+/* ---- inverse and determinant from the factors (build extension; LAPACK dgetri, LINPACK dgedi's determinant) ---------------------------
+ * Inverse: d_LU / d_ipiv are the factors P A' = L U of A' = Dr A Dc as mpf_factor_dev leaves them (d_r, d_c: device, N doubles each,
+ * exact powers of two as mpf_geequ returns them; NULL: the identity).  d_inv (N x N column-major, ldinv >= N) receives
+ *   inv(A) = Dc inv(A') Dr = Dc inv(U) inv(L) P Dr,
+ * out of place: d_LU and d_ipiv are preserved, rows N .. ldinv - 1 of d_inv are not touched, and d_inv must not overlap d_LU (-1).
+ * Any factors are accepted: on fp16 or fp16x3 factors the result is the inverse of the matrix those factors multiply to, no more
+ * accurate than they are; the call does no refinement.
+ * Algorithm: right-looking over d_inv itself in blocks of 256, about 4/3 N^3 flops as dgetri, the O(N^3) part on mpf_dgemm_minus's
+ * fp64 MFMA kernel with K = 256 (no solve against an identity, no N x N workspace: the scratch is ceil(N / 256) 256^2 doubles beside
+ * the solves' 256 x 256 block inverses).
+ *   1. d_inv = I.  Block row k from the last one up: X(k, k:) = inv(U_kk) R(k, k:), then R(0:k, k:) -= U(0:k, k) X(k, k:): inv(U) in
+ *      the upper triangle, N^3 / 3 flops, none on the zero triangle.
+ *   2. X L = inv(U).  Block column j from the last one down: X(:, j) = R(:, j) inv(L_jj), then R(:, 0:j) -= X(:, j) L(j, 0:j): N^3 flops.
+ *   3. dgetri's column interchanges (j = N - 2 .. 0: columns j and ipiv[j] - 1), composed into one permutation, and the scales
+ *      x_ij <- (c_i x_ij) r_j in one pass.
+ * Contract: every element has one fixed operation order (the block-inverse products: one accumulator from zero, k ascending; the
+ * updates: mpf_dgemm_minus's chain); two calls return the same bits; the bits do not depend on ldlu or ldinv; with scales the result
+ * equals (c_i y_ij) r_j bit for bit, Y the call without scales, as long as nothing over- or underflows.
+ * Returns 0; i + 1 when u_ii is the first zero on U's diagonal -- checked before anything is written to d_inv, which is then left
+ * untouched (dgetri's / dtrtri's rule; only the context's own solve scratch may have been allocated); < 0 on error.  N = 0: returns 0, no work.  Synchronises. */
+int mpf_getri(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv, int64_t N,
+              const double *d_r, const double *d_c,   /* device, N each, optional: LU = factors of Dr A Dc */
+              double *d_inv, int64_t ldinv);
+
+/* Determinant of A from the same factors and scales: det(A) = *mant 2^*expo with |*mant| in [0.5, 1) or *mant = 0 (LINPACK's form: no
+ * over- or underflow at any N).  One fixed order, every step exact but the products of two numbers in [0.5, 1):
+ *   (m_i, e_i) = frexp(u_ii); with scales e_i is reduced by the exponents of r_i and c_i (log2 of a power of two);
+ *   chunks of 256 consecutive i, ascending; inside a chunk from p = 1, e = 0:  p = p m_i, (p, k) = frexp(p), e += k + e_i;
+ *   the chunk results are combined in ascending order from (1, 0) by the same step;
+ *   the sign flips once per i with ipiv[i] != i + 1.
+ * Any non-finite u_ii gives (NaN, 0); otherwise a zero u_ii gives (0, 0) and return value 0.  N = 0 gives (0.5, 1).  A restatement in
+ * any IEEE arithmetic gives the same bits (tests/getri_model.py).  One launch, N loads.  *mant, *expo on the host.  Returns 0, < 0 on
+ * error.  Synchronises. */
+int mpf_getdet(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv, int64_t N,
+               const double *d_r, const double *d_c, double *mant, int64_t *expo /* host */);
+
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block
  * b / world; d_Aloc is the rank's N x (local columns) column-major matrix (ldloc >= N), d_ipiv the full pivot vector (N int32,

@@ -36,6 +36,7 @@ C_ABI_SYMBOLS = [
     "mpf_dgetf2_piv", "mpf_solve_gmres_ir_block", "mpf_dgetf2_tp",
     "mpf_residual_x", "mpf_gerfsx",
     "mpf_gerpvgrw", "mpf_gerfsx_scaled", "mpf_gesvxx_block",
+    "mpf_getri", "mpf_getdet",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -200,6 +201,8 @@ def load_library(probe=False):
     L.mpf_gesvxx_block.argtypes = [vp, vp, i64, i64, i32, vp, vp, i32, vp, i64, vp, i64, i32, i32, i32, dbl, i32, dbl, i32, vp, vp,
                                    C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(MpfGesvxStats),
                                    C.POINTER(MpfIrStats), C.POINTER(MpfGerfsxStats)]
+    L.mpf_getri.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64]
+    L.mpf_getdet.argtypes = [vp, vp, i64, vp, i64, vp, vp, C.POINTER(dbl), C.POINTER(i64)]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -951,3 +954,59 @@ class MPFContext:
         out = (X, en[:nrhs], ec[:nrhs], be[:nrhs] if want_berr else None, pg.value if want_rpvgrw else None, st, list(ist)[:nrhs],
                list(xst)[:nrhs], work, ipiv)
         return out + (r, c) if want_scales else out
+
+    # ---- inverse and determinant from the factors (include/mpf_c.h: mpf_getri, mpf_getdet) ---------------------------------------------
+    def _factor_args(self, LU, ipiv, r, c):
+        """The argument checks getri and getdet share: a square float64 LU, int32 pivots and float64 scales of its size, all on the device."""
+        t = self.torch
+        n = LU.shape[0]
+        assert LU.dim() == 2 and LU.shape[1] == n and LU.dtype == t.float64 and LU.is_cuda
+        assert ipiv.dtype == t.int32 and ipiv.is_cuda and ipiv.dim() == 1 and ipiv.numel() == n and ipiv.is_contiguous(), \
+            "ipiv: a contiguous int32 device tensor of N entries"
+        for s in (r, c):
+            assert s is None or (s.dtype == t.float64 and s.is_cuda and s.dim() == 1 and s.numel() == n and s.is_contiguous()), \
+                "r, c: contiguous float64 device tensors of N entries, or None"
+        return n
+
+    def getri(self, LU, ipiv, r=None, c=None, out=None):
+        """mpf_getri (LAPACK dgetri): inv(A) from the factors LU, ipiv of Dr A Dc (r, c: the scale vectors as device tensors, or None
+        for the identity), out of place.  out: a column-major N x N tensor to receive it (a new one when None).  Returns (inv, info):
+        info = i + 1 when u_ii is the first zero on U's diagonal -- `out` is then untouched -- else 0."""
+        self._bind()
+        n = self._factor_args(LU, ipiv, r, c)
+        if out is None:
+            out = self.colmajor(n, n)
+        assert out.shape == (n, n) and out.dtype == self.torch.float64 and out.is_cuda
+        rc = self.L.mpf_getri(self.h, _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n, _ptr(r), _ptr(c), _ptr(out), _colmajor_ld(out))
+        return out, self._check(rc, "mpf_getri")
+
+    def getdet(self, LU, ipiv, r=None, c=None):
+        """mpf_getdet: det(A) = mant * 2**expo from the factors of Dr A Dc, |mant| in [0.5, 1) or 0 (no overflow at any N).  Returns
+        (mant, expo) as a float and an int; (0.0, 0) for a singular U, (nan, 0) for a non-finite one."""
+        self._bind()
+        n = self._factor_args(LU, ipiv, r, c)
+        mant, expo = C.c_double(0), C.c_int64(0)
+        rc = self.L.mpf_getdet(self.h, _ptr(LU), _colmajor_ld(LU), _ptr(ipiv), n, _ptr(r), _ptr(c), C.byref(mant), C.byref(expo))
+        self._check(rc, "mpf_getdet")
+        return mant.value, expo.value
+
+    def slogdet(self, LU, ipiv, r=None, c=None):
+        """(sign, log|det A|) as numpy.linalg.slogdet returns them, from getdet: log|mant| + expo ln 2 on the host -- one rounded
+        logarithm, not N.  (0.0, -inf) for a singular U."""
+        import math
+        mant, expo = self.getdet(LU, ipiv, r, c)
+        if mant == 0.0:
+            return 0.0, -math.inf
+        if math.isnan(mant):
+            return math.nan, math.nan
+        return math.copysign(1.0, mant), math.log(abs(mant)) + expo * math.log(2.0)
+
+    def inv(self, A, nb=256, **factor_kw):
+        """inv(A): factors a copy of A (factor's keyword arguments apply), then getri.  Raises MPFError when U has a zero pivot."""
+        W = self.colmajor(A.shape[0], A.shape[0])
+        W.copy_(A)
+        ipiv, info = self.factor(W, nb, **factor_kw)
+        X, info2 = self.getri(W, ipiv)
+        if info or info2:
+            raise MPFError(f"inv: the matrix is singular (zero pivot {info or info2})")
+        return X

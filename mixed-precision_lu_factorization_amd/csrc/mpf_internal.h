@@ -210,6 +210,9 @@ struct mpf_ctx {
     // blocked GMRES-IR (blk_gmres_core, solve_gmres.hip; its basis lives in `krylov`): partials of the orthogonalisation, its results
     // [h | h' | ||w||^2], and what the host sends per step ([scale | live] per column; [y | counts] per outer step)
     Buf<double> gm_part, gm_out, gm_ctl;
+    // inverse and determinant (mpf_getri.cpp, getri.hip): ceil(N / 256) x 256 x 256 doubles -- L's block inverses transposed, then the
+    // 256-row panel of the interchange pass; mpf_getdet's chunk results
+    Buf<double> getri_buf;
     // factored 32x32 diagonal tiles of the fp64 panel, parked here until every workgroup of the sub-panel launches has
     // read the UNfactored tile from the matrix (dpanel.hip); one tile per 32 panel columns, grown on demand
     Buf<double> dtiles;
@@ -485,6 +488,16 @@ int launch_gmres_ortho(mpf_ctx *c, const double *V, int64_t vs, int ns, double *
 int launch_gmres_append(mpf_ctx *c, const double *src, const double *scale, double *dst, int64_t ldt, int64_t n, int ntiles);   // dst = src * scale[j] where scale[j] != 0
 int launch_gmres_xupdate(mpf_ctx *c, const double *V, int64_t vs, const double *y, const int *cnt, double *X, int64_t ldt, int64_t n,
                          int ntiles);   // X[:, j] += sum_{i < cnt[j]} y[i * tc + j] V_i[:, j]
+// inverse and determinant from the factors (getri.hip; driver in mpf_getri.cpp).  launch_getri_tri: the block-inverse products in place
+// on W -- left: W[r0 .. r0 + w, c0 .. c0 + extent) = G W[same]; right: W[r0 .. r0 + extent, c0 .. c0 + w) = W[same] G^T, G the
+// 256 x 256 upper triangular operand (inv(U_kk), or inv(L_jj) transposed by launch_getri_transpose).  launch_getri_permute:
+// W[:, j] <- cs .* W[:, src[j]] r[j] through the 256 x n panel T
+int launch_getri_init(mpf_ctx *c, double *W, int64_t ld, int64_t n);
+int launch_getri_transpose(mpf_ctx *c, const double *inv, double *out, int64_t nblk);
+int launch_getri_tri(mpf_ctx *c, bool right, const double *G, double *W, int64_t ld, int64_t r0, int64_t c0, int w, int64_t extent);
+int launch_getri_permute(mpf_ctx *c, double *W, int64_t ld, int64_t n, const int *src, const double *r, const double *cs, double *T);
+int launch_getdet(mpf_ctx *c, const double *LU, int64_t ld, const int *ipiv, int64_t n, const double *r, const double *cs, double *part,
+                  double *out);
 // mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
 int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 
