@@ -94,6 +94,8 @@ typedef struct mpf_stats {
                                    (event_timers = 2 for the phase timers) */
     int32_t fp16_fused;         /* the fp16 pivot panel's elimination that ran: 0 rounded product, rounded difference (contract C2), 1 one fused
                                    multiply-add (contract C2f, option fp16_fused); 0 under pivot_search 1 and 2, which run no fp16 panel */
+    int32_t lazy_onepass_blocks; /* look-ahead schedules: column blocks whose deferred left-hand interchanges ran in one pass, in place (option
+                                   lazy_gather = 2; the others went through the temporary: option lazy_onepass_max_rows) */
 } mpf_stats;
 
 /* ---- lifetime -------------------------------------------------------------------------- */
@@ -110,7 +112,7 @@ int mpf_get_stats(mpf_ctx *ctx, mpf_stats *out);
  * "superpanel_fp16", see csrc/mpf_internal.h MpfTuning for the list); afterwards only these calls change them, so contexts
  * on different host threads are independent.  Names: safe_pivots, chain_pipeline, chain_pipeline_below, fp16_work32,
  * superpanel_fp16, superpanel_fp64, no_lookahead, verbose, timeline, hp_spin_limit, hp_gate_ticks, hp_acq_fence, hgemm_pad,
- * hgemm_split_pad, hgemm_big, hgemm_big_tile, dgemm_dma, generic_fused, pivot_fp64 (0 .. 2: the pivot_search every driver that factors internally uses), fp64_rowmajor, fp64_rowmajor_min_n, dist_instalments, dist_instalment_min_bytes, lazy_gather, dpanel_fused_form, trsm_laswp_fused,
+ * hgemm_split_pad, hgemm_big, hgemm_big_tile, dgemm_dma, generic_fused, pivot_fp64 (0 .. 2: the pivot_search every driver that factors internally uses), fp64_rowmajor, fp64_rowmajor_min_n, dist_instalments, dist_instalment_min_bytes, lazy_gather (0 .. 2), lazy_onepass_max_rows, dpanel_fused_form, trsm_laswp_fused,
  * fp16_fused (0 / 1, MPF_FP16_FUSED; default 0.  RESULTS DEPEND ON IT.  The rank-1 step of the fp16 pivot panel, hgetf2_kernel.cu:113
  * `panel[k*ld+row] -= multiplier * panel[k*ld+j]`: 0 = contract C2, the product rounded to fp16, then the difference rounded to fp16 -- what the
  * reference computes when nvcc does not contract, as under the `-G -O0` recipe this project's parity is stated for; 1 = contract C2f,

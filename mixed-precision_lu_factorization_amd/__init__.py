@@ -56,7 +56,8 @@ class MpfStats(C.Structure):
                 ("pivot_path", C.c_int32), ("gemm_flops", C.c_double), ("gemm_bytes", C.c_double),
                 ("ms_gemm_big", C.c_double), ("gemm_big_flops", C.c_double), ("gemm_big_bytes", C.c_double),
                 ("ms_cvt", C.c_double), ("ms_blockrow", C.c_double), ("gemm_big_launches", C.c_int32), ("host_rows_streamed", C.c_int32),
-                ("host_late_segments", C.c_int32), ("pivot_search", C.c_int32), ("fp16_fused", C.c_int32)]
+                ("host_late_segments", C.c_int32), ("pivot_search", C.c_int32), ("fp16_fused", C.c_int32),
+                ("lazy_onepass_blocks", C.c_int32)]
 
 
 class MpfIrStats(C.Structure):

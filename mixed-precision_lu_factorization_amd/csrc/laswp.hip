@@ -418,12 +418,12 @@ __global__ __launch_bounds__(512) void lazy_update_map_kernel(int *F, int *G, co
 }
 // T[d - r0, c] = A[G[d], c] for rows d >= r0 of `w` columns (thread = destination row: coalesced writes; the scattered 8-byte
 // READS of a column segment find their sectors in the caches after the first touch, where scattered writes end as partial
-// sectors in HBM)
+// sectors in HBM).  g0 = the row G's first element stands for (0: the whole map; r0: a snapshot of the one-pass form below)
 __global__ __launch_bounds__(256) void lazy_gather_kernel(const double *__restrict__ A, long long lda, long long n, long long r0,
-                                                         int w, const int *__restrict__ G, double *__restrict__ T, long long ldt) {
+                                                         int w, const int *__restrict__ G, long long g0, double *__restrict__ T, long long ldt) {
     const long long d = r0 + (long long)blockIdx.x * 256 + threadIdx.x;
     if (d >= n) return;
-    const long long sr = G[d];
+    const long long sr = G[d - g0];
     const int c0 = blockIdx.y * 16;
 #pragma unroll 8
     for (int c = c0; c < c0 + 16 && c < w; ++c) T[(d - r0) + (long long)c * ldt] = A[sr + (long long)c * lda];
@@ -447,6 +447,170 @@ __global__ __launch_bounds__(256) void lazy_copyback_kernel(double *__restrict__
     for (int c = c0; c < c0 + 16 && c < w; ++c) A[r + (long long)c * lda] = T[(r - r0) + (long long)c * ldt];
 }
 
+// ---- one-pass form (option lazy_gather = 2; world == 1) ----------------------------------------------------------------
+// The walk above costs three dependent launches per panel and moves every element twice (through perm_tmp and back).  Here ONE
+// launch of one workgroup walks all the panels and keeps what the column blocks need: after every panel p with p % sb == 0 a
+// SNAPSHOT of G for the rows >= p * nb (snapshot q = p / sb, triangular storage, lazy_snap_offset), and a few launches (one per
+// power-of-two class of segment lengths) apply them all, in place: a workgroup owns one column of one block, takes the column's
+// whole segment through the block's snapshot into registers, and writes it back only after every load of the workgroup has
+// returned -- no temporary matrix, no copy-back.  N = 32768, nb = 256: 7.8 ms of kernels in 381 dependent launches -> 2.9 ms
+// in 6 (map 0.49, apply 2.43); DESIGN 4.3.
+constexpr int LAZY1_THREADS = 1024;
+constexpr int LAZY1_SLOTS = 32;     // most rows per thread: 64 data VGPRs of the 128 a wave of a 1024-thread workgroup may hold
+// first element of snapshot q (q = 1, 2, ...; rows >= q * step, step = sb * nb): sum over i < q of (n - i * step)
+__host__ __device__ inline long long lazy_snap_offset(long long n, long long step, long long q) {
+    return (q - 1) * n - step * ((q - 1) * q / 2);
+}
+__global__ __launch_bounds__(LAZY1_THREADS) void lazy_map_all_kernel(int *F, int *G, long long n, int nb, int npanels, int sb,
+                                                                    const MovedList *lists, int *snap) {
+    const int t = threadIdx.x;
+    for (long long i = t; i < n; i += LAZY1_THREADS) { F[i] = (int)i; G[i] = (int)i; }
+    __syncthreads();
+    for (int p = npanels - 1; p >= 1; --p) {
+        // F <- F o P, G = F^-1, as lazy_update_map_kernel
+        const MovedList *ml = lists + p;
+        int m = ml->n;
+        if (m > LASWP_MAXMOVED) m = LASWP_MAXMOVED;
+        int v = 0, s = 0;
+        if (t < m) { v = F[ml->dst[t]]; s = ml->src[t]; }
+        __syncthreads();
+        if (t < m) { F[s] = v; G[v] = s; }
+        __syncthreads();
+        if (p % sb) continue;
+        const long long r0 = (long long)p * nb;
+        int *sq = snap + lazy_snap_offset(n, (long long)sb * nb, p / sb);
+        for (long long d = r0 + t; d < n; d += LAZY1_THREADS) sq[d - r0] = G[d];
+        // (the next panel's writes to G come behind a barrier every wave reaches only with these reads done)
+    }
+}
+// Column j of the blocks [b0, b0 + gridDim.x / nb): A[d, j] = A[Gq[d], j] for the rows d >= r0 of its block, in place.  A is read
+// AND written through the same pointer (no __restrict__), and every load of the workgroup has returned before its first store.
+// SLOTS rows per thread: the segment has at most LAZY1_THREADS * SLOTS rows.
+// The segment comes in through LDS, in passes of LAZY1_LDS_ROWS consecutive source rows (coalesced loads); every thread picks from the
+// pass's image the elements of its destination rows whose source lies in it and keeps them in registers.  (Gathering A[Gq[d]]
+// straight from memory was measured first: the segments of the workgroups resident on an XCD -- 32 x 128 .. 256 KB -- do not
+// fit its 4-MB L2 together, a sector was fetched again for nearly every element of it: 19.2 GB fetched for 3.2 GB written,
+// 3.5 ms for the segments above 16384 rows at N = 32768, 1.9 ms this way.)  Neither the loads nor the LDS reads carry a
+// predicate (a clamped address instead): under one, each waited for the one before.  SLOTS = 32 (two passes, 64 data registers
+// live across them) spills 36 registers per lane under the 128 a 1024-thread workgroup leaves a wave: DESIGN 8 item 7.
+constexpr int LAZY1_LDS_ROWS = 16384;   // 128 KB of the CU's 160
+template <int SLOTS>
+__global__ __launch_bounds__(LAZY1_THREADS) void lazy_apply_all_kernel(double *A, long long lda, long long n, int nb, int sb, int b0,
+                                                                      const int *snap) {
+    constexpr int H = SLOTS * LAZY1_THREADS < LAZY1_LDS_ROWS ? SLOTS * LAZY1_THREADS : LAZY1_LDS_ROWS;   // source rows per pass
+    constexpr int PASSES = SLOTS * LAZY1_THREADS / H;
+    __shared__ double seg[H];
+    const int b = b0 + (int)(blockIdx.x / (unsigned)nb);
+    const long long q = b / sb + 1;                       // block b is owed the panels from q * sb on
+    const long long r0 = q * sb * nb;
+    const int rows = (int)(n - r0);                       // (<= SLOTS * LAZY1_THREADS)
+    const int *Gq = snap + lazy_snap_offset(n, (long long)sb * nb, q);
+    double *col = A + ((long long)b * nb + (long long)(blockIdx.x % (unsigned)nb)) * lda + r0;   // the segment's first element
+    const int t = threadIdx.x;
+    double v[SLOTS];
+    constexpr int GRP = SLOTS < 8 ? SLOTS : 8;            // index loads and LDS reads in flight together (bounds the registers)
+#pragma unroll
+    for (int pass = 0; pass < PASSES; ++pass) {
+        const int base = pass * H;
+        if (pass > 0) __syncthreads();                    // every thread has picked from the image before
+#pragma unroll
+        for (int j0 = 0; j0 < H / LAZY1_THREADS; j0 += GRP) {
+            double x[GRP];
+#pragma unroll
+            for (int j = 0; j < GRP; ++j) {
+                const int r = base + (j0 + j) * LAZY1_THREADS + t;
+                x[j] = col[(unsigned)(r < rows ? r : rows - 1) & (unsigned)(SLOTS * LAZY1_THREADS - 1)];   // (a 32-bit offset the compiler can see the size of)
+            }
+#pragma unroll
+            for (int j = 0; j < GRP; ++j) seg[(j0 + j) * LAZY1_THREADS + t] = x[j];
+            asm volatile("" ::: "memory");
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i0 = 0; i0 < SLOTS; i0 += GRP) {
+            int rel[GRP];
+            double x[GRP];
+#pragma unroll
+            for (int i = 0; i < GRP; ++i) {
+                const int d = (i0 + i) * LAZY1_THREADS + t;   // (row r0 + d)
+                rel[i] = Gq[(unsigned)(d < rows ? d : rows - 1) & (unsigned)(SLOTS * LAZY1_THREADS - 1)] - (int)r0 - base;
+            }
+#pragma unroll
+            for (int i = 0; i < GRP; ++i) {
+                x[i] = seg[(unsigned)rel[i] < (unsigned)H ? rel[i] : 0];
+                asm volatile("" : "+v"(x[i]));            // (the read stays unconditional: no branch around it)
+            }
+#pragma unroll
+            for (int i = 0; i < GRP; ++i)
+                if (PASSES == 1 || (unsigned)rel[i] < (unsigned)H) v[i0 + i] = x[i];
+            asm volatile("" ::: "memory");
+        }
+    }
+    // (every load of the column went into an LDS image that every thread has read behind a barrier: none is outstanding)
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < SLOTS; ++i) {
+        const int d = i * LAZY1_THREADS + t;
+        if (d < rows) col[(unsigned)d & (unsigned)(SLOTS * LAZY1_THREADS - 1)] = v[i];
+    }
+}
+template <int SLOTS>
+static void lazy_apply_launch(mpf_ctx *c, double *A, int64_t lda, int64_t N, int nb, int sb, int b0, int nblocks, const int *snap) {
+    lazy_apply_all_kernel<SLOTS><<<(unsigned)((int64_t)nblocks * nb), LAZY1_THREADS, 0, c->stream>>>(A, lda, N, nb, sb, b0, snap);
+}
+int64_t lazy_snap_elems(int64_t N, int nb, int npanels, int sb) {   // ints the snapshots of one factorization take
+    if (sb < 1) sb = 1;
+    return npanels < 2 ? 0 : lazy_snap_offset(N, (int64_t)sb * nb, (npanels - 1) / sb + 1);
+}
+// max_rows = option lazy_onepass_max_rows: a block whose segment is longer (at most LAZY1_THREADS * LAZY1_SLOTS rows fit a
+// workgroup's registers) goes through perm_tmp with the gather + copy-back kernels, its map read from the same snapshot.  The
+// segments get shorter from block to block, so the one-pass blocks are the later ones, [b1, nblk).
+static int launch_lazy_left_swaps_onepass(mpf_ctx *c, double *A, int64_t lda, int64_t N, int nb, int npanels, const MovedList *lists, int sb) {
+    const int64_t step = (int64_t)sb * nb;
+    const int Q = (npanels - 1) / sb;                    // snapshots 1 .. Q; blocks [0, Q * sb) are owed something
+    c->lazy_onepass_blocks = 0;
+    if (Q < 1) return 0;
+    const int64_t need = lazy_snap_elems(N, nb, npanels, sb);
+    if (c->lazy_snap.cap() < need) {                     // (mpf_factor_setup has sized it: only a caller that came another way gets here)
+        MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        MPF_HIP_TRY(c, c->lazy_snap.grow(need));
+    }
+    int *snap = c->lazy_snap;
+    lazy_map_all_kernel<<<1, LAZY1_THREADS, 0, c->stream>>>(c->Fmap, c->Fmap + N, N, nb, npanels, sb, lists, snap);
+    int64_t cap = c->tune.lazy_onepass_max_rows;
+    if (cap > (int64_t)LAZY1_THREADS * LAZY1_SLOTS) cap = (int64_t)LAZY1_THREADS * LAZY1_SLOTS;
+    const int nblk = Q * sb;
+    int b1 = nblk;
+    for (int b = 0; b < nblk; ++b) {
+        const int64_t q = b / sb + 1, r0 = q * step, rows = N - r0;
+        if (rows <= cap) { b1 = b; break; }
+        dim3 grid((unsigned)((rows + 255) / 256), (unsigned)((nb + 15) / 16));
+        double *Ab = A + (int64_t)b * nb * lda;
+        lazy_gather_kernel<<<grid, 256, 0, c->stream>>>(Ab, lda, N, r0, nb, snap + lazy_snap_offset(N, step, q), r0, c->perm_tmp, rows);
+        lazy_copyback_kernel<<<grid, 256, 0, c->stream>>>(Ab, lda, N, r0, nb, c->perm_tmp, rows);
+    }
+    // one launch per power-of-two class of segment lengths (the kernel's rows per thread), longest first: a class is a range of blocks
+    for (int b = b1; b < nblk;) {
+        const int64_t rows = N - (b / sb + 1) * step;
+        int slots = 2;
+        while ((int64_t)LAZY1_THREADS * slots < rows) slots *= 2;
+        int e = b + 1;
+        while (e < nblk && (N - (e / sb + 1) * step) * 2 > (int64_t)LAZY1_THREADS * slots) ++e;   // (slots = 2 takes every shorter segment too)
+        if (slots == 2) e = nblk;
+        switch (slots) {
+        case 32: lazy_apply_launch<32>(c, A, lda, N, nb, sb, b, e - b, snap); break;
+        case 16: lazy_apply_launch<16>(c, A, lda, N, nb, sb, b, e - b, snap); break;
+        case 8: lazy_apply_launch<8>(c, A, lda, N, nb, sb, b, e - b, snap); break;
+        case 4: lazy_apply_launch<4>(c, A, lda, N, nb, sb, b, e - b, snap); break;
+        default: lazy_apply_launch<2>(c, A, lda, N, nb, sb, b, e - b, snap); break;
+        }
+        b = e;
+    }
+    c->lazy_onepass_blocks = nblk - b1;
+    MPF_HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
 // sb > 1 (super-panels of sb panels, fp16 trailing modes): the schedule applies a panel's interchanges to the earlier
 // columns of its own super-panel right away (the deferred K = sb * nb update reads them), so column block b is only
 // owed the panels from the next super-panel on.
@@ -457,6 +621,8 @@ int launch_lazy_left_swaps(mpf_ctx *c, double *A, int64_t lda, int64_t N, int nb
     if (npanels < 2) return 0;
     if (sb < 1 || world > 1) sb = 1;
     const int gather = c->tune.lazy_gather;
+    c->lazy_onepass_blocks = 0;
+    if (gather == 2 && world == 1) return launch_lazy_left_swaps_onepass(c, A, lda, N, nb, npanels, lists, sb);
     int *Gmap = c->Fmap + N;
     lazy_init_map_kernel<<<(int)((N + 255) / 256), 256, 0, c->stream>>>(c->Fmap, Gmap, N);
     for (int p = npanels - 1; p >= 1; --p) {
@@ -470,7 +636,7 @@ int launch_lazy_left_swaps(mpf_ctx *c, double *A, int64_t lda, int64_t N, int nb
             const int w = nb;                      // blocks left of a panel are never the (possibly narrower) last one
             dim3 grid((unsigned)((rows + 255) / 256), (unsigned)((w + 15) / 16));
             double *Ab = A + (int64_t)(world > 1 ? b / world : b) * nb * lda;
-            if (gather) lazy_gather_kernel<<<grid, 256, 0, c->stream>>>(Ab, lda, N, r0, w, Gmap, c->perm_tmp, rows);
+            if (gather) lazy_gather_kernel<<<grid, 256, 0, c->stream>>>(Ab, lda, N, r0, w, Gmap, 0, c->perm_tmp, rows);
             else lazy_scatter_kernel<<<grid, 256, 0, c->stream>>>(Ab, lda, N, r0, w, c->Fmap, c->perm_tmp, rows);
             lazy_copyback_kernel<<<grid, 256, 0, c->stream>>>(Ab, lda, N, r0, w, c->perm_tmp, rows);
         }

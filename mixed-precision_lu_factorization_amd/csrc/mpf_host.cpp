@@ -44,7 +44,8 @@ const OptDesc kOpts[] = {
     OPT_I(hgemm_big_tile, "MPF_HGEMM_BIG_TILE", 0, 5),
     OPT_I(hgemm_mfma16, "MPF_HGEMM_MFMA16", 0, 1),
     OPT_I(dgemm_dma, "MPF_DGEMM_DMA", 0, 1),
-    OPT_I(lazy_gather, "MPF_LAZY_GATHER", 0, 1),
+    OPT_I(lazy_gather, "MPF_LAZY_GATHER", 0, 2),
+    OPT_I(lazy_onepass_max_rows, "MPF_LAZY_ONEPASS_MAX_ROWS", 0, 32768),
     OPT_I(dpanel_fused_form, "MPF_DPANEL_FUSED", 0, 1),
     OPT_I(dist_instalments, "MPF_DIST_INSTALMENTS", 0, 1),
     OPT_L(dist_instalment_min_bytes, "MPF_DIST_INSTALMENT_MIN_BYTES", 0, 1ll << 40),
@@ -635,7 +636,10 @@ static int factor_epilogue(const FactorArgs &f, int rc, bool sink, int sb, bool 
     hipStream_t S = c->stream;
     const int npanels = (int)((f.N + f.nb - 1) / f.nb);
     if (sink) sink_notify(c, npanels, S);
-    else if (!rc) rc = f.ev.timed(f.st.ms_laswp, S, [&] { return launch_lazy_left_swaps(c, f.d_A, f.lda, f.N, f.nb, npanels, c->lists, sb); });
+    else if (!rc) {
+        rc = f.ev.timed(f.st.ms_laswp, S, [&] { return launch_lazy_left_swaps(c, f.d_A, f.lda, f.N, f.nb, npanels, c->lists, sb); });
+        f.st.lazy_onepass_blocks = c->lazy_onepass_blocks;
+    }
     hipError_t se = sink_stream_wait(c, S);   // (hipStreamSynchronize unless a sink's thread is copying)
     hipError_t sp = side_streams ? sink_stream_wait(c, c->pstream) : hipSuccess;
     if (side_streams && c->tstream) { const hipError_t stt = sink_stream_wait(c, c->tstream); if (sp == hipSuccess) sp = stt; }
@@ -1480,6 +1484,7 @@ int mpf_factor_setup(mpf_ctx *c, int64_t N, int32_t nb, int32_t npanels, bool li
         // 2 * HP_MAXCOLS moved rows x N (or a rank's local) columns (fp32) of an interchange on the row-major working copy
         MPF_HIP_TRY(c, c->perm_tmp.grow(N * (int64_t)(nb > HP_MAXCOLS ? nb : HP_MAXCOLS)));
         MPF_HIP_TRY(c, c->Fmap.grow(2 * N));   // the map and its inverse
+        if (c->tune.lazy_gather == 2) MPF_HIP_TRY(c, c->lazy_snap.grow(lazy_snap_elems(N, nb, npanels, 1)));   // (super-panels keep fewer snapshots)
         MPF_HIP_TRY(c, hipMemsetAsync(c->lists, 0, (size_t)npanels * sizeof(MovedList), c->stream));
     }
     const int imax = INT_MAX;

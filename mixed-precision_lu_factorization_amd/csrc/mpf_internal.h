@@ -77,7 +77,10 @@ struct MpfTuning {
     int hgemm_big_tile = 0;              // MPF_HGEMM_BIG_TILE: form of the big-K fp16 update (launch_hgemm_ptrs): 0 = automatic, 1 / 2 = 128 x 256 tiles (one / two
                                          // workgroups per CU), 3 = round 3's kernel, 4 = hgemm_big_kernel everywhere, 5 = hgemm_pp_kernel everywhere
     int dgemm_dma = 1;                   // MPF_DGEMM_DMA=0: register-staged eight-wave fp64 update kernel (same bits)
-    int lazy_gather = 1;                 // MPF_LAZY_GATHER=0: deferred left-hand interchanges as scattered writes
+    int lazy_gather = 2;                 // MPF_LAZY_GATHER: deferred left-hand interchanges (laswp.hip) 2 = in one pass, in place: one map launch + a few apply launches;
+                                         // 1 = panel by panel through a temporary, as gathered reads; 0 = the same as scattered writes.  Same bits
+    int lazy_onepass_max_rows = 32768;   // MPF_LAZY_ONEPASS_MAX_ROWS: lazy_gather = 2 takes a column block in one pass while its segment has at most that many rows
+                                         // (a workgroup's registers hold 32768); longer segments go through the temporary
     int dpanel_fused_form = 1;           // MPF_DPANEL_FUSED=0: fp64 panel without the fused update + sub-panel launches
     int dist_instalments = 1;            // MPF_DIST_INSTALMENTS=0: the panel message of mpf_factor_dist always travels in one broadcast
     long long dist_instalment_min_bytes = 8ll << 20; // MPF_DIST_INSTALMENT_MIN_BYTES: panels below this go in one broadcast
@@ -193,6 +196,8 @@ struct mpf_ctx {
     Buf<MovedList> lists;              // one moved-row list per panel of the running factorization
     Buf<int> Fmap;                     // composite row map of the deferred left-hand interchanges (the map and its inverse)
     Buf<double> perm_tmp;              // N x nb scratch of the same
+    Buf<int> lazy_snap;                // one-pass form of the same: the inverse map's snapshots, one per (super-)panel, triangular (about N^2 / (2 nb) ints)
+    int lazy_onepass_blocks = 0;       // column blocks the last launch_lazy_left_swaps took in one pass (mpf_stats.lazy_onepass_blocks)
     Buf<double> trsv_inv;              // inverted 64x64 diagonal blocks of L then of U (solve path)
     Buf<double> trsv_inv256;           // full inverses of the 256 x 256 diagonal blocks of L then of U (single-GPU solve)
     Buf<int> trsv_cnt;                 // per-step counters of the solve's launches (near workgroups done), L steps then U steps
@@ -309,6 +314,7 @@ int launch_laswp_from_list_hole(mpf_ctx *c, double *A, int64_t lda, int64_t ncol
 // the end of the factorization (lists[p] = moved rows of panel p, p = 0..npanels-1)
 int launch_lazy_left_swaps(mpf_ctx *c, double *A, int64_t lda, int64_t N, int nb, int npanels, const MovedList *lists, int sb = 1,
                            int world = 1, int rank = 0);
+int64_t lazy_snap_elems(int64_t N, int nb, int npanels, int sb);   // ints of mpf_ctx::lazy_snap its one-pass form needs
 // mpf_factor_host -> factor_lookahead_rm: the matrix's columns from c0[0] on are still being uploaded when the factorization starts.
 // Segment i = columns [c0[i], c0[i + 1]) (the last one ends at N); the panels [0, q[i]) are factored on the columns left of it, then
 // the segment -- in d_A once flags[i] == seq -- receives those panels' interchange / TRSM / update one after the other (per element
