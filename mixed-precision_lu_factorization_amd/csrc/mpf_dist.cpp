@@ -16,6 +16,7 @@
 // (mpf_rccl_init: ncclBroadcast / ncclAllReduce on the context's communicator, resolved with dlopen so that single-GPU
 // users never load RCCL).  Tests drive the same loop through a gloo-backed callback with several ranks on one GPU.
 #include "solve_common.h"
+#include "factor_common.h"
 #include <dlfcn.h>
 #include <climits>
 #include <cstdio>
@@ -128,70 +129,404 @@ int ensure_dist_bufs(mpf_ctx *c, int64_t N, int nb) {
     return 0;
 }
 
-// Panels wider than 256 columns (the LDS pivot kernel and the moved-row lists stop there): the reference's own order, panel by
-// panel on one stream, with the generic (global-memory) pivot kernels and the sequential interchange of ALL local columns
-// (MPF.cu:145-162) -- no look-ahead, no deferred left-hand side.  Message = the factored panel (leading dimension = its rows)
-// followed by its pivots.  Per element the operations are those of factor_generic (mpf_host.cpp): identical bits.
-int factor_dist_wide(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_t nb, int32_t *d_ipiv, const mpf_dist *dist,
-                     const mpf_opts &o, const Layout &L, mpf_bcast_fn bcast_fn, void *user, mpf_stats &st) {
-    EvPool ev(c);
-    ev.keep = &st.ms_gemm;
-    hipStream_t S = c->stream;
-    const int64_t lcols = L.local_cols();
-    const bool split = o.trailing == MPF_TRAIL_FP16X3, f64 = o.trailing == MPF_TRAIL_FP64;
-    int rc = 0;
-    if (!f64) { rc = mpf_ensure_h_images(c, N, nb < 8 * HP_MAXCOLS ? nb : 8 * HP_MAXCOLS, false); if (rc) return rc; }
-    for (int b = 0; L.live(b) && rc == 0; ++b) {
-        const int64_t k = (int64_t)b * nb;
-        const int pc = L.width(b), pr = (int)(N - k);
-        double *buf = c->dist_buf[0];
-        int *piv = (int *)(buf + (size_t)pr * pc);
-        if (L.mine(b)) {
-            double *Ap = d_Aloc + L.lcol(b) * ldloc + k;
-            st.pivot_path = 1;
-            rc = ev.timed(st.ms_hpanel, S, [&] { return launch_hgetf2_generic(c, Ap, ldloc, nullptr, 0, pr, pc, (int)k, d_ipiv + k, nullptr, 0); });
-            if (!rc) rc = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_seq(c, d_Aloc, ldloc, lcols, (int)k, pc, d_ipiv + k, N); });
-            if (!rc) rc = ev.timed(st.ms_dpanel, S, [&] { return launch_dgetf2_npv(c, Ap, ldloc, pr, pc, o.fused_panel, (int)k); });
-            if (rc) break;
-            MPF_HIP_TRY(c, hipMemcpy2DAsync(buf, (size_t)pr * 8, Ap, (size_t)ldloc * 8, (size_t)pr * 8, (size_t)pc, hipMemcpyDeviceToDevice, S));
-            MPF_HIP_TRY(c, hipMemcpyAsync(piv, d_ipiv + k, (size_t)pc * 4, hipMemcpyDeviceToDevice, S));
-            st.panels++;
+// ---- factorization: one call's state and steps -----------------------------------------------------------------------------
+// The steps are the single-GPU schedules' (factor_common.h) on views of this rank's storage: a panel's columns in the local matrix,
+// its L in the panel message; the far columns in the local matrix and an fp32 working copy, their super-panel's L in a store.
+struct DistFactor {
+    mpf_ctx *c; const mpf_opts &o; const Layout L;
+    double *A; const int64_t lda, N; const int nb; int32_t *ipiv;   // the local matrix, the global order
+    mpf_bcast_fn bcast_fn; void *user;
+    const int64_t lcols;
+    const bool f64, split, generic;   // generic: pivot_path = 1 / safe_pivots, as mpf_factor_dev (GPUs shared with other processes)
+    mpf_stats st{}; EvPool ev; const FactorArgs f;
+    hipStream_t S, P, X;              // main; the next panel's chain; the exchange of a message in instalments
+    bool two = false, rm = false;
+    int sb = 1, far_img = 1;          // panels per super-panel (1: one-level schedule); which L image the next K = sb * nb update reads
+    bool inst_ok = false, fused_form_all = false; long long inst_min_bytes = 0, lds_rows_max = 0;   // agreed by the ranks (agree)
+    double *Rl = nullptr, *SPL = nullptr;                  // row-major copy of the local columns (fp64 mode); the super-panel's panels, ld N
+    float *W = nullptr;                                    // fp32 row-major working copy of the local far columns
+    int64_t ldr = 1, ldw = 1; ImageGeom g{};
+    bool image_ready = false;         // the current panel's L21 image (fp16 modes) / row-major L21 (rm) is there
+    std::vector<hipEvent_t> ev_piece;
+
+    DistFactor(mpf_ctx *c_, const mpf_opts &o_, const mpf_dist *d, double *A_, int64_t lda_, int64_t N_, int nb_, int32_t *ipiv_)
+        : c(c_), o(o_), L(N_, nb_, d->rank, d->world), A(A_), lda(lda_), N(N_), nb(nb_), ipiv(ipiv_), bcast_fn(d->bcast ? d->bcast : rccl_bcast),
+          user(d->bcast ? d->user : (void *)c_), lcols(L.local_cols()), f64(o_.trailing == MPF_TRAIL_FP64), split(o_.trailing == MPF_TRAIL_FP16X3),
+          generic(o_.pivot_path == 1 || safe_pivots(c_)), ev(c_), f{c_, ev, st, o_, A_, lda_, N_, nb_, ipiv_}, S(c_->stream), P(c_->stream), X(c_->stream) {
+        ev.keep = &st.ms_gemm; st.n = N; st.nb = nb; st.superpanel = 1;
+        st.fp16_fused = c->tune.fp16_fused != 0;   // (every rank's own option: the ranks must agree on it, include/mpf_c.h)
+    }
+    int bcast(void *buf, size_t bytes, int root, hipStream_t s) {
+        if (L.world == 1) return 0;
+        const int e = bcast_fn(user, buf, (int64_t)bytes, root, (void *)s);
+        return e ? (e < 0 ? e : -5) : 0;
+    }
+    // message buffer of panel b (PANEL_PAD above)
+    char *buf_of(int b) const { return (char *)c->dist_buf[b & 1].get(); }
+    int64_t rows_of(int b) const { return N - (int64_t)b * nb; }
+    int64_t ldp_of(int b) const { return rows_of(b) + PANEL_PAD; }
+    size_t list_off(int b) const { return (size_t)ldp_of(b) * L.width(b) * 8; }
+    int *piv_ptr(int b, int q) const { return (int *)((double *)buf_of(b) + (size_t)(32 * q) * ldp_of(b) + rows_of(b)); }   // pivots of sub-panel q
+    PanelView panel(int b) const { return {A + L.lcol(b) * lda, lda, (int64_t)b * nb, (int)rows_of(b), L.width(b), c->lists + b, ipiv + (int64_t)b * nb}; }
+    // super-panels: first block of b's, one past its last block, one past its look-ahead block, this rank's first far column
+    int sp_first(int b) const { return (b / sb) * sb; }
+    int sp_end(int b) const { const int e = sp_first(b) + sb; return e < L.nblocks ? e : L.nblocks; }
+    int inner_end_blk(int b) const { const int e = sp_end(b) + 1; return e < L.nblocks ? e : L.nblocks; }
+    int64_t far0(int b) const { return sb > 1 ? L.first_local_col_after(inner_end_blk(b) - 1) : lcols; }
+    FarView far_view(int b) const { return {A + far0(b) * lda, lda, W + far0(b), ldw, lcols - far0(b), SPL, N, (const double *)buf_of(b), ldp_of(b)}; }
+
+    // every call starts here: info and the pivot kernel's give-up counter reset (lists: + moved-row lists, left-hand scratch), the clock
+    int begin(bool lists) {
+        const int rc = mpf_factor_setup(c, N, nb, L.nblocks, lists);
+        if (!rc) MPF_HIP_TRY(c, hipEventRecord(c->ev0, S));
+        return rc;
+    }
+    // ---- what every rank must decide alike (ADVICE r3) ------------------------------------------------------------------------------
+    // How many broadcasts a panel message travels in, and the one- / two-level choice, follow from rank-local state: which streams
+    // could be created, what this device's pivot kernel can hold, per-context options.  Ranks that disagreed would issue different
+    // collectives (a hang) or factor with different roundings.  Every rank's values go round once (one 64-byte broadcast per rank)
+    // and everyone takes the minimum; `sb` differing is an error on every rank (the buffers were sized for the local value).
+    int agree() {
+        hp_query_residency(c);
+        // rows this device's pivot kernel can take beside the workgroups of the pipelined chain's gated interchange kernel (which wait for it)
+        const long long lds_rows = hgetf2_capacity_rows(c, laswp_gated_grid(nb)), cap = HP_R * (long long)HP_MAXG;
+        long long mine[8] = {two && c->tune.chain_pipeline != 0 && c->tstream != nullptr && !generic && c->tune.dist_instalments && c->xstream ? 1 : 0,
+                             sb, -(long long)c->tune.dist_instalment_min_bytes, c->tune.dpanel_fused_form ? 1 : 0, lds_rows < cap ? lds_rows : cap,
+                             two ? 1 : 0, 0, 0}, agreed[8];
+        memcpy(agreed, mine, sizeof mine);
+        long long *dv = (long long *)c->dist_buf[0].get();   // (free until the first panel message)
+        for (int root = 0; root < L.world && L.world > 1; ++root) {
+            if (root == L.rank) MPF_HIP_TRY(c, hipMemcpyAsync(dv, mine, sizeof mine, hipMemcpyHostToDevice, c->stream));
+            const int e = bcast(dv, sizeof mine, root, c->stream);
+            if (e) return e;
+            long long got[8];
+            MPF_HIP_TRY(c, hipMemcpyAsync(got, dv, sizeof got, hipMemcpyDeviceToHost, c->stream));
+            MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
+            for (int i = 0; i < 8; ++i) if (got[i] < agreed[i]) agreed[i] = got[i];
         }
-        if (L.world > 1) {
-            const int e = bcast_fn(user, buf, (int64_t)((size_t)pr * pc * 8 + (size_t)pc * 4), L.owner(b), (void *)S);
-            if (e) return e < 0 ? e : -5;
+        if (agreed[1] != sb) { c->err = "mpf_factor_dist: the ranks disagree on the super-panel width (options superpanel_fp16 / fp16_work32 / safe_pivots must be the same on every rank)"; return -1; }
+        inst_ok = agreed[0] != 0; inst_min_bytes = -agreed[2]; fused_form_all = agreed[3] != 0; lds_rows_max = agreed[4];
+        return 0;
+    }
+    // Two-level schedule of the fp16 modes (factor_superpanel in mpf_host.cpp, carried over to the block-cyclic layout): sb panels
+    // form a super-panel; a panel updates only the INNER blocks (the super-panel's own and the next super-panel's first one) of
+    // this rank, panel by panel, in fp64; this rank's FAR columns live in an fp32 row-major working copy and get one update with
+    // K = sb * nb per super-panel, after the U block-row tasks.  What the single-GPU schedule reads from the matrix left of the
+    // panel -- the super-panel's earlier panels -- every rank keeps in a store of its own, assembled from the panel messages.
+    int set_up() {
+        // the width is the single-GPU rule's; the gate is this loop's own: the inner region holds the look-ahead block too
+        const int want_sb = wanted_superpanel(c, o, N);
+        sb = (!f64 && !generic && c->tune.fp16_work32 != 0 && hgetf2_lds_eligible(c, (int)N, (int)(nb < N ? nb : N)) &&
+              (int64_t)(want_sb + 1) * nb < N) ? want_sb : 1;
+        const int64_t sbw = (int64_t)sb * nb;
+        int rc = 0;
+        if (!f64) {
+            const int64_t kimg = sbw < 8 * HP_MAXCOLS ? sbw : 8 * HP_MAXCOLS;
+            rc = sb > 1 ? mpf_ensure_h_images(c, N + HP_MAXCOLS + 64, (int)kimg, true) : mpf_ensure_h_images(c, N, nb, false);
+            if (rc) return rc;
         }
-        if (!L.mine(b)) {
-            MPF_HIP_TRY(c, hipMemcpyAsync(d_ipiv + k, piv, (size_t)pc * 4, hipMemcpyDeviceToDevice, S));
-            if (lcols > 0) rc = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_seq(c, d_Aloc, ldloc, lcols, (int)k, pc, d_ipiv + k, N); });
-            if (rc) break;
+        if (sb > 1) {
+            MPF_HIP_TRY(c, c->dist_w32.grow(N * (lcols > 0 ? lcols : 1)));
+            MPF_HIP_TRY(c, c->dist_spl.grow(N * sbw));
         }
-        const int64_t c0 = L.first_local_col_after(b), nc = lcols - c0, m = (int64_t)pr - pc;
-        if (k + pc < N && nc > 0) {
-            double *U12 = d_Aloc + c0 * ldloc + k;
-            rc = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu(c, pc, nc, buf, pr, U12, ldloc); });
-            if (!rc && m > 0) {
-                rc = ev.timed(st.ms_gemm, S, [&] {
-                    if (f64) return launch_dgemm_minus(c, m, nc, pc, buf + pc, pr, U12, ldloc, U12 + pc, ldloc);
-                    int e = 0;
-                    const int kcmax = c->h_kmax;                 // K capacity of the fp16 operand images
-                    for (int k0 = 0; k0 < pc && !e; k0 += kcmax) {
-                        const int kc = (pc - k0) < kcmax ? (pc - k0) : kcmax;
-                        e = launch_cvt_l21(c, buf + pc + (int64_t)k0 * pr, pr, m, kc, split);
-                        if (!e) e = launch_hgemm_minus(c, m, nc, kc, U12 + k0, ldloc, U12 + pc, ldloc, split);
+        if (!c->xstream && L.world > 1 && c->tune.dist_instalments) {   // exchange stream of the panel's instalments
+            int lo = 0, hi = 0;
+            hipDeviceGetStreamPriorityRange(&lo, &hi);
+            if (hipStreamCreateWithPriority(&c->xstream, hipStreamNonBlocking, hi) != hipSuccess) c->xstream = nullptr;
+        }
+        if (!o.no_lookahead && c->pstream) P = c->pstream;
+        two = P != S;
+        rc = agree();
+        if (rc) return rc;
+        // fp64 mode: this rank's columns right of the current panel live in a ROW-major working copy (as factor_lookahead_rm's): an
+        // interchange moves contiguous row segments instead of one 64-byte sector per moved row and column; the update is the same MFMA
+        // kernel on the transposed problem (c = fma(-u, l, c), kk ascending: the same bits).  Rank-local choice: results do not depend on it.
+        rm = f64 && lcols > 0 && c->tune.fp64_rowmajor && N >= c->tune.fp64_rowmajor_min_n && N > nb && mpf_ensure_rowmajor_copy(c, N, lcols, nb) == 0;
+        Rl = rm ? c->r64.get() : nullptr;
+        W = c->dist_w32; SPL = c->dist_spl;
+        ldr = ldw = lcols > 0 ? lcols : 1;
+        st.superpanel = sb;
+        g = image_geom(N, sb > 1 ? lcols - L.first_local_col_after(sb) : 0, sb, nb, c->h_kmax, f64);
+        rc = begin(true);
+        if (rc) return rc;
+        X = c->xstream ? c->xstream : P;   // (the owner's P runs the pivot kernel meanwhile)
+        if (two) stream_join(ev, S, P);
+        return 0;
+    }
+    // Number of 32-column instalments the message of panel b travels in (0: one broadcast after the whole chain).  A function
+    // of the shape and of options that must be the same on every rank (chain_pipeline, pivot_path / safe_pivots, dist_instalments).
+    // Small panels go in one piece: an instalment costs a collective's latency.
+    int pieces_of(int b) const {
+        const int64_t pc = L.width(b), pr = rows_of(b);
+        if (!inst_ok || pc > HP_MAXCOLS || pr > lds_rows_max) return 0;           // (every rank's pivot kernel can hold the panel)
+        if (pr * pc * 8 < inst_min_bytes) return 0;
+        return (fused_form_all && pc % 32 == 0 && pc >= 64) ? (int)(pc / 32) : 0;        // = dgetf2_npv_pieces with the agreed option
+    }
+    // columns [c0, c0 + nc) of the panel + their sub-panels' pivots into the message
+    int pack(int b, const PanelView &v, hipStream_t ps, int c0, int nc) {
+        const int64_t ldp = ldp_of(b);
+        MPF_HIP_TRY(c, hipMemcpy2DAsync(buf_of(b) + (size_t)c0 * ldp * 8, (size_t)ldp * 8, v.A + v.k + (int64_t)c0 * lda, (size_t)lda * 8, (size_t)v.pr * 8,
+                                        (size_t)nc, hipMemcpyDeviceToDevice, ps));
+        for (int q = c0 / 32; q * 32 < c0 + nc; ++q) {
+            const int w = (v.pc - 32 * q) < 32 ? (v.pc - 32 * q) : 32;
+            MPF_HIP_TRY(c, hipMemcpyAsync(piv_ptr(b, q), v.ipiv + 32 * q, (size_t)w * 4, hipMemcpyDeviceToDevice, ps));
+        }
+        return 0;
+    }
+    // owner only: pivots, interchange of the panel's own columns, fp64 panel, pack -- on stream s (and T).  With instalments
+    // (np > 0) ev_piece[q] is recorded once instalment q (32 packed columns + their pivots; the last one: + the moved-row list)
+    // is complete in the message buffer.
+    int chain(int b, hipStream_t s, int np) {
+        const PanelView v = panel(b);
+        const int64_t ldp = ldp_of(b);
+        char *buf = buf_of(b);
+        StreamSwap sw(c, s);
+        hipEvent_t before_pivots = ev.get();
+        hipEventRecord(before_pivots, s);
+        const bool lds = !generic && hgetf2_lds_eligible(c, v.pr, v.pc);
+        // the fp64 panel follows the pivot kernel 32 columns behind on the helper stream (see chain_behind in mpf_host.cpp) -- where
+        // the panel's workgroups fit beside the gated interchange kernel's, which wait for it while sitting on CUs
+        const int waiters = (c->tune.gate_wait_value && c->hp_signal) ? 0 : laswp_gated_grid(v.pc);
+        const bool will_pipe = c->tune.chain_pipeline != 0 && c->tstream != nullptr && lds && hgetf2_fits_beside(c, v.pr, v.pc, waiters);
+        int e = panel_pivots(f, v, s, will_pipe ? waiters : 0, !lds);
+        if (e) return e;
+        hipEvent_t pivots_done = ev.get();
+        hipEventRecord(pivots_done, s);
+        const int npp = will_pipe ? dgetf2_npv_pieces(c, v.pc) : 0;
+        if (np > 0 && npp != np) { c->err = "mpf_factor_dist: instalment count differs from the agreed one"; return -1; }
+        if (npp > 0) {
+            hipStream_t T = c->tstream;
+            hipStreamWaitEvent(T, before_pivots, 0);
+            {
+                StreamSwap swt(c, T);
+                hipEvent_t t0 = ev.get(), t1 = ev.get();   // (the pieces run under ms_dpanel only where every region is timed)
+                hipEventRecord(t0, T);
+                e = panel_pieces(f, v, npp, [&](int q) -> int {
+                    if (np == 0) return 0;
+                    int e2 = pack(b, v, T, 32 * q, 32);   // instalment q leaves as it is: the interchanges still to come are applied to the message copy
+                    // (the matrix holds the UNfactored diagonal tile until the last piece has run: dpanel.hip)
+                    if (!e2 && q < np - 1) e2 = launch_dpanel_tile_copy(c, (double *)buf + (size_t)(32 * q) * ldp + 32 * q, ldp, q);
+                    if (!e2 && q == np - 1) {
+                        hipStreamWaitEvent(T, pivots_done, 0);   // the moved-row list is complete when the pivot kernel has ended
+                        MPF_HIP_TRY(c, hipMemcpyAsync(buf + list_off(b), v.ml, sizeof(MovedList), hipMemcpyDeviceToDevice, T));
                     }
-                    return e; });
-                count_gemm(st, o, m, nc, pc);
+                    if (!e2) { ev_piece[(size_t)q] = ev.get(); hipEventRecord(ev_piece[(size_t)q], T); }
+                    return e2; });
+                hipEventRecord(t1, T);
+                if (c->tune.timeline || c->tune.event_timers >= 2) ev.pairs.push_back({t0, t1, &st.ms_dpanel, nullptr});
+            }
+            stream_join(ev, T, s);
+        } else e = panel_tail(f, v, s);
+        if (e) return e;
+        if (np == 0) {   // the whole message at once, from the finished panel
+            e = pack(b, v, s, 0, v.pc);
+            if (!e) MPF_HIP_TRY(c, hipMemcpyAsync(buf + list_off(b), v.ml, sizeof(MovedList), hipMemcpyDeviceToDevice, s));
+        }
+        st.panels++;
+        return e;
+    }
+    // every rank: the exchange of panel b on stream s, then (non-owners) pivots and moved list out of the message.
+    // np == 0: ONE broadcast.  np > 0: np instalments; after instalment q every rank applies sub-panel q's 32 interchanges to
+    // the instalments already there (what the owner's matrix got from laswp_block while the later instalments were still being
+    // factored): the assembled message is the finished panel.
+    int exchange(int b, hipStream_t s, int np) {
+        const int pc = L.width(b);
+        const int64_t k = (int64_t)b * nb, ldp = ldp_of(b);
+        char *buf = buf_of(b);
+        int e = 0;
+        if (np == 0) e = bcast(buf, list_off(b) + sizeof(MovedList), L.owner(b), s);
+        else {
+            StreamSwap sw(c, s);
+            for (int q = 0; q < np && !e; ++q) {
+                if (L.mine(b)) hipStreamWaitEvent(s, ev_piece[(size_t)q], 0);
+                const size_t off = (size_t)(32 * q) * ldp * 8;
+                e = bcast(buf + off, q == np - 1 ? list_off(b) + sizeof(MovedList) - off : (size_t)32 * ldp * 8, L.owner(b), s);
+                // rows of the message are rows k.. of the matrix: address it from the matrix' row 0
+                if (!e && q > 0) e = launch_laswp_block(c, (double *)buf - k, ldp, 32 * q, (int)k + 32 * q, 32, piv_ptr(b, q), N);
             }
         }
-        if (o.verbose) printf("[rank %d] panel %d (k=%lld) owner %d (wide panels: generic schedule)\n", L.rank, b, (long long)k, L.owner(b));
+        if (e || L.mine(b)) return e;
+        const int nq = (pc + 31) / 32;
+        MPF_HIP_TRY(c, hipMemcpy2DAsync(ipiv + k, 128, piv_ptr(b, 0), (size_t)32 * ldp * 8, 128, (size_t)(pc / 32), hipMemcpyDeviceToDevice, s));
+        if (pc % 32) MPF_HIP_TRY(c, hipMemcpyAsync(ipiv + k + 32 * (nq - 1), piv_ptr(b, nq - 1), (size_t)(pc % 32) * 4, hipMemcpyDeviceToDevice, s));
+        MPF_HIP_TRY(c, hipMemcpyAsync(c->lists + b, buf + list_off(b), sizeof(MovedList), hipMemcpyDeviceToDevice, s));
+        return 0;
     }
-    const hipError_t se = hipStreamSynchronize(S);
-    if (!rc && se != hipSuccess) { c->err = std::string("distributed factorization failed: ") + hipGetErrorString(se); return -2; }
-    ev.collect();
-    (void)dist;
-    return rc;
-}
+    // interchange + TRSM + trailing update of panel b on the local columns [c0, c0 + nc) (all right of block b)
+    int update(int b, int64_t c0, int64_t nc) {
+        if (nc <= 0) return 0;
+        const int64_t k = (int64_t)b * nb, ldp = ldp_of(b);
+        const int pc = L.width(b);
+        const int64_t m = N - k - pc;
+        const double *Pb = (const double *)buf_of(b);
+        if (rm) {
+            // interchange of contiguous row segments, TRSM through strides, L21 row-major once per panel, the update on the transposed
+            // problem, then the finished U rows of these columns go home to the column-major matrix
+            double *LT = c->rm_lt, *Rk = Rl + k * ldr + c0;
+            int e = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_from_list_rm64(c, Rl + c0, ldr, nc, c->lists + b); });
+            if (!e) e = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu_strided(c, pc, nc, Pb, ldp, Rk, ldr, 1); });
+            if (!e && m > 0) {
+                if (!image_ready) { e = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, (double *)Pb + pc, ldp, LT, pc, m, pc, true); }); image_ready = true; }
+                if (!e) e = ev.timed(st.ms_gemm, S, [&] { return launch_dgemm_minus(c, nc, m, pc, Rk, ldr, LT, pc, Rk + pc * ldr, ldr); });
+                count_gemm(st, o, m, nc, pc);
+            }
+            if (!e) e = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, A + c0 * lda + k, lda, Rk, ldr, pc, nc, false); });
+            return e;
+        }
+        int e = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_from_list(c, A + c0 * lda, lda, nc, c->lists + b); });
+        double *U12 = A + c0 * lda + k;
+        if (!e) e = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu(c, pc, nc, Pb, ldp, U12, lda); });
+        if (e || m <= 0) return e;
+        e = ev.timed(st.ms_gemm, S, [&] {
+            int e2 = 0;
+            if (!f64 && !image_ready) { e2 = launch_cvt_l21(c, Pb + pc, ldp, m, pc, split); image_ready = true; } // once per panel
+            if (!f64 && sb == 1) return e2 ? e2 : launch_hgemm_minus(c, m, nc, pc, U12, lda, U12 + pc, lda, split);
+            if (!f64 && !e2) e2 = launch_inner_u_image(c, o, U12, lda, pc, nc, g.inner_u_off);
+            return e2 ? e2 : launch_inner_gemm(c, o, m, nc, pc, Pb + pc, ldp, U12, lda, g.inner_u_off); });
+        count_gemm(st, o, m, nc, pc);
+        return e;
+    }
+    // ---- two-level schedule: this rank's far columns (sb > 1) -------------------------------------------------------------
+    // the super-panel's panels as received: eager interchanges of panel b on the earlier ones, then panel b itself
+    int spl_add(int b) {
+        const int p = b - sp_first(b);
+        const int64_t k = (int64_t)b * nb;
+        int e = 0;
+        if (p > 0) e = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_from_list(c, SPL, N, (int64_t)p * nb, c->lists + b); });
+        if (!e) MPF_HIP_TRY(c, hipMemcpy2DAsync(SPL + (int64_t)p * nb * N + k, (size_t)N * 8, buf_of(b), (size_t)ldp_of(b) * 8, (size_t)(N - k) * 8, (size_t)L.width(b),
+                                                hipMemcpyDeviceToDevice, S));
+        return e;
+    }
+    int far_task(int b) {   // block-row task of panel b on the far columns (T_p of factor_superpanel)
+        if (far0(b) >= lcols) return 0;
+        const int e = spl_add(b);
+        return e ? e : far_block_row(f, far_view(b), g, (int64_t)sp_first(b) * nb, b - sp_first(b));
+    }
+    int superpanel_begin(int b) { return far_zero_padding(f, lcols - far0(b), g); }
+    // end of b's super-panel: the operand image of L[s1.., s0..s1) once, the K = s1 - s0 update on the columns that join the next inner
+    // region first (they return to fp64), then on the rest
+    int superpanel_end(int b) {
+        const int64_t f0 = far0(b), f0n = far0(sp_end(b));            // first far column of this and of the next super-panel
+        if (f0 >= lcols) return 0;
+        const int64_t s0 = (int64_t)sp_first(b) * nb, s1 = (int64_t)sp_end(b) * nb;
+        const FarView v = far_view(b);
+        int e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_l21(c, SPL + s1, N, N - s1, (int)(s1 - s0), split, far_img); });
+        if (!e) e = far_big_update(f, v, g, s0, s1, 0, f0n - f0, far_img);
+        if (!e && f0n > f0) e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_f32_f64(c, W + s1 * ldw + f0, ldw, A + f0 * lda + s1, lda, N - s1, f0n - f0); });
+        if (!e) e = far_big_update(f, v, g, s0, s1, f0n - f0, lcols - f0n, far_img);
+        far_img = 3 - far_img;
+        return e;
+    }
+    // Schedule = the look-ahead schedule of mpf_host.cpp with column indices translated (top of this file)
+    int run() {
+        int rc = 0;
+        if (sb > 1 && far0(0) < lcols)   // this rank's far columns of the first super-panel go into the working copy
+            rc = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_f64_f32(c, A + far0(0) * lda, lda, W + far0(0), ldw, N, lcols - far0(0)); });
+        if (!rc && L.live(0)) {
+            if (L.mine(0)) rc = chain(0, S, 0);
+            if (!rc) rc = exchange(0, S, 0);
+        }
+        if (!rc && rm)   // everything this rank owns goes into the row-major copy (block 0, if it is here, is finished: its copy is never read)
+            rc = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, A, lda, Rl, ldr, N, lcols, true); });
+        for (int b = 0; L.live(b) && rc == 0; ++b) {
+            const int64_t k = (int64_t)b * nb;
+            const int pc = L.width(b);
+            const int nxt = b + 1;
+            const bool has_next = L.live(nxt), own_next = has_next && L.mine(nxt), trailing = k + pc < N;
+            int64_t rest0 = L.first_local_col_after(b);
+            image_ready = false;
+            hipEvent_t e2 = nullptr;
+            if (trailing && own_next) { // my block of panel b+1 first, then its chain on the side stream
+                rc = update(b, L.lcol(nxt), L.width(nxt));
+                if (!rc && rm)   // the next panel's columns return to the column-major matrix before its chain (rows k + pc ..; its U rows went with the update)
+                    rc = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, A + L.lcol(nxt) * lda + k + pc, lda, Rl + (k + pc) * ldr + L.lcol(nxt), ldr,
+                                                                                N - k - pc, L.width(nxt), false); });
+                if (rc) break;
+                rest0 = L.lcol(nxt) + L.width(nxt);
+            }
+            if (has_next) {
+                const int np = pieces_of(nxt);
+                hipStream_t xs = np > 0 ? X : P;
+                if (two) { // strip done; receive buffer free (its last reader was update b - 1, in front of this event on S)
+                    hipEvent_t e1 = ev.get(); hipEventRecord(e1, S); hipStreamWaitEvent(P, e1, 0);
+                    if (xs != P) hipStreamWaitEvent(xs, e1, 0);
+                }
+                ev_piece.assign((size_t)(np > 0 ? np : 1), nullptr);
+                if (own_next) rc = chain(nxt, P, np);
+                if (!rc) rc = exchange(nxt, xs, np);
+                if (rc) break;
+                if (two) {
+                    e2 = ev.get(); hipEventRecord(e2, xs);
+                    if (xs != P && own_next) stream_join(ev, P, S);   // the owner's chain itself
+                }
+            }
+            if (sb == 1) { if (trailing && rest0 < lcols) rc = update(b, rest0, lcols - rest0); }
+            else if (trailing) {
+                // inner blocks right of the strip, panel by panel in fp64; far columns: block-row task now, K = sb * nb update at the
+                // end of the super-panel (it runs under the chain of the next super-panel's first panel, launched above)
+                if (b == sp_first(b)) rc = superpanel_begin(b);
+                if (!rc && rest0 < far0(b)) rc = update(b, rest0, far0(b) - rest0);
+                if (!rc) rc = far_task(b);
+                if (!rc && b + 1 == sp_end(b)) rc = superpanel_end(b);
+            }
+            if (e2) hipStreamWaitEvent(S, e2, 0);
+            if (o.verbose) printf("[rank %d] panel %d (k=%lld) owner %d\n", L.rank, b, (long long)k, L.owner(b));
+        }
+        if (!rc) rc = ev.timed(st.ms_laswp, S, [&] { return launch_lazy_left_swaps(c, A, lda, N, nb, L.nblocks, c->lists, 1, L.world, L.rank); });
+        return rc;
+    }
+    // Panels wider than 256 columns (the LDS pivot kernel and the moved-row lists stop there): the reference's own order, panel by
+    // panel on one stream, with the generic (global-memory) pivot kernels and the sequential interchange of ALL local columns
+    // (MPF.cu:145-162) -- no look-ahead, no deferred left-hand side.  Message = the factored panel (leading dimension = its rows)
+    // followed by its pivots.  Per element the operations are those of factor_generic (mpf_host.cpp): identical bits.
+    int run_wide() {
+        int rc = f64 ? 0 : mpf_ensure_h_images(c, N, nb < 8 * HP_MAXCOLS ? nb : 8 * HP_MAXCOLS, false);
+        for (int b = 0; L.live(b) && rc == 0; ++b) {
+            const int64_t k = (int64_t)b * nb;
+            const int pc = L.width(b), pr = (int)(N - k);
+            double *buf = c->dist_buf[0];
+            int *piv = (int *)(buf + (size_t)pr * pc);
+            if (L.mine(b)) {
+                double *Ap = A + L.lcol(b) * lda + k;
+                st.pivot_path = 1;
+                rc = ev.timed(st.ms_hpanel, S, [&] { return launch_hgetf2_generic(c, Ap, lda, nullptr, 0, pr, pc, (int)k, ipiv + k, nullptr, 0); });
+                if (!rc) rc = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_seq(c, A, lda, lcols, (int)k, pc, ipiv + k, N); });
+                if (!rc) rc = ev.timed(st.ms_dpanel, S, [&] { return launch_dgetf2_npv(c, Ap, lda, pr, pc, o.fused_panel, (int)k); });
+                if (rc) break;
+                MPF_HIP_TRY(c, hipMemcpy2DAsync(buf, (size_t)pr * 8, Ap, (size_t)lda * 8, (size_t)pr * 8, (size_t)pc, hipMemcpyDeviceToDevice, S));
+                MPF_HIP_TRY(c, hipMemcpyAsync(piv, ipiv + k, (size_t)pc * 4, hipMemcpyDeviceToDevice, S));
+                st.panels++;
+            }
+            rc = bcast(buf, (size_t)pr * pc * 8 + (size_t)pc * 4, L.owner(b), S);
+            if (rc) break;
+            if (!L.mine(b)) {
+                MPF_HIP_TRY(c, hipMemcpyAsync(ipiv + k, piv, (size_t)pc * 4, hipMemcpyDeviceToDevice, S));
+                if (lcols > 0) rc = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_seq(c, A, lda, lcols, (int)k, pc, ipiv + k, N); });
+                if (rc) break;
+            }
+            const int64_t c0 = L.first_local_col_after(b), nc = lcols - c0, m = (int64_t)pr - pc;
+            if (k + pc < N && nc > 0) {
+                double *U12 = A + c0 * lda + k;
+                rc = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu(c, pc, nc, buf, pr, U12, lda); });
+                if (!rc && m > 0) {
+                    rc = ev.timed(st.ms_gemm, S, [&] { return launch_generic_update(c, o, m, nc, pc, buf + pc, pr, U12, lda); });
+                    count_gemm(st, o, m, nc, pc);
+                }
+            }
+            if (o.verbose) printf("[rank %d] panel %d (k=%lld) owner %d (wide panels: generic schedule)\n", L.rank, b, (long long)k, L.owner(b));
+        }
+        return rc;
+    }
+    // the end of every call: the host waits for every stream; info covers this rank's panels only (the caller combines: min over the positive values)
+    int report(int rc) {
+        return factor_report(c, st, rc, [&] {
+            hipError_t e = hipStreamSynchronize(S);
+            for (hipStream_t s : {P, c->xstream, c->tstream})
+                if (two && s) { const hipError_t e2 = hipStreamSynchronize(s); if (e == hipSuccess) e = e2; }
+            if (!rc && e == hipSuccess) { ev.collect(); st.lookahead = two ? 1 : 0; }
+            return e; }, "distributed factorization", "fp16 pivot kernel: inter-workgroup hand-off timed out (buffers invalid; use pivot_path = 1)");
+    }
+};
 } // namespace
 
 extern "C" {
@@ -319,29 +654,18 @@ int mpf_rccl_version(void) {
     return v;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// factorization
-// ---------------------------------------------------------------------------------------------------------------------
+// ---- factorization ---------------------------------------------------------------------------------------------------
 int mpf_factor_dist(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_t nb, int32_t *d_ipiv, const mpf_dist *dist,
                     const mpf_opts *opts) {
     if (!c || !d_ipiv || !dist) return -1;
-    if (N <= 0 || nb <= 0) { c->err = "mpf_factor_dist: N and panel width must be positive"; return -1; }
-    if (dist->world < 1 || dist->rank < 0 || dist->rank >= dist->world) { c->err = "mpf_factor_dist: bad rank / world"; return -1; }
-    if (ldloc < N) { c->err = "mpf_factor_dist: ldloc < N"; return -1; }
-    if (nb > 65535) { c->err = "mpf_factor_dist: panel width > 65535"; return -1; }
-    if (N > INT_MAX / 2) { c->err = "mpf_factor_dist: N too large"; return -1; }
     mpf_opts o{};
     if (opts) o = *opts;
-    if (o.trailing < MPF_TRAIL_FP64 || o.trailing > MPF_TRAIL_FP16X3) { c->err = "mpf_factor_dist: unknown trailing mode"; return -1; }
+    if (factor_check_args(c, "mpf_factor_dist", "ldloc", N, nb, ldloc, o)) return -1;
+    if (dist->world < 1 || dist->rank < 0 || dist->rank >= dist->world) { c->err = "mpf_factor_dist: bad rank / world"; return -1; }
     if (o.pivot_search != 0 || c->tune.pivot_fp64) {
         c->err = "mpf_factor_dist: the fp64 pivot rules (mpf_opts.pivot_search = 1 or 2, option pivot_fp64) are single-GPU only; use mpf_factor_dev";
         return -1;
     }
-    // fp16 modes: the full-slab pivot kernel (a CU per workgroup) except where a panel leaves fewer than 72 CUs free -- the gated
-    // interchange kernel of the pipelined chain (64 workgroups) waits for the pivot kernel's progress, each of its workgroups keeps
-    // a pivot workgroup off its CU (measured: 192 pivot workgroups + 64 run, 208 + 64 never become resident), and a pivot workgroup
-    // that finds no CU never starts: N = 53 248 and up gave up after the bounded spin (-4).  The column-window form (two per CU)
-    // has the room.
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     // One rank owns every column: the local matrix IS the matrix, and the single-GPU driver's schedules (row-major working copy in
     // two column lanes for fp64, three lanes for the fp16 modes) are the ones to run -- the N = 1 point of a scaling curve is the
@@ -350,446 +674,17 @@ int mpf_factor_dist(mpf_ctx *c, double *d_Aloc, int64_t ldloc, int64_t N, int32_
         if (!d_Aloc) return -1;
         return mpf_factor_dev(c, d_Aloc, ldloc, N, nb, d_ipiv, &o);
     }
-    mpf_bcast_fn bcast_fn = dist->bcast ? dist->bcast : rccl_bcast;
-    void *user = dist->bcast ? dist->user : (void *)c;
     if (!dist->bcast && dist->world > 1 && (!c->rccl_comm || c->rccl_world != dist->world || c->rccl_rank != dist->rank)) {
         c->err = "mpf_factor_dist: no broadcast callback and no matching RCCL communicator (mpf_rccl_init)"; return -5;
     }
-    const Layout L(N, nb, dist->rank, dist->world);
-    const int64_t lcols = L.local_cols();
-    if (lcols > 0 && !d_Aloc) return -1;
-    const bool split = o.trailing == MPF_TRAIL_FP16X3, f64 = o.trailing == MPF_TRAIL_FP64;
+    DistFactor d(c, o, dist, d_Aloc, ldloc, N, nb, d_ipiv);
+    if (d.lcols > 0 && !d_Aloc) return -1;
     int rc = ensure_dist_bufs(c, N, nb);
     if (rc) return rc;
-    if (nb > HP_MAXCOLS) {   // wide panels: the generic schedule (reference order, one stream)
-        const int imax0 = INT_MAX;
-        MPF_HIP_TRY(c, hipMemcpyAsync(&c->ws->info, &imax0, sizeof(int), hipMemcpyHostToDevice, c->stream));
-        mpf_stats stw{};
-        stw.n = N; stw.nb = nb; stw.superpanel = 1;
-        stw.fp16_fused = c->tune.fp16_fused != 0;
-        MPF_HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-        rc = factor_dist_wide(c, d_Aloc, ldloc, N, nb, d_ipiv, dist, o, L, bcast_fn, user, stw);
-        hipEventRecord(c->ev1, c->stream);
-        const hipError_t sew = hipStreamSynchronize(c->stream);
-        if (rc) return rc;
-        if (sew != hipSuccess) { c->err = std::string("distributed factorization failed: ") + hipGetErrorString(sew); return -2; }
-        float msw = 0;
-        hipEventElapsedTime(&msw, c->ev0, c->ev1);
-        stw.ms_total = msw;
-        int infow = 0;
-        MPF_HIP_TRY(c, hipMemcpy(&infow, &c->ws->info, sizeof(int), hipMemcpyDeviceToHost));
-        stw.info = infow == INT_MAX ? 0 : infow;
-        c->stats = stw;
-        return stw.info;
-    }
-    // Two-level schedule of the fp16 modes (factor_superpanel in mpf_host.cpp, carried over to the block-cyclic layout): sb panels
-    // form a super-panel; a panel updates only the INNER blocks (the super-panel's own and the next super-panel's first one) of
-    // this rank, panel by panel, in fp64; this rank's FAR columns live in an fp32 row-major working copy and get one update with
-    // K = sb * nb per super-panel, after the U block-row tasks.  What the single-GPU schedule reads from the matrix left of the
-    // panel -- the super-panel's earlier panels -- every rank keeps in a store of its own, assembled from the panel messages.
-    const bool force_generic_ = o.pivot_path == 1 || safe_pivots(c);
-    // (0 = automatic: the single-GPU rule, a function of N and the mode only -- the same on every rank, and the same summation grouping as
-    //  mpf_factor_dev: the multi-rank result stays bit-identical to the single-GPU one)
-    int want_sb = f64 ? 1 : (c->tune.superpanel_fp16 > 0 ? c->tune.superpanel_fp16 : ((o.trailing == MPF_TRAIL_FP16 && N >= 24576) ? 6 : 4));
-    if (!f64 && o.superpanel > 0) want_sb = o.superpanel > 8 ? 8 : o.superpanel;
-    const int sb = (!f64 && !force_generic_ && c->tune.fp16_work32 != 0 && hgetf2_lds_eligible(c, (int)N, (int)(nb < N ? nb : N)) &&
-                    (int64_t)(want_sb + 1) * nb < N) ? want_sb : 1;
-    const int64_t sbw = (int64_t)sb * nb;
-    if (!f64) {
-        const int64_t kimg = sbw < 8 * HP_MAXCOLS ? sbw : 8 * HP_MAXCOLS;
-        rc = sb > 1 ? mpf_ensure_h_images(c, N + HP_MAXCOLS + 64, (int)kimg, true) : mpf_ensure_h_images(c, N, nb, false);
-        if (rc) return rc;
-    }
-    if (sb > 1) {
-        const int64_t wneed = N * (lcols > 0 ? lcols : 1), sneed = N * sbw;
-        MPF_HIP_TRY(c, c->dist_w32.grow(wneed));
-        MPF_HIP_TRY(c, c->dist_spl.grow(sneed));
-    }
-    if (!c->xstream && dist->world > 1 && c->tune.dist_instalments) {   // exchange stream of the panel's instalments
-        int lo = 0, hi = 0;
-        hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (hipStreamCreateWithPriority(&c->xstream, hipStreamNonBlocking, hi) != hipSuccess) c->xstream = nullptr;
-    }
-    // ---- what every rank must decide alike (ADVICE r3) ------------------------------------------------------------------------------
-    // How many broadcasts a panel message travels in, and the one- / two-level choice, follow from rank-local state: which streams
-    // could be created, what this device's pivot kernel can hold, per-context options.  Ranks that disagreed would issue different
-    // collectives (a hang) or factor with different roundings.  Every rank's values go round once (one 64-byte broadcast per rank)
-    // and everyone takes the minimum; `sb` differing is an error on every rank (the buffers above were sized for the local value).
-    long long agreed[8];
-    {
-        hp_query_residency(c);
-        // rows this device's pivot kernel can take beside the workgroups of the pipelined chain's gated interchange kernel (which wait for it)
-        const long long lds_rows = hgetf2_capacity_rows(c, laswp_gated_grid(nb));
-        const bool two_ = !(o.no_lookahead || !c->pstream);
-        long long mine[8] = {two_ && c->tune.chain_pipeline != 0 && c->tstream != nullptr && !force_generic_ && c->tune.dist_instalments && c->xstream ? 1 : 0,
-                             sb, -(long long)c->tune.dist_instalment_min_bytes, c->tune.dpanel_fused_form ? 1 : 0, lds_rows < HP_R * (long long)HP_MAXG ? lds_rows : HP_R * (long long)HP_MAXG,
-                             two_ ? 1 : 0, 0, 0};
-        for (int i = 0; i < 8; ++i) agreed[i] = mine[i];
-        if (dist->world > 1) {
-            long long *dv = (long long *)c->dist_buf[0].get();   // (free until the first panel message)
-            for (int root = 0; root < dist->world; ++root) {
-                if (root == dist->rank) MPF_HIP_TRY(c, hipMemcpyAsync(dv, mine, sizeof mine, hipMemcpyHostToDevice, c->stream));
-                const int e = bcast_fn(user, dv, (int64_t)sizeof mine, root, (void *)c->stream);
-                if (e) return e < 0 ? e : -5;
-                long long got[8];
-                MPF_HIP_TRY(c, hipMemcpyAsync(got, dv, sizeof got, hipMemcpyDeviceToHost, c->stream));
-                MPF_HIP_TRY(c, hipStreamSynchronize(c->stream));
-                for (int i = 0; i < 8; ++i) if (got[i] < agreed[i]) agreed[i] = got[i];
-            }
-        }
-        if (agreed[1] != sb) { c->err = "mpf_factor_dist: the ranks disagree on the super-panel width (options superpanel_fp16 / fp16_work32 / safe_pivots must be the same on every rank)"; return -1; }
-    }
-    const bool inst_ok = agreed[0] != 0;
-    const long long inst_min_bytes = -agreed[2], lds_rows_max = agreed[4];
-    const bool fused_form_all = agreed[3] != 0;
-    // fp64 mode: this rank's columns right of the current panel live in a ROW-major working copy (as factor_lookahead_rm's): an
-    // interchange moves contiguous row segments instead of one 64-byte sector per moved row and column; the update is the same MFMA
-    // kernel on the transposed problem (c = fma(-u, l, c), kk ascending: the same bits).  Rank-local choice: results do not depend on it.
-    const bool rm = f64 && lcols > 0 && c->tune.fp64_rowmajor && N >= c->tune.fp64_rowmajor_min_n && N > nb &&
-                    mpf_ensure_rowmajor_copy(c, N, lcols, nb) == 0;
-    double *Rl = rm ? c->r64 : nullptr;
-    const int64_t ldr = lcols > 0 ? lcols : 1;
-    rc = mpf_factor_setup(c, N, nb, L.nblocks, true);   // per-panel moved-row lists + scratch of the deferred left-hand interchanges
+    const bool wide = nb > HP_MAXCOLS;   // wide panels: the generic schedule (reference order, one stream)
+    rc = wide ? d.begin(false) : d.set_up();
     if (rc) return rc;
-    mpf_stats st{};
-    st.n = N; st.nb = nb; st.superpanel = sb;
-    st.fp16_fused = c->tune.fp16_fused != 0;   // (every rank's own option: the ranks must agree on it, include/mpf_c.h)
-    hipStream_t S = c->stream, P = (o.no_lookahead || !c->pstream) ? c->stream : c->pstream;
-    const bool two = P != S;
-    EvPool ev(c);
-    ev.keep = &st.ms_gemm;
-    MPF_HIP_TRY(c, hipEventRecord(c->ev0, S));
-    if (two) { hipEvent_t e = ev.get(); hipEventRecord(e, S); hipStreamWaitEvent(P, e, 0); }
-
-    auto buf_of = [&](int b) { return (char *)c->dist_buf[b & 1].get(); };
-    auto rows_of = [&](int b) { return N - (int64_t)b * nb; };
-    auto ldp_of = [&](int b) { return rows_of(b) + PANEL_PAD; };
-    auto list_off = [&](int b) { return (size_t)ldp_of(b) * L.width(b) * 8; };
-    auto piv_ptr = [&](int b, int q) { return (int *)((double *)buf_of(b) + (size_t)(32 * q) * ldp_of(b) + rows_of(b)); };  // pivots of sub-panel q
-    const bool piped_ok = c->tune.chain_pipeline != 0 && c->tstream != nullptr;
-    const bool force_generic = force_generic_;   // as mpf_factor_dev: GPUs shared with other processes
-    // Number of 32-column instalments the message of panel b travels in (0: one broadcast after the whole chain).  A function
-    // of the shape and of options that must be the same on every rank (chain_pipeline, pivot_path / safe_pivots, dist_instalments).
-    // Small panels go in one piece: an instalment costs a collective's latency.
-    auto pieces_of = [&](int b) -> int {
-        const int pc = L.width(b), pr = (int)rows_of(b);
-        if (!inst_ok) return 0;
-        if (pc > HP_MAXCOLS || pr > lds_rows_max) return 0;                       // (every rank's pivot kernel can hold the panel)
-        if ((long long)pr * pc * 8 < inst_min_bytes) return 0;
-        return (fused_form_all && pc % 32 == 0 && pc >= 64) ? pc / 32 : 0;        // = dgetf2_npv_pieces with the agreed option
-    };
-    // owner only: pivots, interchange of the panel's own columns, fp64 panel, pack -- on stream s (and T).  With instalments
-    // (np > 0) ev_piece[q] is recorded once instalment q (32 packed columns + their pivots; the last one: + the moved-row list)
-    // is complete in the message buffer.
-    std::vector<hipEvent_t> ev_piece;
-    auto chain = [&](int b, hipStream_t s, int np) -> int {
-        const int64_t k = (int64_t)b * nb;
-        const int pc = L.width(b), pr = (int)(N - k);
-        const int64_t ldp = ldp_of(b);
-        StreamSwap sw(c, s);
-        double *Ap = d_Aloc + L.lcol(b) * ldloc + k;
-        MovedList *ml = c->lists + b;
-        char *buf = buf_of(b);
-        hipEvent_t before_pivots = ev.get();
-        hipEventRecord(before_pivots, s);
-        const bool lds = !force_generic && hgetf2_lds_eligible(c, pr, pc);
-        // the fp64 panel follows the pivot kernel 32 columns behind on the helper stream (see chain_behind in mpf_host.cpp) -- where
-        // the panel's workgroups fit beside the gated interchange kernel's, which wait for it while sitting on CUs
-        const int waiters = (c->tune.gate_wait_value && c->hp_signal) ? 0 : laswp_gated_grid(pc);
-        const bool will_pipe = piped_ok && lds && hgetf2_fits_beside(c, pr, pc, waiters);
-        int e = ev.timed(st.ms_hpanel, s, [&] {
-            if (lds) return launch_hgetf2(c, Ap, ldloc, nullptr, 0, pr, pc, (int)k, d_ipiv + k, nullptr, 0, ml, will_pipe ? waiters : 0, f64 ? HP_FP64_WINDOW_ROWS : 0);
-            st.pivot_path = 1; // generic pivots, then the sequential swap list resolved into a moved-row list (laswp.hip)
-            int e2 = launch_hgetf2_generic(c, Ap, ldloc, nullptr, 0, pr, pc, (int)k, d_ipiv + k, nullptr, 0);
-            if (!e2) e2 = launch_laswp_plan(c, d_ipiv + k, (int)k, pc, ml);
-            return e2; });
-        if (e) return e;
-        hipEvent_t pivots_done = ev.get();
-        hipEventRecord(pivots_done, s);
-        const int npp = will_pipe ? dgetf2_npv_pieces(c, pc) : 0;
-        if (np > 0 && npp != np) { c->err = "mpf_factor_dist: instalment count differs from the agreed one"; return -1; }
-        auto pack = [&](hipStream_t ps, int c0, int nc) -> int {   // columns [c0, c0 + nc) of the panel + their sub-panels' pivots
-            MPF_HIP_TRY(c, hipMemcpy2DAsync(buf + (size_t)c0 * ldp * 8, (size_t)ldp * 8, Ap + (int64_t)c0 * ldloc, (size_t)ldloc * 8, (size_t)pr * 8, (size_t)nc,
-                                            hipMemcpyDeviceToDevice, ps));
-            for (int q = c0 / 32; q * 32 < c0 + nc; ++q) {
-                const int w = (pc - 32 * q) < 32 ? (pc - 32 * q) : 32;
-                MPF_HIP_TRY(c, hipMemcpyAsync(piv_ptr(b, q), d_ipiv + k + 32 * q, (size_t)w * 4, hipMemcpyDeviceToDevice, ps));
-            }
-            return 0;
-        };
-        if (npp > 0) {
-            hipStream_t T = c->tstream;
-            hipStreamWaitEvent(T, before_pivots, 0);
-            {
-                StreamSwap swt(c, T);
-                hipEvent_t t0 = ev.get(), t1 = ev.get();
-                hipEventRecord(t0, T);
-                for (int q = 0; q < npp && !e; ++q) {
-                    e = launch_laswp_block_gated(c, d_Aloc + L.lcol(b) * ldloc, ldloc, pc, (int)k + 32 * q, 32, d_ipiv + k + 32 * q, N, 32 * (q + 1));
-                    if (!e) e = launch_dgetf2_npv_piece(c, Ap, ldloc, pr, pc, o.fused_panel, (int)k, q);
-                    if (!e && np > 0) {   // instalment q leaves as it is: the interchanges still to come are applied to the message copy
-                        e = pack(T, 32 * q, 32);
-                        // (the matrix holds the UNfactored diagonal tile until the last piece has run: dpanel.hip)
-                        if (!e && q < np - 1) e = launch_dpanel_tile_copy(c, (double *)buf + (size_t)(32 * q) * ldp + 32 * q, ldp, q);
-                        if (!e && q == np - 1) {
-                            hipStreamWaitEvent(T, pivots_done, 0);   // the moved-row list is complete when the pivot kernel has ended
-                            MPF_HIP_TRY(c, hipMemcpyAsync(buf + list_off(b), ml, sizeof(MovedList), hipMemcpyDeviceToDevice, T));
-                        }
-                        if (!e) { ev_piece[(size_t)q] = ev.get(); hipEventRecord(ev_piece[(size_t)q], T); }
-                    }
-                }
-                hipEventRecord(t1, T);
-                if (c->tune.timeline || c->tune.event_timers >= 2) ev.pairs.push_back({t0, t1, &st.ms_dpanel, nullptr});
-            }
-            hipEvent_t eb = ev.get();
-            hipEventRecord(eb, T);
-            hipStreamWaitEvent(s, eb, 0);
-        } else e = ev.timed(st.ms_dpanel, s, [&] {
-            int e2 = launch_laswp_from_list(c, d_Aloc + L.lcol(b) * ldloc, ldloc, pc, ml);
-            if (!e2) e2 = launch_dgetf2_npv(c, Ap, ldloc, pr, pc, o.fused_panel, (int)k);
-            return e2; });
-        if (e) return e;
-        if (np == 0) {   // the whole message at once, from the finished panel
-            e = pack(s, 0, pc);
-            if (!e) MPF_HIP_TRY(c, hipMemcpyAsync(buf + list_off(b), ml, sizeof(MovedList), hipMemcpyDeviceToDevice, s));
-        }
-        st.panels++;
-        return e;
-    };
-    // every rank: the exchange of panel b on stream s, then (non-owners) pivots and moved list out of the message.
-    // np == 0: ONE broadcast.  np > 0: np instalments; after instalment q every rank applies sub-panel q's 32 interchanges to
-    // the instalments already there (what the owner's matrix got from laswp_block while the later instalments were still being
-    // factored): the assembled message is the finished panel.
-    auto exchange = [&](int b, hipStream_t s, int np) -> int {
-        const int pc = L.width(b);
-        const int64_t k = (int64_t)b * nb, ldp = ldp_of(b);
-        char *buf = buf_of(b);
-        if (np == 0) {
-            if (L.world > 1) {
-                const int e = bcast_fn(user, buf, (int64_t)(list_off(b) + sizeof(MovedList)), L.owner(b), (void *)s);
-                if (e) return e < 0 ? e : -5;
-            }
-        } else {
-            StreamSwap sw(c, s);
-            for (int q = 0; q < np; ++q) {
-                if (L.mine(b)) hipStreamWaitEvent(s, ev_piece[(size_t)q], 0);
-                if (L.world > 1) {
-                    const size_t off = (size_t)(32 * q) * ldp * 8;
-                    const size_t bytes = q == np - 1 ? list_off(b) + sizeof(MovedList) - off : (size_t)32 * ldp * 8;
-                    const int e = bcast_fn(user, buf + off, (int64_t)bytes, L.owner(b), (void *)s);
-                    if (e) return e < 0 ? e : -5;
-                }
-                if (q > 0) {   // rows of the message are rows k.. of the matrix: address it from the matrix' row 0
-                    const int e = launch_laswp_block(c, (double *)buf - k, ldp, 32 * q, (int)k + 32 * q, 32, piv_ptr(b, q), N);
-                    if (e) return e;
-                }
-            }
-        }
-        if (!L.mine(b)) {
-            const int nq = (pc + 31) / 32;
-            MPF_HIP_TRY(c, hipMemcpy2DAsync(d_ipiv + k, 128, piv_ptr(b, 0), (size_t)32 * ldp * 8, 128, (size_t)(pc / 32), hipMemcpyDeviceToDevice, s));
-            if (pc % 32) MPF_HIP_TRY(c, hipMemcpyAsync(d_ipiv + k + 32 * (nq - 1), piv_ptr(b, nq - 1), (size_t)(pc % 32) * 4, hipMemcpyDeviceToDevice, s));
-            MPF_HIP_TRY(c, hipMemcpyAsync(c->lists + b, buf + list_off(b), sizeof(MovedList), hipMemcpyDeviceToDevice, s));
-        }
-        return 0;
-    };
-    const int kst = (int)((sbw + 63) & ~(int64_t)63);                                      // row stride of the far U image (elements)
-    const int64_t far_cap = sb > 1 ? lcols - L.first_local_col_after(sb) : 0;              // most far columns any super-panel has here
-    const int64_t inner_u_off = far_cap > 0 ? far_cap * kst : 0;                           // the inner steps' U image lives behind the far image
-    const int64_t brow_l_off = (int64_t)N * c->h_kmax;                                     // block-row L images: rows the image buffers hold beyond N
-    // interchange + TRSM + trailing update of panel b on the local columns [c0, c0 + nc) (all right of block b)
-    bool image_ready = false;
-    auto update = [&](int b, int64_t c0, int64_t nc) -> int {
-        if (nc <= 0) return 0;
-        const int64_t k = (int64_t)b * nb;
-        const int pc = L.width(b);
-        const int64_t pr = N - k, m = pr - pc;
-        const double *Pb = (const double *)buf_of(b);
-        const int64_t ldp = ldp_of(b);
-        if (rm) {
-            // interchange of contiguous row segments, TRSM through strides, L21 row-major once per panel, the update on the transposed
-            // problem, then the finished U rows of these columns go home to the column-major matrix
-            double *LT = c->rm_lt;
-            int e = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_from_list_rm64(c, Rl + c0, ldr, nc, c->lists + b); });
-            if (!e) e = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu_strided(c, pc, nc, Pb, ldp, Rl + k * ldr + c0, ldr, 1); });
-            if (!e && m > 0) {
-                if (!image_ready) { e = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, (double *)Pb + pc, ldp, LT, pc, m, pc, true); }); image_ready = true; }
-                if (!e) e = ev.timed(st.ms_gemm, S, [&] { return launch_dgemm_minus(c, nc, m, pc, Rl + k * ldr + c0, ldr, LT, pc, Rl + (k + pc) * ldr + c0, ldr); });
-                count_gemm(st, o, m, nc, pc);
-            }
-            if (!e) e = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, d_Aloc + c0 * ldloc + k, ldloc, Rl + k * ldr + c0, ldr, pc, nc, false); });
-            return e;
-        }
-        int e = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_from_list(c, d_Aloc + c0 * ldloc, ldloc, nc, c->lists + b); });
-        double *U12 = d_Aloc + c0 * ldloc + k;
-        if (!e) e = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu(c, pc, nc, Pb, ldp, U12, ldloc); });
-        if (!e && m > 0) {
-            e = ev.timed(st.ms_gemm, S, [&] {
-                if (f64) return launch_dgemm_minus(c, m, nc, pc, Pb + pc, ldp, U12, ldloc, U12 + pc, ldloc);
-                int e2 = 0;
-                if (!image_ready) { e2 = launch_cvt_l21(c, Pb + pc, ldp, m, pc, split); image_ready = true; } // once per panel
-                if (sb == 1) { if (!e2) e2 = launch_hgemm_minus(c, m, nc, pc, U12, ldloc, U12 + pc, ldloc, split); }
-                else {   // the inner steps' U image lives behind the far columns' image
-                    if (!e2) e2 = launch_cvt_u12(c, U12, ldloc, pc, nc, split, inner_u_off);
-                    if (!e2) e2 = launch_hgemm_images(c, m, nc, pc, U12 + pc, ldloc, false, split, 0, 0, inner_u_off);
-                }
-                return e2; });
-            count_gemm(st, o, m, nc, pc);
-        }
-        return e;
-    };
-    // ---- two-level schedule: this rank's far columns (sb > 1) -------------------------------------------------------------
-    float *W = c->dist_w32;
-    double *SPL = c->dist_spl;
-    const int64_t ldw = lcols > 0 ? lcols : 1;
-    auto sp_first = [&](int b) { return (b / sb) * sb; };                                        // first block of b's super-panel
-    auto sp_end = [&](int b) { const int e = sp_first(b) + sb; return e < L.nblocks ? e : L.nblocks; };   // one past its last block
-    auto inner_end_blk = [&](int b) { const int e = sp_end(b) + 1; return e < L.nblocks ? e : L.nblocks; };  // one past the look-ahead block
-    auto far0 = [&](int b) { return sb > 1 ? L.first_local_col_after(inner_end_blk(b) - 1) : lcols; };     // first local far column
-    int far_img = 1;
-    // the super-panel's panels as received: eager interchanges of panel b on the earlier ones, then panel b itself
-    auto spl_add = [&](int b) -> int {
-        const int p = b - sp_first(b), pc = L.width(b);
-        const int64_t k = (int64_t)b * nb;
-        int e = 0;
-        if (p > 0) e = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_from_list(c, SPL, N, (int64_t)p * nb, c->lists + b); });
-        if (!e) MPF_HIP_TRY(c, hipMemcpy2DAsync(SPL + (int64_t)p * nb * N + k, (size_t)N * 8, buf_of(b), (size_t)ldp_of(b) * 8, (size_t)(N - k) * 8, (size_t)pc,
-                                                hipMemcpyDeviceToDevice, S));
-        return e;
-    };
-    // block-row task of panel b on the far columns (T_p of factor_superpanel): interchange on the working copy; the rows of block
-    // b lose L[b, earlier panels of the super-panel] U; they return to fp64; TRSM with the panel's L11; appended to the U image
-    auto far_task = [&](int b) -> int {
-        const int64_t f0 = far0(b), ncols = lcols - f0, kq = (int64_t)b * nb;
-        if (ncols <= 0) return 0;
-        const int p = b - sp_first(b), pc = L.width(b);
-        int e = spl_add(b);
-        if (!e) e = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_from_list_f32(c, W + f0, ldw, ncols, c->lists + b); });
-        if (!e && p > 0) {
-            const int K = p * nb;
-            e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_l21(c, SPL + kq, N, pc, K, split, 0, brow_l_off); });
-            if (!e) e = ev.timed(st.ms_trsm, S, [&] {
-                return launch_hgemm_images_rowmajor(c, pc, ncols, K, W + kq * ldw + f0, ldw, split, 0, brow_l_off, 0, 0, kst); }, &st.ms_blockrow);
-        }
-        if (!e) e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_f32_f64(c, W + kq * ldw + f0, ldw, d_Aloc + f0 * ldloc + kq, ldloc, pc, ncols); });
-        if (!e) e = ev.timed(st.ms_trsm, S, [&] {
-            return launch_dtrsm_llnu(c, pc, ncols, (const double *)buf_of(b), ldp_of(b), d_Aloc + f0 * ldloc + kq, ldloc); }, &st.ms_blockrow);
-        if (!e) e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_u12(c, d_Aloc + f0 * ldloc + kq, ldloc, pc, ncols, split, (int64_t)p * nb, kst); });
-        return e;
-    };
-    // the K = (super-panel width) update of the local far columns [col0, col0 + ncols); f0 = first far column of that super-panel
-    auto big_update = [&](int64_t s0, int64_t s1, int64_t f0, int64_t col0, int64_t ncols) -> int {
-        const int64_t mrows = N - s1;
-        const int K = (int)(s1 - s0);
-        if (ncols <= 0 || mrows <= 0) return 0;
-        const int e = ev.timed(st.ms_gemm, S, [&] {
-            return launch_hgemm_images_rowmajor(c, mrows, ncols, K, W + s1 * ldw + col0, ldw, split, far_img, 0, (col0 - f0) * kst, 0, kst); }, &st.ms_gemm_big);
-        const double opb = split ? 4.0 : 2.0;
-        count_gemm(st, o, mrows, ncols, K, 8.0);
-        st.gemm_big_flops += 2.0 * (double)mrows * (double)ncols * K;
-        st.gemm_big_bytes += 8.0 * (double)mrows * (double)ncols + opb * K * (double)(mrows + ncols);
-        st.gemm_big_launches++;
-        return e;
-    };
-    // end of b's super-panel: the operand image of L[s1.., s0..s1) once, the update on the columns that join the next inner region
-    // first (they return to fp64), then on the rest
-    auto superpanel_end = [&](int b) -> int {
-        const int64_t f0 = far0(b);
-        if (f0 >= lcols) return 0;
-        const int64_t s0 = (int64_t)sp_first(b) * nb, s1 = (int64_t)sp_end(b) * nb;
-        const int64_t f0n = far0(sp_end(b));                          // first far column of the next super-panel
-        int e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_l21(c, SPL + s1, N, N - s1, (int)(s1 - s0), split, far_img); });
-        if (!e) e = big_update(s0, s1, f0, f0, f0n - f0);
-        if (!e && f0n > f0) e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_f32_f64(c, W + s1 * ldw + f0, ldw, d_Aloc + f0 * ldloc + s1, ldloc, N - s1, f0n - f0); });
-        if (!e) e = big_update(s0, s1, f0, f0n, lcols - f0n);
-        far_img = 3 - far_img;
-        return e;
-    };
-    auto superpanel_begin = [&](int b) -> int {   // image blocks of odd width: the padding the kernels read beyond a block must be zero
-        const int64_t f0 = far0(b);
-        if (f0 >= lcols || nb % 64 == 0) return 0;
-        const size_t bytes = (size_t)(lcols - f0) * kst * sizeof(unsigned short);
-        MPF_HIP_TRY(c, hipMemsetAsync(c->h_U, 0, bytes, S));
-        if (split) MPF_HIP_TRY(c, hipMemsetAsync(c->h_U + c->h_rows * c->h_kmax, 0, bytes, S));
-        return 0;
-    };
-
-    rc = 0;
-    if (sb > 1 && far0(0) < lcols)   // this rank's far columns of the first super-panel go into the working copy
-        rc = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_f64_f32(c, d_Aloc + far0(0) * ldloc, ldloc, W + far0(0), ldw, N, lcols - far0(0)); });
-    if (!rc && L.live(0)) {
-        if (L.mine(0)) rc = chain(0, S, 0);
-        if (!rc) rc = exchange(0, S, 0);
-    }
-    if (!rc && rm)   // everything this rank owns goes into the row-major copy (block 0, if it is here, is finished: its copy is never read)
-        rc = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, d_Aloc, ldloc, Rl, ldr, N, lcols, true); });
-    hipStream_t X = c->xstream ? c->xstream : P;   // exchange stream of the instalments (the owner's P runs the pivot kernel meanwhile)
-    for (int b = 0; L.live(b) && rc == 0; ++b) {
-        const int64_t k = (int64_t)b * nb;
-        const int pc = L.width(b);
-        const int nxt = b + 1;
-        const bool has_next = L.live(nxt), own_next = has_next && L.mine(nxt), trailing = k + pc < N;
-        int64_t rest0 = L.first_local_col_after(b);
-        image_ready = false;
-        hipEvent_t e2 = nullptr;
-        if (trailing && own_next) { // my block of panel b+1 first, then its chain on the side stream
-            rc = update(b, L.lcol(nxt), L.width(nxt));
-            if (!rc && rm)   // the next panel's columns return to the column-major matrix before its chain (rows k + pc ..; its U rows went with the update)
-                rc = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, d_Aloc + L.lcol(nxt) * ldloc + k + pc, ldloc, Rl + (k + pc) * ldr + L.lcol(nxt), ldr,
-                                                                            N - k - pc, L.width(nxt), false); });
-            if (rc) break;
-            rest0 = L.lcol(nxt) + L.width(nxt);
-        }
-        if (has_next) {
-            const int np = pieces_of(nxt);
-            hipStream_t xs = np > 0 ? X : P;
-            if (two) { // strip done; receive buffer free (its last reader was update b - 1, in front of this event on S)
-                hipEvent_t e1 = ev.get(); hipEventRecord(e1, S); hipStreamWaitEvent(P, e1, 0);
-                if (xs != P) hipStreamWaitEvent(xs, e1, 0);
-            }
-            ev_piece.assign((size_t)(np > 0 ? np : 1), nullptr);
-            if (own_next) rc = chain(nxt, P, np);
-            if (!rc) rc = exchange(nxt, xs, np);
-            if (rc) break;
-            if (two) {
-                e2 = ev.get(); hipEventRecord(e2, xs);
-                if (xs != P && own_next) { hipEvent_t e3 = ev.get(); hipEventRecord(e3, P); hipStreamWaitEvent(S, e3, 0); }   // the owner's chain itself
-            }
-        }
-        if (sb == 1) { if (trailing && rest0 < lcols) rc = update(b, rest0, lcols - rest0); }
-        else if (trailing) {
-            // inner blocks right of the strip, panel by panel in fp64; far columns: block-row task now, K = sb * nb update at the
-            // end of the super-panel (it runs under the chain of the next super-panel's first panel, launched above)
-            const int64_t f0 = far0(b);
-            if (b == sp_first(b)) rc = superpanel_begin(b);
-            if (!rc && rest0 < f0) rc = update(b, rest0, f0 - rest0);
-            if (!rc) rc = far_task(b);
-            if (!rc && b + 1 == sp_end(b)) rc = superpanel_end(b);
-        }
-        if (e2) hipStreamWaitEvent(S, e2, 0);
-        if (o.verbose) printf("[rank %d] panel %d (k=%lld) owner %d\n", L.rank, b, (long long)k, L.owner(b));
-    }
-    if (!rc) rc = ev.timed(st.ms_laswp, S, [&] { return launch_lazy_left_swaps(c, d_Aloc, ldloc, N, nb, L.nblocks, c->lists, 1, L.world, L.rank); });
-    hipEventRecord(c->ev1, S);
-    hipError_t se = hipStreamSynchronize(S);
-    hipError_t sp = two ? hipStreamSynchronize(P) : hipSuccess;
-    if (two && c->xstream) { const hipError_t sx = hipStreamSynchronize(c->xstream); if (sp == hipSuccess) sp = sx; }
-    if (two && c->tstream) { const hipError_t stt = hipStreamSynchronize(c->tstream); if (sp == hipSuccess) sp = stt; }
-    if (rc) return rc;
-    if (se != hipSuccess || sp != hipSuccess) { c->err = std::string("distributed factorization failed: ") + hipGetErrorString(se != hipSuccess ? se : sp); return -2; }
-    ev.collect();
-    float ms = 0;
-    hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    st.ms_total = ms;
-    st.lookahead = two ? 1 : 0;
-    int info = 0, flags0 = 0;
-    MPF_HIP_TRY(c, hipMemcpy(&info, &c->ws->info, sizeof(int), hipMemcpyDeviceToHost));
-    MPF_HIP_TRY(c, hipMemcpy(&flags0, &c->ws->hp_timeouts, sizeof(int), hipMemcpyDeviceToHost));
-    st.info = info == INT_MAX ? 0 : info;
-    st.hpanel_timeouts = flags0;
-    c->stats = st;
-    if (flags0) { c->err = "fp16 pivot kernel: inter-workgroup hand-off timed out (buffers invalid; use pivot_path = 1)"; return -4; }
-    return st.info; // this rank's panels only: the caller combines (min over the positive values)
+    return d.report(wide ? d.run_wide() : d.run());
 }
 
 int mpf_dist_set_p2p(mpf_ctx *c, mpf_p2p_fn fn, void *user) {

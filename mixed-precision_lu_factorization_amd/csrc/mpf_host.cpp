@@ -2,6 +2,7 @@
 // as an asynchronous HIP stream of kernels with no per-panel host synchronisation), the refinement
 // solve, the C ABI (include/mpf_c.h) and the drop-in C++ symbol MPF() (include/MPF.h).
 #include "solve_common.h"
+#include "factor_common.h"
 #include "../../include/MPF.h"
 #include <climits>
 #include <cstdio>
@@ -104,6 +105,128 @@ void tuning_from_env(MpfTuning &t) {   // called by mpf_create only
 static int fail(mpf_ctx *c, int code, const std::string &msg) {
     if (c) c->err = msg; else g_noctx_err = msg;
     return code;
+}
+
+// ---- pieces all schedules share, mpf_factor_dist's among them (factor_common.h) --------------------------------------------------
+int factor_check_args(mpf_ctx *c, const char *who, const char *ldname, int64_t N, int32_t nb, int64_t ld, const mpf_opts &o) {
+    const std::string w = std::string(who) + ": ";
+    if (N <= 0 || nb <= 0) return fail(c, -1, w + "N and panel width must be positive");
+    if (ld < N) return fail(c, -1, w + ldname + " < N");
+    if (N > INT_MAX / 2) return fail(c, -1, w + "N too large");
+    if (nb > 65535) return fail(c, -1, w + "panel width > 65535");
+    if (o.trailing < MPF_TRAIL_FP64 || o.trailing > MPF_TRAIL_FP16X3) return fail(c, -1, w + "unknown trailing mode");
+    return 0;
+}
+
+int factor_report(mpf_ctx *c, mpf_stats &st, int rc, const std::function<hipError_t()> &wait, const char *what, const char *timeout_text) {
+    hipEventRecord(c->ev1, c->stream);
+    const hipError_t se = wait();
+    if (rc) return rc;
+    if (se != hipSuccess) return fail(c, -2, std::string(what) + " failed: " + hipGetErrorString(se));
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    st.ms_total = ms;
+    int info = 0, flags0 = 0;
+    MPF_HIP_TRY(c, hipMemcpy(&info, &c->ws->info, sizeof(int), hipMemcpyDeviceToHost));
+    MPF_HIP_TRY(c, hipMemcpy(&flags0, &c->ws->hp_timeouts, sizeof(int), hipMemcpyDeviceToHost));
+    st.info = info == INT_MAX ? 0 : info;
+    st.hpanel_timeouts = flags0;
+    c->stats = st;
+    return flags0 ? fail(c, -4, timeout_text) : st.info;
+}
+
+int panel_pivots(const FactorArgs &f, const PanelView &v, hipStream_t s, int waiters, bool generic) {
+    mpf_ctx *c = f.c;
+    return f.ev.timed(f.st.ms_hpanel, s, [&] {
+        if (!generic) return launch_hgetf2(c, v.A + v.k, v.lda, nullptr, 0, v.pr, v.pc, (int)v.k, v.ipiv, nullptr, 0, v.ml, waiters, pref_window_rows(f.o));
+        f.st.pivot_path = 1;
+        int e = launch_hgetf2_generic(c, v.A + v.k, v.lda, nullptr, 0, v.pr, v.pc, (int)v.k, v.ipiv, nullptr, 0);
+        if (!e) e = launch_laswp_plan(c, v.ipiv, (int)v.k, v.pc, v.ml);
+        return e; });
+}
+
+int panel_tail(const FactorArgs &f, const PanelView &v, hipStream_t s) {
+    return f.ev.timed(f.st.ms_dpanel, s, [&] {
+        int e = launch_laswp_from_list(f.c, v.A, v.lda, v.pc, v.ml);
+        if (!e) e = launch_dgetf2_npv(f.c, v.A + v.k, v.lda, v.pr, v.pc, f.o.fused_panel, (int)v.k);
+        return e; });
+}
+
+int panel_pieces(const FactorArgs &f, const PanelView &v, int np, const std::function<int(int)> &after_piece) {
+    int e = 0;
+    for (int q = 0; q < np && !e; ++q) {
+        e = launch_laswp_block_gated(f.c, v.A, v.lda, v.pc, (int)v.k + 32 * q, 32, v.ipiv + 32 * q, f.N, 32 * (q + 1));
+        if (!e) e = launch_dgetf2_npv_piece(f.c, v.A + v.k, v.lda, v.pr, v.pc, f.o.fused_panel, (int)v.k, q);
+        if (!e && after_piece) e = after_piece(q);
+    }
+    return e;
+}
+
+int launch_generic_update(mpf_ctx *c, const mpf_opts &o, int64_t m, int64_t n, int pc, const double *L21, int64_t ldl, double *U12, int64_t ldu) {
+    if (o.trailing == MPF_TRAIL_FP64) return launch_dgemm_minus(c, m, n, pc, L21, ldl, U12, ldu, U12 + pc, ldu);
+    int e = 0;
+    const int kcmax = c->h_kmax;                 // K capacity of the fp16 operand images
+    for (int k0 = 0; k0 < pc && !e; k0 += kcmax) {
+        const int kc = (pc - k0) < kcmax ? (pc - k0) : kcmax;
+        e = launch_cvt_l21(c, L21 + (int64_t)k0 * ldl, ldl, m, kc, o.trailing == MPF_TRAIL_FP16X3);
+        if (!e) e = launch_hgemm_minus(c, m, n, kc, U12 + k0, ldu, U12 + pc, ldu, o.trailing == MPF_TRAIL_FP16X3);
+    }
+    return e;
+}
+
+int far_zero_padding(const FactorArgs &f, int64_t ncols, const ImageGeom &g) {
+    mpf_ctx *c = f.c;
+    if (f.o.trailing == MPF_TRAIL_FP64 || f.nb % 64 == 0 || ncols <= 0) return 0;
+    const size_t bytes = (size_t)ncols * g.kst * sizeof(unsigned short);
+    MPF_HIP_TRY(c, hipMemsetAsync(c->h_U, 0, bytes, c->stream));
+    if (f.o.trailing == MPF_TRAIL_FP16X3) MPF_HIP_TRY(c, hipMemsetAsync(c->h_U + c->h_rows * c->h_kmax, 0, bytes, c->stream));
+    return 0;
+}
+
+// Full width: one launch of each kind per block instead of one per column piece (a 256-row TRSM costs the same ~90 us for 7000 columns
+// as for 28000).  The rows of block p lose what the one-level schedule would have given them panel by panel: identical bits.
+int far_block_row(const FactorArgs &f, const FarView &v, const ImageGeom &g, int64_t s0, int p) {
+    mpf_ctx *c = f.c; EvPool &ev = f.ev; mpf_stats &st = f.st;
+    hipStream_t S = c->stream;
+    const bool f64 = f.o.trailing == MPF_TRAIL_FP64, split = f.o.trailing == MPF_TRAIL_FP16X3;
+    const int nb = f.nb, K = p * nb;
+    const int64_t kq = s0 + K, n = v.ncols;
+    MovedList *ml = c->lists + (kq / nb);
+    double *Ar = v.A + kq;                                  // the block's rows of the far columns
+    float *Wr = v.W ? v.W + kq * v.ldw : nullptr;
+    int e = ev.timed(st.ms_laswp, S, [&] { return v.W ? launch_laswp_from_list_f32(c, v.W, v.ldw, n, ml) : launch_laswp_from_list(c, v.A, v.lda, n, ml); });
+    if (!e && p > 0) {
+        if (f64) e = ev.timed(st.ms_trsm, S, [&] { return launch_dgemm_minus(c, nb, n, K, v.Lsp + kq, v.ldl, v.A + s0, v.lda, Ar, v.lda); }, &st.ms_blockrow);
+        else {
+            e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_l21(c, v.Lsp + kq, v.ldl, nb, K, split, 0, g.brow_l_off); });
+            if (!e) e = ev.timed(st.ms_trsm, S, [&] {
+                return v.W ? launch_hgemm_images_rowmajor(c, nb, n, K, Wr, v.ldw, split, 0, g.brow_l_off, 0, 0, g.kst)
+                           : launch_hgemm_images(c, nb, n, K, Ar, v.lda, false, split, 0, g.brow_l_off, 0, 0, g.kst); }, &st.ms_blockrow);
+        }
+    }
+    if (!e && v.W) e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_f32_f64(c, Wr, v.ldw, Ar, v.lda, nb, n); });
+    if (!e) e = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu(c, nb, n, v.L11, v.ld11, Ar, v.lda); }, &st.ms_blockrow);
+    if (!e && !f64) e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_u12(c, Ar, v.lda, nb, n, split, (int64_t)K, g.kst); });
+    return e;
+}
+
+int far_big_update(const FactorArgs &f, const FarView &v, const ImageGeom &g, int64_t s0, int64_t s1, int64_t col, int64_t ncols, int img) {
+    mpf_ctx *c = f.c; mpf_stats &st = f.st;
+    const bool f64 = f.o.trailing == MPF_TRAIL_FP64, split = f.o.trailing == MPF_TRAIL_FP16X3;
+    const int64_t mrows = f.N - s1;
+    const int K = (int)(s1 - s0);
+    if (ncols <= 0 || mrows <= 0) return 0;
+    double *C = v.A + col * v.lda + s1;
+    const int e = f.ev.timed(st.ms_gemm, c->stream, [&] {
+        if (f64) return launch_dgemm_minus(c, mrows, ncols, K, v.Lsp + s1, v.ldl, v.A + col * v.lda + s0, v.lda, C, v.lda);
+        return v.W ? launch_hgemm_images_rowmajor(c, mrows, ncols, K, v.W + s1 * v.ldw + col, v.ldw, split, img, 0, col * g.kst, 0, g.kst)
+                   : launch_hgemm_images(c, mrows, ncols, K, C, v.lda, false, split, img, 0, col * g.kst, 0, g.kst); }, &st.ms_gemm_big);
+    const double cb = v.W ? 8.0 : 16.0, opb = f64 ? 8.0 : (split ? 4.0 : 2.0);
+    count_gemm(st, f.o, mrows, ncols, K, cb);
+    st.gemm_big_flops += 2.0 * (double)mrows * (double)ncols * K;
+    st.gemm_big_bytes += cb * (double)mrows * (double)ncols + opb * K * (double)(mrows + ncols);
+    st.gemm_big_launches++;
+    return e;
 }
 
 extern "C" {
@@ -413,22 +536,6 @@ static int trail_gemm(mpf_ctx *c, const mpf_opts &o, int64_t m, int64_t n, int p
     return launch_dgemm_minus(c, m, n, pc, L21, lda, U12, lda, C, lda);
 }
 
-// ---- pieces the schedules share ----------------------------------------------------------------------------------------
-// what every schedule of one factorization works on (mpf_factor_dev's arguments, the event pool, the statistics)
-struct FactorArgs {
-    mpf_ctx *c; EvPool &ev; mpf_stats &st; const mpf_opts &o;
-    double *d_A; int64_t lda, N; int32_t nb; int32_t *d_ipiv;
-};
-
-// panel rows from which the pivot kernel takes its column-window form (launch_hgetf2's prefer_window_rows): the fp64 schedules only
-static int pref_window_rows(const mpf_opts &o) { return o.trailing == MPF_TRAIL_FP64 ? HP_FP64_WINDOW_ROWS : 0; }
-
-// `into` goes on only behind everything queued on `from` so far
-static void stream_join(EvPool &ev, hipStream_t from, hipStream_t into) {
-    hipEvent_t e = ev.get();
-    hipEventRecord(e, from);
-    hipStreamWaitEvent(into, e, 0);
-}
 
 // Single-stream schedule with a host synchronisation after every phase (per-phase timers).
 static int factor_sync_timed(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, int32_t *d_ipiv,
@@ -493,7 +600,6 @@ static int factor_generic(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32
     ev.keep = &st.ms_gemm;
     hipStream_t S = c->stream;
     int rc = 0;
-    const bool split = o.trailing == MPF_TRAIL_FP16X3;
     for (int64_t k = 0; k < N && rc == 0; k += nb) {
         const int pc = (int)((N - k) < nb ? (N - k) : nb);   // MPF.cu:101
         const int pr = (int)(N - k);                         // MPF.cu:102
@@ -526,16 +632,7 @@ static int factor_generic(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32
             double *A12 = d_A + (k + pc) * lda + k;
             rc = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu(c, pc, n, Ap, lda, A12, lda); });             // :215
             if (rc) break;
-            rc = ev.timed(st.ms_gemm, S, [&] {                                                                         // :230
-                if (o.trailing == MPF_TRAIL_FP64) return launch_dgemm_minus(c, n, n, pc, Ap + pc, lda, A12, lda, A12 + pc, lda);
-                int e = 0;
-                const int kcmax = c->h_kmax;                 // K capacity of the fp16 operand images
-                for (int k0 = 0; k0 < pc && !e; k0 += kcmax) {
-                    const int kc = (pc - k0) < kcmax ? (pc - k0) : kcmax;
-                    e = launch_cvt_l21(c, Ap + pc + (int64_t)k0 * lda, lda, n, kc, split);
-                    if (!e) e = launch_hgemm_minus(c, n, n, kc, A12 + k0, lda, A12 + pc, lda, split);
-                }
-                return e; });
+            rc = ev.timed(st.ms_gemm, S, [&] { return launch_generic_update(c, o, n, n, pc, Ap + pc, lda, A12, lda); });      // :230
             if (rc) break;
             count_gemm(st, o, n, n, pc);
         }
@@ -549,20 +646,16 @@ static int factor_generic(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32
 }
 
 // The plain chain of the panel at k on stream s: pivot kernel, then the interchange of the panel's own columns and the fp64 panel.
+static PanelView panel_at(const FactorArgs &f, int64_t k) {
+    const int64_t pr = f.N - k;
+    return {f.d_A + k * f.lda, f.lda, k, (int)pr, (int)(pr < f.nb ? pr : f.nb), f.c->lists + (k / f.nb), f.d_ipiv + k};
+}
 static int panel_chain(const FactorArgs &f, int64_t k, hipStream_t s) {
-    mpf_ctx *c = f.c;
-    const int pc = (int)((f.N - k) < f.nb ? (f.N - k) : f.nb);
-    const int pr = (int)(f.N - k);
-    if (pr <= 1) return 0;
-    StreamSwap sw(c, s);
-    double *Ak = f.d_A + k * f.lda + k;
-    MovedList *ml = c->lists + (k / f.nb);
-    int e = f.ev.timed(f.st.ms_hpanel, s, [&] {
-        return launch_hgetf2(c, Ak, f.lda, nullptr, 0, pr, pc, (int)k, f.d_ipiv + k, nullptr, 0, ml, 0, pref_window_rows(f.o)); });
-    if (!e) e = f.ev.timed(f.st.ms_dpanel, s, [&] {
-        int e2 = launch_laswp_from_list(c, f.d_A + k * f.lda, f.lda, pc, ml);
-        if (!e2) e2 = launch_dgetf2_npv(c, Ak, f.lda, pr, pc, f.o.fused_panel, (int)k);
-        return e2; });
+    if (f.N - k <= 1) return 0;
+    StreamSwap sw(f.c, s);
+    const PanelView v = panel_at(f, k);
+    int e = panel_pivots(f, v, s, 0);
+    if (!e) e = panel_tail(f, v, s);
     f.st.panels++;
     return e;
 }
@@ -580,20 +673,18 @@ static int panel_chain(const FactorArgs &f, int64_t k, hipStream_t s) {
 // chain runs when the shape has no pieces or there is no third stream, and in the two cases below.
 struct ChainEnd { int rc = 0; hipEvent_t a = nullptr, b = nullptr; };
 static ChainEnd chain_behind(const FactorArgs &f, int64_t nx, hipEvent_t e1) {
-    mpf_ctx *c = f.c;
-    EvPool &ev = f.ev;
-    const int64_t N = f.N, lda = f.lda;
-    const int pc2 = (int)((N - nx) < f.nb ? (N - nx) : f.nb);
+    mpf_ctx *c = f.c; EvPool &ev = f.ev;
+    const PanelView v = panel_at(f, nx);
     hipStream_t P = c->pstream, T = c->tstream;
-    const int np = dgetf2_npv_pieces(c, pc2);
-    const int waiters = (c->tune.gate_wait_value && c->hp_signal) ? 0 : laswp_gated_grid(pc2);   // (a stream that waits holds no CU)
+    const int np = dgetf2_npv_pieces(c, v.pc);
+    const int waiters = (c->tune.gate_wait_value && c->hp_signal) ? 0 : laswp_gated_grid(v.pc);   // (a stream that waits holds no CU)
     const bool piped = c->tune.chain_pipeline && np != 0 && T && P &&
         // fp64 mode: while the update is the longer side (large trailing matrix) the chain hides under it anyway, and the extra
         // launches beside it only cost the update time (measured + 4 ms per factorization): pipeline the chain-bound panels only
-        !(f.o.trailing == MPF_TRAIL_FP64 && (N - nx) > c->tune.chain_pipeline_below) &&
+        !(f.o.trailing == MPF_TRAIL_FP64 && v.pr > c->tune.chain_pipeline_below) &&
         // the gated interchange kernel's workgroups wait for the pivot kernel while sitting on CUs: the panel must fit beside them
         // (else the chain runs unpipelined: nobody waits for a kernel whose workgroups cannot all become resident)
-        hgetf2_fits_beside(c, (int)(N - nx), pc2, waiters);
+        hgetf2_fits_beside(c, v.pr, v.pc, waiters);
     ChainEnd r;
     hipStreamWaitEvent(P, e1, 0);
     if (!piped) {
@@ -603,23 +694,15 @@ static ChainEnd chain_behind(const FactorArgs &f, int64_t nx, hipEvent_t e1) {
         return r;
     }
     hipStreamWaitEvent(T, e1, 0);
-    double *Anx = f.d_A + nx * lda + nx;
     {
         StreamSwap sw(c, P);
-        r.rc = ev.timed(f.st.ms_hpanel, P, [&] {
-            return launch_hgetf2(c, Anx, lda, nullptr, 0, (int)(N - nx), pc2, (int)nx, f.d_ipiv + nx, nullptr, 0, c->lists + (nx / f.nb), waiters, pref_window_rows(f.o)); });
+        r.rc = panel_pivots(f, v, P, waiters);
         r.a = ev.get();
         hipEventRecord(r.a, P);
     }
     if (!r.rc) {
         StreamSwap sw(c, T);
-        r.rc = ev.timed(f.st.ms_dpanel, T, [&] {
-            int e = 0;
-            for (int s = 0; s < np && !e; ++s) {
-                e = launch_laswp_block_gated(c, f.d_A + nx * lda, lda, pc2, (int)nx + 32 * s, 32, f.d_ipiv + nx + 32 * s, N, 32 * (s + 1));
-                if (!e) e = launch_dgetf2_npv_piece(c, Anx, lda, (int)(N - nx), pc2, f.o.fused_panel, (int)nx, s);
-            }
-            return e; });
+        r.rc = ev.timed(f.st.ms_dpanel, T, [&] { return panel_pieces(f, v, np); });
         r.b = ev.get();
         hipEventRecord(r.b, T);
     }
@@ -1270,10 +1353,7 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
     }
     if (overlap) stream_join(ev, S, P);
     const int64_t sbw = (int64_t)sb * nb;
-    const int kst = (int)((sbw + 63) & ~(int64_t)63);                       // row stride of the far U image (elements)
-    const int64_t far_cap = N - (int64_t)(sb + 1) * nb;                     // most far columns any super-panel has
-    const int64_t inner_u_off = (!f64 && far_cap > 0) ? far_cap * kst : 0;  // the inner steps' U image lives behind the far image
-    const int64_t brow_l_off = (int64_t)N * c->h_kmax;                      // block-row L images: in the rows the image buffers hold beyond N
+    const ImageGeom g = image_geom(N, N - (int64_t)(sb + 1) * nb, sb, nb, c->h_kmax, f64);
     auto width = [&](int64_t k) { return (int)((N - k) < nb ? (N - k) : nb); };
     auto side_chain = [&](int64_t kx, hipEvent_t e1, hipEvent_t &e2) -> int { // chain of the panel at kx (N - kx > 1) behind E1, E2 behind all of it
         if (!overlap) return panel_chain(f, kx, S);
@@ -1309,49 +1389,30 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
         const int64_t mrows = N - k - pc;
         int e = ev.timed(st.ms_trsm, Ci, [&] { return launch_dtrsm_llnu(c, pc, ncols, Ap, lda, A12, lda); });
         if (e || mrows <= 0) return e;
-        if (f64) e = ev.timed(st.ms_gemm, Ci, [&] { return launch_dgemm_minus(c, mrows, ncols, pc, Ap + pc, lda, A12, lda, A12 + pc, lda); });
-        else {
-            e = ev.timed(st.ms_cvt, Ci, [&] { return launch_cvt_u12(c, A12, lda, pc, ncols, split, inner_u_off); });
+        if (!f64) {
+            e = ev.timed(st.ms_cvt, Ci, [&] { return launch_inner_u_image(c, o, A12, lda, pc, ncols, g.inner_u_off); });
             if (first && img_ready) hipStreamWaitEvent(Ci, img_ready, 0);
-            if (!e) e = ev.timed(st.ms_gemm, Ci, [&] { return launch_hgemm_images(c, mrows, ncols, pc, A12 + pc, lda, false, split, 0, 0, inner_u_off); });
         }
+        if (!e) e = ev.timed(st.ms_gemm, Ci, [&] { return launch_inner_gemm(c, o, mrows, ncols, pc, Ap + pc, lda, A12, lda, g.inner_u_off); });
         count_gemm(st, o, mrows, ncols, pc);
         return e;
     };
     // ---- far lane: everything right of the inner region ("far" columns [f0, N) of the super-panel [s0, s1)) -----------------------
-    // U block-row, one 256-row block per finished panel p of the super-panel (task T_p, full width: one launch of each kind per
-    // block instead of one per column piece -- a 256-row TRSM costs the same ~90 us for 7000 columns as for 28000):
-    //   interchange of panel p on the far columns; rows of block p lose L[p, < p] U[< p] (the update the one-level schedule
-    //   would have given them panel by panel: fp16 modes through the fp16 MFMA kernel with the mode's operands, fp64 mode
-    //   through the fp64 MFMA GEMM -- same fma chains as the blocked TRSM, identical bits); the block returns to fp64;
-    //   TRSM with the panel's L11; the finished U rows are appended to the U image of the K = s1 - s0 update.
+    // U block-row, one block per finished panel p of the super-panel (task T_p: far_block_row, factor_common.h).
     // Then the update itself: operand image of L[s1.., s0..s1) once, the kernel on the columns that join the next inner region
     // first (they return to fp64: event NI releases the inner lane), then on all the rest in one launch.  U image:
     // Uh[n_far][kst] at the start of the context's U buffer; the inner region's steps keep their small image behind it.
     struct Far { bool on = false; int64_t s0 = 0, s1 = 0, f0 = 0; int done = 0, img = 1; } far;
     std::vector<hipEvent_t> panel_done;   // per panel of the current super-panel: recorded on the inner lane after its eager interchanges
+    // the far job's columns: in the matrix (fp64 mode, fp16 modes in place) or in the fp32 copy; L and the L11 of panel p in the matrix
+    auto far_view = [&](const Far &fj, int p) -> FarView {
+        const int64_t kq = fj.s0 + (int64_t)p * nb;
+        return {d_A + fj.f0 * lda, lda, use32 ? W + fj.f0 : nullptr, ldw, N - fj.f0, d_A + fj.s0 * lda, lda, d_A + kq * lda + kq, lda};
+    };
     auto far_task = [&](int p) -> int {   // T_p of the current far job
-        const int64_t kq = far.s0 + (int64_t)p * nb, f0 = far.f0, ncols = N - f0;
-        if (ncols <= 0) return 0;
+        if (N - far.f0 <= 0) return 0;
         if (lanes) hipStreamWaitEvent(S, panel_done[(size_t)p], 0);
-        int e = ev.timed(st.ms_laswp, S, [&] {
-            return use32 ? launch_laswp_from_list_f32(c, W + f0, ldw, ncols, c->lists + (kq / nb))      // row-major copy: contiguous rows
-                         : launch_laswp_from_list(c, d_A + f0 * lda, lda, ncols, c->lists + (kq / nb)); });
-        if (!e && p > 0) {
-            const int K = p * nb;
-            if (f64) e = ev.timed(st.ms_trsm, S, [&] {
-                return launch_dgemm_minus(c, nb, ncols, K, d_A + far.s0 * lda + kq, lda, d_A + f0 * lda + far.s0, lda, d_A + f0 * lda + kq, lda); }, &st.ms_blockrow);
-            else {
-                e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_l21(c, d_A + far.s0 * lda + kq, lda, nb, K, split, 0, brow_l_off); });
-                if (!e) e = ev.timed(st.ms_trsm, S, [&] {
-                    return use32 ? launch_hgemm_images_rowmajor(c, nb, ncols, K, W + kq * ldw + f0, ldw, split, 0, brow_l_off, 0, 0, kst)
-                                 : launch_hgemm_images(c, nb, ncols, K, d_A + f0 * lda + kq, lda, false, split, 0, brow_l_off, 0, 0, kst); }, &st.ms_blockrow);
-            }
-        }
-        if (!e && use32) e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_f32_f64(c, W + kq * ldw + f0, ldw, d_A + f0 * lda + kq, lda, nb, ncols); });
-        if (!e) e = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu(c, nb, ncols, d_A + kq * lda + kq, lda, d_A + f0 * lda + kq, lda); }, &st.ms_blockrow);
-        if (!e && !f64) e = ev.timed(st.ms_cvt, S, [&] { return launch_cvt_u12(c, d_A + f0 * lda + kq, lda, nb, ncols, split, (int64_t)p * nb, kst); });
-        return e;
+        return far_block_row(f, far_view(far, p), g, far.s0, p);
     };
     auto far_tasks_upto = [&](int ready) -> int { // run the block-row tasks of the panels 0 .. ready - 1 that have not run yet
         int e = 0;
@@ -1359,23 +1420,7 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
         return e;
     };
     // the K = s1 - s0 update of the far job on the columns [col0, col0 + ncols) (block-row and U image complete)
-    auto big_update = [&](const Far &fj, int64_t col0, int64_t ncols) -> int {
-        const int64_t mrows = N - fj.s1;
-        const int K = (int)(fj.s1 - fj.s0);
-        if (ncols <= 0 || mrows <= 0) return 0;
-        int e;
-        if (f64) e = ev.timed(st.ms_gemm, S, [&] { return launch_dgemm_minus(c, mrows, ncols, K, d_A + fj.s0 * lda + fj.s1, lda, d_A + col0 * lda + fj.s0, lda, d_A + col0 * lda + fj.s1, lda); }, &st.ms_gemm_big);
-        else e = ev.timed(st.ms_gemm, S, [&] {
-                const int64_t uo = (col0 - fj.f0) * kst;
-                return use32 ? launch_hgemm_images_rowmajor(c, mrows, ncols, K, W + fj.s1 * ldw + col0, ldw, split, fj.img, 0, uo, 0, kst)
-                             : launch_hgemm_images(c, mrows, ncols, K, d_A + col0 * lda + fj.s1, lda, false, split, fj.img, 0, uo, 0, kst); }, &st.ms_gemm_big);
-        const double cb = f64 ? 16.0 : (use32 ? 8.0 : 16.0), opb = f64 ? 8.0 : (split ? 4.0 : 2.0);
-        count_gemm(st, o, mrows, ncols, K, cb);
-        st.gemm_big_flops += 2.0 * (double)mrows * (double)ncols * K;
-        st.gemm_big_bytes += cb * (double)mrows * (double)ncols + opb * K * (double)(mrows + ncols);
-        st.gemm_big_launches++;
-        return e;
-    };
+    auto big_update = [&](const Far &fj, int64_t col0, int64_t ncols) { return far_big_update(f, far_view(fj, 0), g, fj.s0, fj.s1, col0 - fj.f0, ncols, fj.img); };
     // a column range that joins the next inner region returns to fp64: rows >= r0 (above them: finished U rows in A)
     auto back_to_f64 = [&](int64_t r0, int64_t col0, int64_t ncols) -> int {
         if (!use32 || ncols <= 0) return 0;
@@ -1400,11 +1445,7 @@ static int factor_superpanel(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, in
         far = Far();
         if (e1c < N) {
             far.on = true; far.s0 = c0; far.s1 = c1; far.f0 = e1c; far.img = next_img; next_img = 3 - next_img;
-            if (!f64 && nb % 64 != 0) {   // image blocks of odd width: the padding the kernels read beyond a block must be zero
-                const size_t bytes = (size_t)(N - e1c) * kst * sizeof(unsigned short);
-                MPF_HIP_TRY(c, hipMemsetAsync(c->h_U, 0, bytes, S));
-                if (split) MPF_HIP_TRY(c, hipMemsetAsync(c->h_U + c->h_rows * c->h_kmax, 0, bytes, S));
-            }
+            rc = far_zero_padding(f, N - e1c, g);
         }
         panel_done.assign((size_t)npan, nullptr);
         bool stop = false;
@@ -1495,13 +1536,9 @@ int mpf_factor_setup(mpf_ctx *c, int64_t N, int32_t nb, int32_t npanels, bool li
 
 int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, int32_t *d_ipiv, const mpf_opts *opts) {
     if (!c || !d_A || !d_ipiv) return -1;
-    if (N <= 0 || nb <= 0) return fail(c, -1, "mpf_factor: N and panel width must be positive");
-    if (lda < N) return fail(c, -1, "mpf_factor: lda < N");
-    if (N > INT_MAX / 2) return fail(c, -1, "mpf_factor: N too large");
-    if (nb > 65535) return fail(c, -1, "mpf_factor: panel width > 65535");
     mpf_opts o{};
     if (opts) o = *opts;
-    if (o.trailing < MPF_TRAIL_FP64 || o.trailing > MPF_TRAIL_FP16X3) return fail(c, -1, "mpf_factor: unknown trailing mode");
+    if (factor_check_args(c, "mpf_factor", "lda", N, nb, lda, o)) return -1;
     if (o.pivot_search < 0 || o.pivot_search > 2)
         return fail(c, -1, "mpf_factor: unknown pivot_search (0: fp16 image, 1: fp64 partial pivoting, 2: fp64 tournament pivoting)");
     // fp64 pivot rules (1 partial, 2 tournament pivoting): the generic schedule's loop in every mode; an explicit rule wins over the option
@@ -1512,9 +1549,7 @@ int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, 
     const bool force_generic = o.pivot_path == 1 || safe_pivots(c);
     const bool generic = piv64 || force_generic || !hgetf2_lds_eligible(c, (int)N, (int)(nb < N ? nb : N));
     // super-panels need equal-width column blocks left of every panel (deferred interchanges), i.e. N > sb * nb columns of nb
-    int want_sb = o.trailing != MPF_TRAIL_FP64 ? c->tune.superpanel_fp16 : c->tune.superpanel_fp64;
-    if (o.trailing != MPF_TRAIL_FP64 && want_sb == 0) want_sb = (o.trailing == MPF_TRAIL_FP16 && N >= 24576) ? 6 : 4;   // (MpfTuning::superpanel_fp16)
-    if (o.superpanel > 0) want_sb = o.superpanel > 8 ? 8 : o.superpanel;
+    const int want_sb = wanted_superpanel(c, o, N);
     const int sb = (!generic && !o.sync_timing && (int64_t)want_sb * nb < N) ? want_sb : 1;
     if (o.trailing != MPF_TRAIL_FP64) {
         const int64_t kimg = (int64_t)sb * nb < 8 * HP_MAXCOLS ? (int64_t)sb * nb : 8 * HP_MAXCOLS; // the generic schedule cuts K to the images
@@ -1547,30 +1582,15 @@ int mpf_factor_dev(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, 
     else if (sb > 1) rc = factor_superpanel(c, d_A, lda, N, nb, d_ipiv, o, st, sb, lookahead);
     else if (use_rm) rc = factor_lookahead_rm(c, d_A, lda, N, nb, d_ipiv, o, st, use_pairs);
     else if (lookahead) rc = factor_lookahead(c, d_A, lda, N, nb, d_ipiv, o, st);
-    else {
-        mpf_opts o2 = o;
-        rc = factor_sync_timed(c, d_A, lda, N, nb, d_ipiv, o2, st);
-    }
-    hipEventRecord(c->ev1, c->stream);
-    hipError_t se = sink_stream_wait(c, c->stream);
-    if (rc) return rc;
-    if (se != hipSuccess) return fail(c, -2, std::string("factorization failed: ") + hipGetErrorString(se));
-    float ms = 0;
-    hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    st.ms_total = ms;
-    if (o.trailing == MPF_TRAIL_FP64 && N >= 8192 && ms > 0)   // what mpf_gesv prices an fp64 refactorization with
-        c->fp64_rate_tflops = 2.0 / 3.0 * (double)N * (double)N * (double)N / (ms * 1e-3) / 1e12;
-    int info = 0, flags0 = 0;
-    MPF_HIP_TRY(c, hipMemcpy(&info, &c->ws->info, sizeof(int), hipMemcpyDeviceToHost));
-    MPF_HIP_TRY(c, hipMemcpy(&flags0, &c->ws->hp_timeouts, sizeof(int), hipMemcpyDeviceToHost));
-    st.info = info == INT_MAX ? 0 : info;
-    st.hpanel_timeouts = flags0;
-    const double h2d = c->stats.ms_h2d, d2h = c->stats.ms_d2h;
-    c->stats = st;
+    else rc = factor_sync_timed(c, d_A, lda, N, nb, d_ipiv, o, st);
+    const double h2d = c->stats.ms_h2d, d2h = c->stats.ms_d2h;   // (mpf_factor_host's transfers: they outlive the statistics of this call)
+    rc = factor_report(c, st, rc, [&] { return sink_stream_wait(c, c->stream); }, "factorization",
+                       "fp16 pivot kernel: inter-workgroup hand-off timed out (its workgroups were not all resident: GPU "
+                       "shared with another process?).  d_A and ipiv are invalid.  Use mpf_opts.pivot_path = 1 or MPF_SAFE_PIVOTS=1");
     c->stats.ms_h2d = h2d; c->stats.ms_d2h = d2h;
-    if (flags0) return fail(c, -4, "fp16 pivot kernel: inter-workgroup hand-off timed out (its workgroups were not all resident: GPU "
-                                   "shared with another process?).  d_A and ipiv are invalid.  Use mpf_opts.pivot_path = 1 or MPF_SAFE_PIVOTS=1");
-    return st.info;
+    if (o.trailing == MPF_TRAIL_FP64 && N >= 8192 && st.ms_total > 0)   // what mpf_gesv prices an fp64 refactorization with
+        c->fp64_rate_tflops = 2.0 / 3.0 * (double)N * (double)N * (double)N / (st.ms_total * 1e-3) / 1e12;
+    return rc;
 }
 
 // Device copies of the host entry point's buffers live in the context and only ever grow (round 4): the reference allocates and

@@ -90,6 +90,29 @@ def test_cxx_dist_loop_world1_all_modes(ctx, oracle, mpf):
     c1.close(); c1r.close()
 
 
+def test_superpanel_gates_of_the_two_drivers_stay_apart(ctx, oracle, mpf):
+    """Both drivers take the wanted super-panel width from one rule (automatic: 4 at these sizes) and gate it differently on purpose:
+    mpf_factor_dev needs 4 nb < N, the distributed loop 5 nb < N (its inner region holds the look-ahead block).  nb = 128 at the two
+    sides of both bounds; the distributed run equals mpf_factor_dev at the width it reports, bit for bit."""
+    one = mpf.MpfDist(rank=0, world=1)
+    c1 = mpf.MPFContext(0, options={"dist_world1_loop": 1})
+    nb = 128
+    for n, sb_dev, sb_dist in ((512, 1, 1), (513, 4, 1), (640, 4, 1), (641, 4, 4)):
+        dA = ctx.from_numpy_f(oracle.matgen_skip(n, skip=3))
+        for mode in (mpf.TRAIL_FP16, mpf.TRAIL_FP16X3):
+            V = dA.clone()
+            ctx.factor(V, nb, trailing=mode, superpanel=0)
+            assert ctx.stats().superpanel == sb_dev, (n, mode)
+            W = dA.clone()
+            p1, _ = c1.factor_dist(W, n, nb, one, trailing=mode, superpanel=0)
+            assert c1.stats().superpanel == sb_dist, (n, mode)
+            V = dA.clone()
+            p2, _ = ctx.factor(V, nb, trailing=mode, superpanel=sb_dist)
+            assert ctx.stats().superpanel == sb_dist
+            assert torch.equal(p1, p2) and torch.equal(W, V), (n, mode)
+    c1.close()
+
+
 def test_cxx_dist_loop_wide_panels_world1(ctx, oracle, mpf):
     """Panels wider than 256 columns in the distributed loop (generic pivot kernels, the reference's sequential interchange of all
     local columns, one stream): fp64 bit-exact against the oracle, the fp16 modes equal mpf_factor_dev's generic schedule."""
