@@ -679,6 +679,43 @@ int mpf_getri(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, const int32_t *d_i
 int mpf_getdet(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, const int32_t *d_ipiv, int64_t N,
                const double *d_r, const double *d_c, double *mant, int64_t *expo /* host */);
 
+/* ---- LU of many small matrices (build extension; LAPACK dgetrf / dgetrs per matrix of a strided batch) ---------------------------------
+ * Every other entry point works on ONE matrix and is tuned for N >= 4096; these two take `batch` matrices of one size n <= 128 in one
+ * launch (csrc/batched.hip).  fp64 only, LAPACK partial pivoting: the fp16-image pivot rule and the fp16 trailing modes have no meaning
+ * at these sizes.  No driver uses them; there is no batched inverse, determinant or refinement.
+ *
+ * Layout: A[b] = d_A + b * strideA, n x n column-major, lda >= n, strideA >= lda * n (or batch == 1);
+ * ipiv[b] = d_ipiv + b * strideP, strideP >= n (or batch == 1), 1-based as LAPACK; d_info: batch int32 on the device, optional.
+ *
+ * Factorization.  For every b, A[b] and ipiv[b][0 .. n-1] on return equal, bit for bit, what
+ * mpf_dgetf2_piv(ctx, A[b], lda, n, n, fused, 0, ipiv[b], ...) leaves:
+ *   idamax with a strict >, so the first maximum wins; a NaN never beats a number; a column whose remaining part is all zero or all
+ *   NaN keeps p = j; the multiplier is a_ij / a_jj (IEEE division); each element is then updated once per k in ascending order, as a
+ *   separate product and difference (fused = 0) or as one FMA (fused = 1; contract C3); all n pivot entries are written, so the last
+ *   one is n; a zero pivot is divided by, as there (Inf / NaN follow); d_info[b] = the first zero pivot, 1-based, or 0.
+ * Matrix b's bits do not depend on batch, on b's position, on lda, strideA or strideP, or on which kernel form took it (n <= 32: 8, 16
+ * or 32 lanes of a wave per matrix, the matrix in registers; above: one workgroup per matrix, the matrix in LDS).  Rows n .. lda-1 and the bytes between
+ * matrices are not touched.  Every launch is an ordinary launch: no kernel waits for another workgroup, no bounded spin, no
+ * co-residency requirement.
+ * Returns 0, or < 0 with a message: -1 for n > 128 (use mpf_factor_dev), negative sizes, lda < n, strides too small, NULL d_A or
+ * d_ipiv.  n == 0 or batch == 0: returns 0, no work.  Per-matrix singularity is reported through d_info only.  Asynchronous on the
+ * context's stream. */
+int mpf_getrf_batched(mpf_ctx *ctx, double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                      int32_t *d_ipiv, int64_t strideP, int32_t *d_info, int32_t fused);
+/* B[b] = d_B + b * strideB, n x nrhs column-major, ldb >= n, strideB >= ldb * nrhs (or batch == 1):
+ * B[b] := A[b]^-1 B[b] (trans = 0) or A[b]^-T B[b] (trans = 1), in place, with the factors and pivots mpf_getrf_batched leaves.
+ * LAPACK dgetrs per matrix with ONE fixed order per element, always unfused (the product is rounded, then the difference):
+ *   trans = 0: for j = 0 .. n-1 rows j and ipiv[j] - 1 of B change places; for i ascending b_i <- b_i - l_ij b_j, j = 0 .. i-1
+ *              ascending; for i descending b_i <- b_i - u_ij b_j, j = n-1 down to i+1, then b_i <- b_i / u_ii.
+ *   trans = 1: with U^T, for i ascending b_i <- b_i - u_ji b_j, j ascending, then b_i <- b_i / u_ii; with L^T, for i descending
+ *              b_i <- b_i - l_ji b_j, j = n-1 down to i+1; then the interchanges in reverse order, j = n-1 .. 0.
+ * Columns do not read each other, and matrix b's result depends on nothing but its own LU, ipiv and B (tests/batched_model.py restates
+ * the chains).  No singularity check, as in dgetrs.  Rows n .. ldb-1 of B are not touched.
+ * Returns 0, or < 0 with a message (n > 128, negative sizes, trans not 0 or 1, leading dimensions < n, strides too small, NULL
+ * pointers).  n == 0, batch == 0 or nrhs == 0: returns 0, no work.  Asynchronous on the context's stream. */
+int mpf_getrs_batched(mpf_ctx *ctx, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                      const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB);
+
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block
  * b / world; d_Aloc is the rank's N x (local columns) column-major matrix (ldloc >= N), d_ipiv the full pivot vector (N int32,

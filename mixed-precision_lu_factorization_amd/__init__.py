@@ -37,6 +37,7 @@ C_ABI_SYMBOLS = [
     "mpf_residual_x", "mpf_gerfsx",
     "mpf_gerpvgrw", "mpf_gerfsx_scaled", "mpf_gesvxx_block",
     "mpf_getri", "mpf_getdet",
+    "mpf_getrf_batched", "mpf_getrs_batched",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -204,6 +205,8 @@ def load_library(probe=False):
                                    C.POINTER(MpfIrStats), C.POINTER(MpfGerfsxStats)]
     L.mpf_getri.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64]
     L.mpf_getdet.argtypes = [vp, vp, i64, vp, i64, vp, vp, C.POINTER(dbl), C.POINTER(i64)]
+    L.mpf_getrf_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, i32]
+    L.mpf_getrs_batched.argtypes = [vp, i32, vp, i64, i64, i32, i64, vp, i64, i32, vp, i64, i64]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -346,6 +349,11 @@ class MPFContext:
     def colmajor(self, rows, cols, dtype=None):
         t = self.torch
         return t.empty((cols, rows), dtype=dtype or t.float64, device=self.device).t()
+
+    def colmajor_batch(self, batch, rows, cols, dtype=None):
+        """A tensor of logical shape (batch, rows, cols) whose matrices are column-major and packed: strides (rows * cols, 1, rows)."""
+        t = self.torch
+        return t.empty((batch, cols, rows), dtype=dtype or t.float64, device=self.device).transpose(1, 2)
 
     def from_numpy_f(self, a):
         """numpy (rows, cols) array -> column-major device tensor of the same logical shape."""
@@ -1011,3 +1019,83 @@ class MPFContext:
         if info or info2:
             raise MPFError(f"inv: the matrix is singular (zero pivot {info or info2})")
         return X
+
+    # ---- LU of many small matrices (include/mpf_c.h: mpf_getrf_batched, mpf_getrs_batched) ----------------------------------------------
+    @staticmethod
+    def _batch_layout(M):
+        """(ld, stride) of a (batch, rows, cols) tensor whose matrices are column-major as they stand (stride 1 along the rows,
+        ld >= rows, matrices that do not overlap), or None: such a tensor has to be copied."""
+        b, r, c = M.shape
+        s0, s1, s2 = M.stride()
+        if r > 1 and s1 != 1:
+            return None
+        ld = s2 if c > 1 else max(r, 1)
+        if ld < max(r, 1) or (b > 1 and s0 < ld * c):
+            return None
+        return ld, (s0 if b > 1 else ld * c)
+
+    def _batch_arg(self, M, what, overwrite, copy=True):
+        """(tensor, ld, stride) the library takes: M itself when overwrite (an error unless its matrices are column-major), else a
+        packed column-major copy; copy=False: M itself when its layout allows (read-only arguments)."""
+        t = self.torch
+        assert M.dim() == 3 and M.dtype == t.float64 and M.is_cuda, f"{what}: a (batch, rows, cols) float64 device tensor"
+        lay = self._batch_layout(M)
+        if overwrite and lay is None:
+            raise MPFError(f"{what}: overwrite=True needs column-major matrices (MPFContext.colmajor_batch); this tensor would be copied")
+        if not overwrite and (copy or lay is None):
+            W = self.colmajor_batch(*M.shape)
+            W.copy_(M)
+            M, lay = W, self._batch_layout(W)
+        return (M,) + lay
+
+    def getrf_batched(self, A, fused=False, overwrite=False, ipiv=None, info=None):
+        """mpf_getrf_batched: LAPACK dgetrf (fp64 partial pivoting, mpf_dgetf2_piv's pivots and bits) of every matrix of the
+        (batch, n, n) tensor A, n <= 128.  Returns (LU, ipiv, info): LU a column-major batch (A itself with overwrite=True, which
+        needs A's matrices column-major -- any other layout, torch's row-major default included, is copied), ipiv int32 (batch, n),
+        1-based, info int32 (batch,) on the device: the first zero pivot of each matrix or 0.  ipiv / info: tensors to receive them
+        (ipiv rows may be padded: stride(1) == 1, stride(0) >= n)."""
+        self._bind()
+        t = self.torch
+        assert A.dim() == 3 and A.shape[1] == A.shape[2], "A: (batch, n, n)"
+        batch, n = A.shape[0], A.shape[1]
+        LU, lda, stride = self._batch_arg(A, "getrf_batched", overwrite)
+        if ipiv is None:
+            ipiv = t.zeros((batch, n), dtype=t.int32, device=self.device)
+        if info is None:
+            info = t.zeros(batch, dtype=t.int32, device=self.device)
+        assert ipiv.dtype == t.int32 and ipiv.is_cuda and ipiv.shape == (batch, n) and (n <= 1 or ipiv.stride(1) == 1)
+        assert info.dtype == t.int32 and info.is_cuda and info.shape == (batch,) and info.is_contiguous()
+        sp = ipiv.stride(0) if batch > 1 else max(n, 1)
+        rc = self.L.mpf_getrf_batched(self.h, _ptr(LU), lda, stride, n, batch, _ptr(ipiv), sp, _ptr(info), int(bool(fused)))
+        self._check(rc, "mpf_getrf_batched")
+        return LU, ipiv, info
+
+    def getrs_batched(self, LU, ipiv, B, trans=False, overwrite=False):
+        """mpf_getrs_batched: X[b] = A[b]^-1 B[b] (or A[b]^-T B[b]) with the factors of getrf_batched; B is (batch, n, nrhs), or
+        (batch, n) for one right-hand side each.  Returns a new column-major X and leaves B untouched, unless overwrite=True: then B
+        itself (column-major matrices) is solved in place and returned."""
+        self._bind()
+        t = self.torch
+        if B.dim() == 2:
+            return self.getrs_batched(LU, ipiv, B.unsqueeze(2), trans, overwrite).squeeze(2)
+        assert LU.dim() == 3 and LU.shape[1] == LU.shape[2] and B.dim() == 3 and B.shape[:2] == LU.shape[:2], "LU: (batch, n, n), B: (batch, n, nrhs)"
+        batch, n, nrhs = B.shape
+        LUm, ldlu, slu = self._batch_arg(LU, "getrs_batched", False, copy=False)
+        assert ipiv.dtype == t.int32 and ipiv.is_cuda and ipiv.shape == (batch, n)
+        if n > 1 and ipiv.stride(1) != 1:
+            ipiv = ipiv.contiguous()
+        sp = ipiv.stride(0) if batch > 1 else max(n, 1)
+        X, ldb, sb = self._batch_arg(B, "getrs_batched", overwrite)
+        rc = self.L.mpf_getrs_batched(self.h, int(bool(trans)), _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, nrhs, _ptr(X), ldb, sb)
+        self._check(rc, "mpf_getrs_batched")
+        return X
+
+    def solve_batched(self, A, B, trans=False):
+        """X[b] = A[b]^-1 B[b] (or A[b]^-T B[b]) for a (batch, n, n) tensor A, n <= 128: getrf_batched on a copy, then getrs_batched.
+        Raises MPFError naming the first singular matrix."""
+        LU, ipiv, info = self.getrf_batched(A)
+        bad = self.torch.nonzero(info)
+        if bad.numel():
+            b = int(bad[0])
+            raise MPFError(f"solve_batched: matrix {b} of the batch is singular (zero pivot {int(info[b])})")
+        return self.getrs_batched(LU, ipiv, B, trans=trans)

@@ -272,7 +272,7 @@ struct mpf_ctx {
         }                                                                             \
     } while (0)
 
-enum { ATTR_HP = 1, ATTR_DGEMM = 2, ATTR_HGEMM = 4, ATTR_HGEMM256 = 8, ATTR_HGEMM_PP = 16, ATTR_HGEMM16_BIG32 = 32, ATTR_HGEMM16_BIG64 = 64 };
+enum { ATTR_HP = 1, ATTR_DGEMM = 2, ATTR_HGEMM = 4, ATTR_HGEMM256 = 8, ATTR_HGEMM_PP = 16, ATTR_HGEMM16_BIG32 = 32, ATTR_HGEMM16_BIG64 = 64, ATTR_BATCHED = 128 };
 inline bool safe_pivots(const mpf_ctx *c) { return c->tune.safe_pivots != 0; }
 
 // ---- launchers implemented in the .hip files (all asynchronous on `s`) -----------------------
@@ -504,6 +504,15 @@ int launch_getri_tri(mpf_ctx *c, bool right, const double *G, double *W, int64_t
 int launch_getri_permute(mpf_ctx *c, double *W, int64_t ld, int64_t n, const int *src, const double *r, const double *cs, double *T);
 int launch_getdet(mpf_ctx *c, const double *LU, int64_t ld, const int *ipiv, int64_t n, const double *r, const double *cs, double *part,
                   double *out);
+// LU of many small matrices (batched.hip; argument checks and chunks in mpf_batched.cpp): one launch each on at most BT_MAX_LAUNCH
+// matrices of 1 <= n <= 128.  launch_getrf_batched: mpf_dgetf2_piv's pivots and bits per matrix (n <= 32: 8, 16 or 32 lanes per matrix from
+// registers; above: a workgroup per matrix from LDS), info[b] = first zero pivot or 0 when info is not null.  launch_getrs_batched:
+// dgetrs per matrix, in place on B, always unfused
+constexpr int64_t BT_MAX_LAUNCH = 1 << 22;
+int launch_getrf_batched(mpf_ctx *c, double *A, int64_t lda, int64_t strideA, int n, int64_t batch, int *ipiv, int64_t strideP, int *info,
+                         int fused);
+int launch_getrs_batched(mpf_ctx *c, int trans, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv,
+                         int64_t strideP, int nrhs, double *B, int64_t ldb, int64_t strideB);
 // mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
 int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 
