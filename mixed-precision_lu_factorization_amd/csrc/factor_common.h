@@ -1,10 +1,12 @@
-// What the factor schedules share (mpf_host.cpp: the single-GPU driver, mpf_dist.cpp: the multi-rank loop, which runs the same steps on
-// views of its block-cyclic storage): the argument checks, the wanted super-panel width, the bodies of a panel chain, the updates of
-// the generic schedule and of an inner step, the far lane's steps and the report that ends a call.  Host only; defined in mpf_host.cpp
-// unless inline.  The steps issue launches on the stream they are given (c->stream where none is): which stream waits for which
-// event, and which schedule runs at a shape, stays with the callers.
+// What the factor schedules share (mpf_factor.cpp and factor_rm.cpp: the single-GPU driver, mpf_dist.cpp: the multi-rank loop, which
+// runs the same steps on views of its block-cyclic storage): the argument checks, the wanted super-panel width, the bodies of a panel
+// chain, the chain of the next panel and the end of a look-ahead schedule, the updates of the generic schedule and of an inner step,
+// the far lane's steps, the steps on the fp64 row-major copy and the report that ends a call.  Host only; defined in mpf_factor.cpp
+// (the row-major steps: factor_rm.cpp) unless inline.  The steps issue launches on the stream they are given (c->stream where none
+// is): which stream waits for which event, and which schedule runs at a shape, stays with the callers.
 #pragma once
 #include "mpf_internal.h"
+#include <initializer_list>
 
 // what every schedule of one factorization works on (the entry point's arguments, the event pool, the statistics)
 struct FactorArgs {
@@ -49,6 +51,13 @@ int panel_tail(const FactorArgs &f, const PanelView &v, hipStream_t s);
 // (c) the pipelined tail in np pieces of 32 columns (launches only): gated interchange of sub-panel q's pivots, piece q of the fp64
 // panel, then after_piece(q)
 int panel_pieces(const FactorArgs &f, const PanelView &v, int np, const std::function<int(int)> &after_piece = nullptr);
+// single-GPU schedules (mpf_factor.cpp has the full story): the plain chain (a) + (b) of the matrix' panel at k on stream s; the chain of the
+// NEXT panel (at nx) on the side streams behind e1, plain or pipelined (`b` is set), with the events that mark its end; the end of a
+// look-ahead schedule -- the sink's last block rows or the deferred left-hand interchanges, then the host waits for the schedule's streams
+int panel_chain(const FactorArgs &f, int64_t k, hipStream_t s);
+struct ChainEnd { int rc = 0; hipEvent_t a = nullptr, b = nullptr; };
+ChainEnd chain_behind(const FactorArgs &f, int64_t nx, hipEvent_t e1);
+int factor_epilogue(const FactorArgs &f, int rc, bool sink, int sb, bool side_streams);
 
 // ---- updates (launches only: the callers time and count them) ------------------------------------------------------------------------
 // generic schedule, C = U12 + pc rows: one fp64 GEMM, or in the fp16 modes K cut to what the operand images hold
@@ -82,3 +91,28 @@ int far_zero_padding(const FactorArgs &f, int64_t ncols, const ImageGeom &g);
 int far_block_row(const FactorArgs &f, const FarView &v, const ImageGeom &g, int64_t s0, int p);
 // the K = s1 - s0 update of the view's columns [col, col + ncols) below row s1 from L image `img`, with its statistics
 int far_big_update(const FactorArgs &f, const FarView &v, const ImageGeom &g, int64_t s0, int64_t s1, int64_t col, int64_t ncols, int img);
+
+// ---- fp64 row-major working copy (factor_rm.cpp; the multi-rank loop: a rank's local columns, ldr = their count) ----------------------
+// Element (i, j) -- j a column of THIS storage -- lives at A[j * lda + i] and at R[i * ldr + j].  The two accessors are the only address
+// arithmetic on R and on the U rows of A.
+struct RmView {
+    double *A; int64_t lda;
+    double *R; int64_t ldr;
+    double *a(int64_t i, int64_t j) const { return A + j * lda + i; }
+    double *r(int64_t i, int64_t j) const { return R + i * ldr + j; }
+};
+// The steps of one panel on the columns [c, c + w) of the copy: each issues its launches on c->stream (the caller's StreamSwap scope) as ONE
+// timed region booked on stream s.  rm_swap: interchange of contiguous row segments, list after list, under ms_laswp; scratch_off: where in
+// the interchange scratch these columns' moved rows go (ranges in flight on different streams must not share it).  rm_solve_u: U[k : k + pc)
+// = L11^-1 R[k : k + pc) through strides, under ms_trsm (L11: in the matrix, or in the panel message).  rm_update: R[r0 : r0 + rows) -=
+// Limg U[ku : ku + K), the MFMA GEMM on the transposed problem under ms_gemm, and its count_gemm (Limg: row-major L image of the rows r0..).
+// rm_home: the rows [row, row + rows) go home to the column-major matrix, under ms_cvt (split > 0: two launches, `split` rows first).
+// rm_l_image: the other direction, a column-major block (of L21, of the matrix) into a row-major image (an L image, the copy itself).
+int rm_swap(const FactorArgs &f, const RmView &v, hipStream_t s, int64_t c, int64_t w, std::initializer_list<const MovedList *> lists, int64_t scratch_off);
+int rm_solve_u(const FactorArgs &f, const RmView &v, hipStream_t s, const double *L11, int64_t ld11, int64_t k, int pc, int64_t c, int64_t w);
+int rm_update(const FactorArgs &f, const RmView &v, hipStream_t s, int64_t ku, int K, int64_t r0, int64_t rows, int64_t c, int64_t w, const double *Limg, int64_t ldimg);
+int rm_home(const FactorArgs &f, const RmView &v, hipStream_t s, int64_t row, int64_t rows, int64_t c, int64_t w, int64_t split = 0);
+int rm_l_image(const FactorArgs &f, hipStream_t s, const double *src, int64_t lds, int64_t rows, int64_t cols, double *img, int64_t ldimg);
+bool pivots_fit_beside_update(const mpf_ctx *c, int64_t rows);   // the pivot kernel of a panel of `rows` rows fits beside a running update
+// the schedule itself (mpf_factor_dev's fp64 default from fp64_rowmajor_min_n on)
+int factor_lookahead_rm(mpf_ctx *c, double *d_A, int64_t lda, int64_t N, int32_t nb, int32_t *d_ipiv, const mpf_opts &o, mpf_stats &st, bool pairs);

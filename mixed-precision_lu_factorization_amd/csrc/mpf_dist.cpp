@@ -8,7 +8,7 @@
 // every rank then interchanges / TRSMs / GEMMs the columns it owns.  Per element the arithmetic is that of the 1-GPU path
 // (the partition only changes WHO computes a column block): IPIV and LU are bit-identical to mpf_factor_dev.
 //
-// Schedule = the look-ahead schedule of mpf_host.cpp with column indices translated: the owner of panel b+1 updates that
+// Schedule = the look-ahead schedule of mpf_factor.cpp with column indices translated: the owner of panel b+1 updates that
 // block first ("strip"), runs its chain and posts the broadcast on the side stream P while every rank finishes update b on
 // the main stream S.  Columns LEFT of a panel are interchanged once at the end (composite maps, laswp.hip).
 //
@@ -143,9 +143,10 @@ struct DistFactor {
     bool two = false, rm = false;
     int sb = 1, far_img = 1;          // panels per super-panel (1: one-level schedule); which L image the next K = sb * nb update reads
     bool inst_ok = false, fused_form_all = false; long long inst_min_bytes = 0, lds_rows_max = 0;   // agreed by the ranks (agree)
-    double *Rl = nullptr, *SPL = nullptr;                  // row-major copy of the local columns (fp64 mode); the super-panel's panels, ld N
+    RmView rv{};                                           // the local columns and their row-major copy (fp64 mode, rm)
+    double *SPL = nullptr;                                 // the super-panel's panels, ld N
     float *W = nullptr;                                    // fp32 row-major working copy of the local far columns
-    int64_t ldr = 1, ldw = 1; ImageGeom g{};
+    int64_t ldw = 1; ImageGeom g{};
     bool image_ready = false;         // the current panel's L21 image (fp16 modes) / row-major L21 (rm) is there
     std::vector<hipEvent_t> ev_piece;
 
@@ -208,7 +209,7 @@ struct DistFactor {
         inst_ok = agreed[0] != 0; inst_min_bytes = -agreed[2]; fused_form_all = agreed[3] != 0; lds_rows_max = agreed[4];
         return 0;
     }
-    // Two-level schedule of the fp16 modes (factor_superpanel in mpf_host.cpp, carried over to the block-cyclic layout): sb panels
+    // Two-level schedule of the fp16 modes (factor_superpanel in mpf_factor.cpp, carried over to the block-cyclic layout): sb panels
     // form a super-panel; a panel updates only the INNER blocks (the super-panel's own and the next super-panel's first one) of
     // this rank, panel by panel, in fp64; this rank's FAR columns live in an fp32 row-major working copy and get one update with
     // K = sb * nb per super-panel, after the U block-row tasks.  What the single-GPU schedule reads from the matrix left of the
@@ -242,9 +243,9 @@ struct DistFactor {
         // interchange moves contiguous row segments instead of one 64-byte sector per moved row and column; the update is the same MFMA
         // kernel on the transposed problem (c = fma(-u, l, c), kk ascending: the same bits).  Rank-local choice: results do not depend on it.
         rm = f64 && lcols > 0 && c->tune.fp64_rowmajor && N >= c->tune.fp64_rowmajor_min_n && N > nb && mpf_ensure_rowmajor_copy(c, N, lcols, nb) == 0;
-        Rl = rm ? c->r64.get() : nullptr;
         W = c->dist_w32; SPL = c->dist_spl;
-        ldr = ldw = lcols > 0 ? lcols : 1;
+        ldw = lcols > 0 ? lcols : 1;
+        rv = {A, lda, rm ? c->r64.get() : nullptr, ldw};
         st.superpanel = sb;
         g = image_geom(N, sb > 1 ? lcols - L.first_local_col_after(sb) : 0, sb, nb, c->h_kmax, f64);
         rc = begin(true);
@@ -284,7 +285,7 @@ struct DistFactor {
         hipEvent_t before_pivots = ev.get();
         hipEventRecord(before_pivots, s);
         const bool lds = !generic && hgetf2_lds_eligible(c, v.pr, v.pc);
-        // the fp64 panel follows the pivot kernel 32 columns behind on the helper stream (see chain_behind in mpf_host.cpp) -- where
+        // the fp64 panel follows the pivot kernel 32 columns behind on the helper stream (see chain_behind in mpf_factor.cpp) -- where
         // the panel's workgroups fit beside the gated interchange kernel's, which wait for it while sitting on CUs
         const int waiters = (c->tune.gate_wait_value && c->hp_signal) ? 0 : laswp_gated_grid(v.pc);
         const bool will_pipe = c->tune.chain_pipeline != 0 && c->tstream != nullptr && lds && hgetf2_fits_beside(c, v.pr, v.pc, waiters);
@@ -362,15 +363,14 @@ struct DistFactor {
         if (rm) {
             // interchange of contiguous row segments, TRSM through strides, L21 row-major once per panel, the update on the transposed
             // problem, then the finished U rows of these columns go home to the column-major matrix
-            double *LT = c->rm_lt, *Rk = Rl + k * ldr + c0;
-            int e = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_from_list_rm64(c, Rl + c0, ldr, nc, c->lists + b); });
-            if (!e) e = ev.timed(st.ms_trsm, S, [&] { return launch_dtrsm_llnu_strided(c, pc, nc, Pb, ldp, Rk, ldr, 1); });
+            double *LT = c->rm_lt;
+            int e = rm_swap(f, rv, S, c0, nc, {c->lists + b}, 0);
+            if (!e) e = rm_solve_u(f, rv, S, Pb, ldp, k, pc, c0, nc);
             if (!e && m > 0) {
-                if (!image_ready) { e = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, (double *)Pb + pc, ldp, LT, pc, m, pc, true); }); image_ready = true; }
-                if (!e) e = ev.timed(st.ms_gemm, S, [&] { return launch_dgemm_minus(c, nc, m, pc, Rk, ldr, LT, pc, Rk + pc * ldr, ldr); });
-                count_gemm(st, o, m, nc, pc);
+                if (!image_ready) { e = rm_l_image(f, S, Pb + pc, ldp, m, pc, LT, pc); image_ready = true; }
+                if (!e) e = rm_update(f, rv, S, k, pc, k + pc, m, c0, nc, LT, pc);
             }
-            if (!e) e = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, A + c0 * lda + k, lda, Rk, ldr, pc, nc, false); });
+            if (!e) e = rm_home(f, rv, S, k, pc, c0, nc);
             return e;
         }
         int e = ev.timed(st.ms_laswp, S, [&] { return launch_laswp_from_list(c, A + c0 * lda, lda, nc, c->lists + b); });
@@ -417,7 +417,7 @@ struct DistFactor {
         far_img = 3 - far_img;
         return e;
     }
-    // Schedule = the look-ahead schedule of mpf_host.cpp with column indices translated (top of this file)
+    // Schedule = the look-ahead schedule of mpf_factor.cpp with column indices translated (top of this file)
     int run() {
         int rc = 0;
         if (sb > 1 && far0(0) < lcols)   // this rank's far columns of the first super-panel go into the working copy
@@ -427,7 +427,7 @@ struct DistFactor {
             if (!rc) rc = exchange(0, S, 0);
         }
         if (!rc && rm)   // everything this rank owns goes into the row-major copy (block 0, if it is here, is finished: its copy is never read)
-            rc = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, A, lda, Rl, ldr, N, lcols, true); });
+            rc = rm_l_image(f, S, rv.a(0, 0), lda, N, lcols, rv.r(0, 0), rv.ldr);
         for (int b = 0; L.live(b) && rc == 0; ++b) {
             const int64_t k = (int64_t)b * nb;
             const int pc = L.width(b);
@@ -439,8 +439,7 @@ struct DistFactor {
             if (trailing && own_next) { // my block of panel b+1 first, then its chain on the side stream
                 rc = update(b, L.lcol(nxt), L.width(nxt));
                 if (!rc && rm)   // the next panel's columns return to the column-major matrix before its chain (rows k + pc ..; its U rows went with the update)
-                    rc = ev.timed(st.ms_cvt, S, [&] { return launch_transpose64(c, A + L.lcol(nxt) * lda + k + pc, lda, Rl + (k + pc) * ldr + L.lcol(nxt), ldr,
-                                                                                N - k - pc, L.width(nxt), false); });
+                    rc = rm_home(f, rv, S, k + pc, N - k - pc, L.lcol(nxt), L.width(nxt));
                 if (rc) break;
                 rest0 = L.lcol(nxt) + L.width(nxt);
             }
@@ -478,7 +477,7 @@ struct DistFactor {
     // Panels wider than 256 columns (the LDS pivot kernel and the moved-row lists stop there): the reference's own order, panel by
     // panel on one stream, with the generic (global-memory) pivot kernels and the sequential interchange of ALL local columns
     // (MPF.cu:145-162) -- no look-ahead, no deferred left-hand side.  Message = the factored panel (leading dimension = its rows)
-    // followed by its pivots.  Per element the operations are those of factor_generic (mpf_host.cpp): identical bits.
+    // followed by its pivots.  Per element the operations are those of factor_generic (mpf_factor.cpp): identical bits.
     int run_wide() {
         int rc = f64 ? 0 : mpf_ensure_h_images(c, N, nb < 8 * HP_MAXCOLS ? nb : 8 * HP_MAXCOLS, false);
         for (int b = 0; L.live(b) && rc == 0; ++b) {

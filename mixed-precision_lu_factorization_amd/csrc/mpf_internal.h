@@ -271,6 +271,13 @@ struct mpf_ctx {
             return -2;                                                                \
         }                                                                             \
     } while (0)
+// a call's error text and code: into the context, or -- a call without one -- into the calling thread's slot (mpf_host.cpp) that
+// mpf_last_error(nullptr) reads
+std::string &noctx_error();
+inline int fail(mpf_ctx *c, int code, const std::string &msg) {
+    (c ? c->err : noctx_error()) = msg;
+    return code;
+}
 
 enum { ATTR_HP = 1, ATTR_DGEMM = 2, ATTR_HGEMM = 4, ATTR_HGEMM256 = 8, ATTR_HGEMM_PP = 16, ATTR_HGEMM16_BIG32 = 32, ATTR_HGEMM16_BIG64 = 64, ATTR_BATCHED = 128 };
 inline bool safe_pivots(const mpf_ctx *c) { return c->tune.safe_pivots != 0; }
@@ -516,7 +523,7 @@ int launch_getrs_batched(mpf_ctx *c, int trans, const double *LU, int64_t ldlu, 
 // mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
 int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 
-// ---- host-side helpers shared by the schedules (mpf_host.cpp, mpf_dist.cpp) --------------------------------------------
+// ---- host-side helpers shared by the schedules (mpf_factor.cpp, factor_rm.cpp, mpf_dist.cpp) --------------------------------------------
 struct StreamSwap { // launch_* helpers use c->stream: point it at another stream for a scope
     mpf_ctx *c; hipStream_t saved;
     StreamSwap(mpf_ctx *c_, hipStream_t s) : c(c_), saved(c_->stream) { c->stream = s; }

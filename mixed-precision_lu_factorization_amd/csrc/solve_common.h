@@ -1,4 +1,4 @@
-// What the host files of the solve layer share (mpf_solve.cpp, mpf_expert.cpp, mpf_block.cpp, mpf_dist.cpp, mpf_gesv in mpf_host.cpp):
+// What the host files of the solve layer share (mpf_solve.cpp, mpf_expert.cpp, mpf_block.cpp, mpf_dist.cpp):
 // the rules (solve_rules.h), the one vector refinement loop, the read-back and timing helpers.
 #pragma once
 #include "mpf_internal.h"

@@ -1,4 +1,4 @@
-"""The generic path (fp16_panel_generic.hip + the generic schedule in mpf_host.cpp): every shape the reference accepts and
+"""The generic path (fp16_panel_generic.hip + the generic schedule in mpf_factor.cpp): every shape the reference accepts and
 the tuned LDS-resident design does not cover -- panels wider than 256 columns (MPF() takes any r, MPF.cu:66,100-102),
 panels taller than 256 rows x #CUs (hgetf2_kernel.cu:6 allows 262 144 rows) -- and the opt-in no-spin mode for shared GPUs.
 Everything is compared bit for bit with the CPU oracle, and with the tuned path where both apply."""
