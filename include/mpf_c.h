@@ -680,9 +680,10 @@ int mpf_getdet(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, const int32_t *d_
                const double *d_r, const double *d_c, double *mant, int64_t *expo /* host */);
 
 /* ---- LU of many small matrices (build extension; LAPACK dgetrf / dgetrs per matrix of a strided batch) ---------------------------------
- * Every other entry point works on ONE matrix and is tuned for N >= 4096; these two take `batch` matrices of one size n <= 128 in one
+ * Every other entry point works on ONE matrix and is tuned for N >= 4096; these take `batch` matrices of one size n <= 128 in one
  * launch (csrc/batched.hip).  fp64 only, LAPACK partial pivoting: the fp16-image pivot rule and the fp16 trailing modes have no meaning
- * at these sizes.  No driver uses them; there is no batched inverse, determinant or refinement.
+ * at these sizes.  No driver uses them; the inverse and the determinant from the factors are mpf_getri_batched and mpf_getdet_batched
+ * below; there is no batched refinement.
  *
  * Layout: A[b] = d_A + b * strideA, n x n column-major, lda >= n, strideA >= lda * n (or batch == 1);
  * ipiv[b] = d_ipiv + b * strideP, strideP >= n (or batch == 1), 1-based as LAPACK; d_info: batch int32 on the device, optional.
@@ -715,6 +716,43 @@ int mpf_getrf_batched(mpf_ctx *ctx, double *d_A, int64_t lda, int64_t strideA, i
  * pointers).  n == 0, batch == 0 or nrhs == 0: returns 0, no work.  Asynchronous on the context's stream. */
 int mpf_getrs_batched(mpf_ctx *ctx, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                       const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB);
+/* inv[b] = d_inv + b * strideInv, n x n column-major, ldinv >= n, strideInv >= ldinv * n (or batch == 1):
+ * inv[b] := A[b]^-1 from the factors and pivots mpf_getrf_batched leaves, out of place: d_LU and d_ipiv are preserved, rows
+ * n .. ldinv-1 of every inv[b] and the bytes between matrices are not touched, and the address range of the d_inv batch must not
+ * overlap that of the d_LU batch (-1; mpf_getri's rule).
+ * Contract: for a matrix whose factors are finite and whose U has no zero on the diagonal, inv[b] equals, bit for bit, what
+ * mpf_getrs_batched(trans = 0) returns for B[b] = I with the same factors (tests/batched_model.py: getrs_model(LU, ipiv, eye(n))).
+ * Per element, column k
+ *   starts as e_q, q the position row k reaches under the interchanges j = 0 .. n-1;
+ *   then x_i <- x_i - l_ij x_j for j ascending;
+ *   then for i descending x_i <- x_i - u_ij x_j, j = n-1 down to i+1, and x_i <- x_i / u_ii;
+ * every step unfused (the product is rounded, then the difference).  No identity is formed or read.
+ * Structural zeros: above and below its one the column holds +0 until forward step q, so a forward step j < q subtracts
+ * l_ij (+0) = +-0 from +0, and +0 - (+-0) = +0 in round-to-nearest: a kernel form may skip those steps (rows above q stay +0) without
+ * changing a bit, the signs of zeros included, as long as the factors are finite.  Nothing is skipped in the backward sweep.
+ * (tests/batched_inv_model.py states the chain both ways and checks that they agree.)
+ * Singular matrices: d_info[b] (optional, batch int32 on the device) = i + 1 for the first u_ii == 0.0, else 0; such a matrix leaves
+ * inv[b] untouched (mpf_getri's and dgetri's rule), whether or not d_info is given.
+ * Not promised: the values of a matrix's result when its factors are not finite.  Even then every access stays in range (an ipiv
+ * entry outside 1 .. n reads as "no interchange", as in mpf_getrs_batched) and no other matrix is affected.  A matrix's bits depend on
+ * nothing but its own LU and ipiv: not on batch, its position, any ld or stride, or the kernel form (n <= 32: 8, 16 or 32 lanes of a
+ * wave per matrix, from registers; above: one workgroup per matrix, the factors in LDS).  Every launch is an ordinary launch.
+ * Returns 0, or < 0 with a message (n > 128: use mpf_factor_dev and mpf_getri; negative sizes, leading dimensions < n, strides too
+ * small, NULL d_LU, d_ipiv or d_inv, overlap).  n == 0 or batch == 0: returns 0, no work.  Asynchronous on the context's stream. */
+int mpf_getri_batched(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                      const int32_t *d_ipiv, int64_t strideP,
+                      double *d_inv, int64_t ldinv, int64_t strideInv, int32_t *d_info /* optional */);
+/* det(A[b]) = d_mant[b] 2^d_expo[b] from the same factors, |d_mant[b]| in [0.5, 1) or 0: mpf_getdet's order and special cases on
+ * every matrix.  n <= 128 is a single chunk of that order: (m_i, e_i) = frexp(u_ii); from p = 1, e = 0, i ascending: p = p m_i,
+ * (p, k) = frexp(p), e += k + e_i; the one combining step from (1, 0); the sign flips once per ipiv[i] != i + 1 -- the bits of
+ * tests/getri_model.py: getdet_model(diag(U), ipiv).  Any non-finite u_ii gives (NaN, 0); otherwise a zero u_ii gives (0, 0).
+ * d_expo is int32 (|expo| <= 128 * 1075).  No scale vectors: the batched factorization has no equilibration.  Reads n of the n^2
+ * doubles of a matrix.
+ * Returns 0, or < 0 with a message (as above; NULL d_mant or d_expo).  n == 0 or batch == 0: returns 0, no work, nothing written.
+ * Asynchronous on the context's stream. */
+int mpf_getdet_batched(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                       const int32_t *d_ipiv, int64_t strideP,
+                       double *d_mant, int32_t *d_expo /* device, batch each */);
 
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block

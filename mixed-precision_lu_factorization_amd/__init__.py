@@ -38,6 +38,7 @@ C_ABI_SYMBOLS = [
     "mpf_gerpvgrw", "mpf_gerfsx_scaled", "mpf_gesvxx_block",
     "mpf_getri", "mpf_getdet",
     "mpf_getrf_batched", "mpf_getrs_batched",
+    "mpf_getri_batched", "mpf_getdet_batched",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -207,6 +208,8 @@ def load_library(probe=False):
     L.mpf_getdet.argtypes = [vp, vp, i64, vp, i64, vp, vp, C.POINTER(dbl), C.POINTER(i64)]
     L.mpf_getrf_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, i32]
     L.mpf_getrs_batched.argtypes = [vp, i32, vp, i64, i64, i32, i64, vp, i64, i32, vp, i64, i64]
+    L.mpf_getri_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, i64, i64, vp]
+    L.mpf_getdet_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, vp]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -1099,3 +1102,72 @@ class MPFContext:
             b = int(bad[0])
             raise MPFError(f"solve_batched: matrix {b} of the batch is singular (zero pivot {int(info[b])})")
         return self.getrs_batched(LU, ipiv, B, trans=trans)
+
+    def _batch_factors(self, LU, ipiv, what):
+        """(LU, ldlu, strideLU, ipiv, strideP, batch, n) of a batch of factors as the library reads them (LU is copied only when its
+        matrices are not column-major as they stand)."""
+        t = self.torch
+        assert LU.dim() == 3 and LU.shape[1] == LU.shape[2], "LU: (batch, n, n)"
+        batch, n = LU.shape[0], LU.shape[1]
+        LUm, ldlu, slu = self._batch_arg(LU, what, False, copy=False)
+        assert ipiv.dtype == t.int32 and ipiv.is_cuda and ipiv.shape == (batch, n)
+        if n > 1 and ipiv.stride(1) != 1:
+            ipiv = ipiv.contiguous()
+        return LUm, ldlu, slu, ipiv, (ipiv.stride(0) if batch > 1 else max(n, 1)), batch, n
+
+    def getri_batched(self, LU, ipiv, out=None, info=None):
+        """mpf_getri_batched: inv(A[b]) from the factors of getrf_batched, out of place, bit for bit getrs_batched on an identity.
+        out: a (batch, n, n) tensor of column-major matrices to receive the inverses (colmajor_batch; a new one when None); info:
+        an int32 (batch,) device tensor.  Returns (inv, info): info[b] = i + 1 when u_ii is the first zero on U[b]'s diagonal --
+        out[b] is then untouched -- else 0."""
+        self._bind()
+        t = self.torch
+        LUm, ldlu, slu, ipiv, sp, batch, n = self._batch_factors(LU, ipiv, "getri_batched")
+        if out is None:
+            out = self.colmajor_batch(batch, n, n)
+        assert out.dim() == 3 and out.shape == (batch, n, n) and out.dtype == t.float64 and out.is_cuda
+        lay = self._batch_layout(out)
+        if lay is None:
+            raise MPFError("getri_batched: out needs column-major matrices (MPFContext.colmajor_batch)")
+        if info is None:
+            info = t.zeros(batch, dtype=t.int32, device=self.device)
+        assert info.dtype == t.int32 and info.is_cuda and info.shape == (batch,) and info.is_contiguous()
+        rc = self.L.mpf_getri_batched(self.h, _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, _ptr(out), lay[0], lay[1], _ptr(info))
+        self._check(rc, "mpf_getri_batched")
+        return out, info
+
+    def getdet_batched(self, LU, ipiv):
+        """mpf_getdet_batched: det(A[b]) = mant[b] * 2**expo[b] from the factors of getrf_batched, |mant| in [0.5, 1) or 0.  Returns
+        (mant float64 (batch,), expo int32 (batch,)) on the device; (0, 0) for a singular U[b], (nan, 0) for a non-finite one."""
+        self._bind()
+        t = self.torch
+        LUm, ldlu, slu, ipiv, sp, batch, n = self._batch_factors(LU, ipiv, "getdet_batched")
+        mant = t.full((batch,), 0.5, dtype=t.float64, device=self.device)     # n == 0: the empty product, mpf_getdet's (0.5, 1)
+        expo = t.ones(batch, dtype=t.int32, device=self.device)
+        rc = self.L.mpf_getdet_batched(self.h, _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, _ptr(mant), _ptr(expo))
+        self._check(rc, "mpf_getdet_batched")
+        return mant, expo
+
+    def inv_batched(self, A):
+        """inv(A[b]) for a (batch, n, n) tensor A, n <= 128: getrf_batched on a copy, then getri_batched.  Raises MPFError naming the
+        first singular matrix."""
+        LU, ipiv, info = self.getrf_batched(A)
+        X, info2 = self.getri_batched(LU, ipiv)
+        for inf in (info, info2):
+            bad = self.torch.nonzero(inf)
+            if bad.numel():
+                b = int(bad[0])
+                raise MPFError(f"inv_batched: matrix {b} of the batch is singular (zero pivot {int(inf[b])})")
+        return X
+
+    def slogdet_batched(self, A_or_LU, ipiv=None):
+        """(sign, log|det A[b]|) as torch.linalg.slogdet returns them, device tensors of (batch,): from getdet_batched,
+        log|mant| + expo ln 2 -- one rounded logarithm per matrix.  (0, -inf) for a zero determinant, (nan, nan) for a non-finite one.
+        ipiv=None: A_or_LU holds the matrices, and a copy is factored first; otherwise it holds getrf_batched's factors."""
+        import math
+        t = self.torch
+        if ipiv is None:
+            A_or_LU, ipiv, _ = self.getrf_batched(A_or_LU)
+        mant, expo = self.getdet_batched(A_or_LU, ipiv)
+        sign = t.where(t.isnan(mant), mant, t.sign(mant))         # (sign(0) is 0; sign(nan) is not nan on every backend)
+        return sign, t.log(t.abs(mant)) + expo.to(t.float64) * math.log(2.0)  # (expo is 0 beside log(0) = -inf and log(nan) = nan)

@@ -1,4 +1,5 @@
-// LU of many small matrices (mpf_getrf_batched, mpf_getrs_batched; contracts in include/mpf_c.h, host side in mpf_batched.cpp).
+// LU of many small matrices (mpf_getrf_batched, mpf_getrs_batched, and from their factors mpf_getri_batched, mpf_getdet_batched;
+// contracts in include/mpf_c.h, host side in mpf_batched.cpp).
 //
 // The numeric contract is dpivot.hip's on an n x n panel: idamax with a strict > on |a| (a NaN counts as 0, the first maximum wins,
 // an all-zero rest keeps p = j), m = a_ij / a_jj, then per element one update per k in ascending order (contract C3: separate
@@ -347,11 +348,273 @@ __global__ __launch_bounds__(BT_T) void bt_getrs_kernel(int trans, const double 
     }
 }
 
+// ---- inverse from the factors -----------------------------------------------------------------------------------------------------
+// inv[b] = what bt_getrs_kernel(trans = 0) leaves for B[b] = I, without the identity.  Column k of X starts as e_q, q = the position row
+// k reaches under the interchanges j = 0 .. n-1; then x_i -= l_ij x_j (j ascending); then, j descending, x_j /= u_jj and x_i -= u_ij x_j
+// for i < j.  Per element that is the solve's chain, so the bits are the solve's.
+// Structural zeros: before step q of the forward sweep column k holds +0 above and below its one, so the steps j < q subtract
+// l_ij * (+0) = +-0 from +0 (finite l_ij), and +0 - (+-0) = +0: skipping them changes no bit, the signs of zeros included.  The wave
+// form does not skip (a lane's column starts where it starts; the step is the wave's), the workgroup form starts a group of four
+// columns at the smallest q among them.  Nothing is skipped in the backward sweep.
+//   bt_getri_wave_kernel<W>     n <= W = 8, 16, 32: 64 / W matrices per wave64; lane = (matrix, row) for the load of LU -- the row's W
+//                               columns in registers -- and lane = (matrix, COLUMN of X) for the sweeps: the column's W rows in registers,
+//                               l_ij / u_ij broadcast from the row's lane by ds_bpermute (W^2 broadcasts per matrix for both sweeps),
+//                               x_j is the lane's own register, and the division x_j / u_jj is one instruction sequence per step for all
+//                               W columns.  (With lane = row for X, as the factorization has it, a step broadcasts row j of X -- 2 W^2
+//                               broadcasts -- and every lane repeats the W divisions of the step for the one lane that holds row j: W^2
+//                               division sequences per wave against W here; not built for that reason.)  No LDS memory, no barrier.
+//   bt_getri_wg_kernel<H>       32 < n <= 128: one workgroup per matrix, LU once into LDS (odd leading dimension), X never: a wave owns
+//                               four columns of X at a time, lane = row, H rows per lane; x_j by v_readlane.  The four x_j of a backward
+//                               step are gathered into lanes 0 .. 3, divided by u_jj in ONE division sequence and read back by v_readlane
+//                               (every lane of the wave repeating the division per column was the larger half of a backward step's
+//                               instructions); one LDS read of l_ij / u_ij serves the four columns.  256 threads for n <= 64, 1024 above
+//                               (the LDS leaves room for one workgroup per CU there).  No barrier after the pivots are composed.
+//                               The updates are selects, not branches: written as `if (r == j) .. else if (r < j) ..` per column the
+//                               compiler built a nest of exec-mask branches with a copy of all eight registers on each side --
+//                               3.89 ms for 16384 matrices of order 64 and 5.69 ms for 4096 of order 128 against 3.43 and 5.45 ms now.
+// Measured on one MI355X, 512 MB of factors per size (tools/batched_inv_probe.py; "before" = an identity batch filled on the device and
+// bt_getrs_kernel with nrhs = n, the only route before these kernels): n = 8: 0.445 ms against 1.110 ms; 16: 0.665 / 1.811; 32: 0.800 /
+// 4.591; 64: 3.425 / 4.879; 128: 5.452 / 24.385.  Not tried: X in LDS with LU streamed from L2 and a rank-1 update per step; staging
+// the wave form's stores through LDS (a lane stores a column: 8-byte stores ldinv apart, where the load of LU is coalesced).
+// A zero on U's diagonal: found by the matrix's lanes before any store; the whole team then skips the stores.
+template <int W>
+__global__ __launch_bounds__(BT_T) void bt_getri_wave_kernel(const double *LU, long long ldlu, long long strideLU, int n, long long batch,
+                                                            const int *ipiv, long long strideP, double *inv, long long ldinv,
+                                                            long long strideInv, int *info) {
+    constexpr int G = 64 / W;
+    const int lane = threadIdx.x & 63, r = lane & (W - 1), g = lane / W, base = lane & ~(W - 1);
+    const long long b0 = ((long long)blockIdx.x * (BT_T / 64) + (threadIdx.x >> 6)) * G, b = b0 + g;
+    if (b0 >= batch) return;                                    // (the whole wave)
+    const bool valid = b < batch && r < n;
+    const double *a = LU + (valid ? b : b0) * strideLU;
+    double lu[W], x[W];
+#pragma unroll
+    for (int c = 0; c < W; ++c) lu[c] = (valid && c < n) ? a[r + (long long)c * ldlu] : 0.0;   // row r of LU
+    int p = r;
+    if (valid) {
+        p = ipiv[b * strideP + r] - 1;
+        if (p < 0 || p >= n) p = r;                             // (never, for pivots of a factorization: as bt_getrs_kernel)
+    }
+    int q = r;                                                  // where row r stands after the interchanges: column r of X starts as e_q
+    double d = 1.0;                                             // u_rr
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        if (j < n) {                                            // (uniform)
+            const int pj = __shfl(p, base | j);
+            q = q == j ? pj : (q == pj ? j : q);
+        }
+        if (j == r) d = lu[j];
+    }
+    int z = (valid && d == 0.0) ? r + 1 : INT_MAX;              // the first zero on U's diagonal, in every lane of the matrix
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) { const int z1 = __shfl_xor(z, o); z = z1 < z ? z1 : z; }
+#pragma unroll
+    for (int i = 0; i < W; ++i) x[i] = i == q ? 1.0 : 0.0;
+    // from here on the lane is column r of X; lane base | i still holds row i of LU
+#pragma unroll
+    for (int j = 0; j < W; ++j) {                               // L: x_i -= l_ij x_j
+        if (j + 1 < n) {
+#pragma unroll
+            for (int i = j + 1; i < W; ++i) {
+                if (i < n) {
+                    const double l = __shfl(lu[j], base | i);
+                    const double t = l * x[j];
+                    x[i] = x[i] - t;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = W - 1; j >= 0; --j) {                          // U: x_j /= u_jj, then x_i -= u_ij x_j
+        if (j < n) {
+            const double ujj = __shfl(lu[j], base | j);
+            x[j] = x[j] / ujj;
+#pragma unroll
+            for (int i = 0; i < j; ++i) {
+                const double u = __shfl(lu[j], base | i);
+                const double t = u * x[j];
+                x[i] = x[i] - t;
+            }
+        }
+    }
+    if (!valid) return;
+    if (z == INT_MAX) {
+        double *o = inv + b * strideInv + (long long)r * ldinv;
+#pragma unroll
+        for (int i = 0; i < W; ++i)
+            if (i < n) o[i] = x[i];
+    }
+    if (info && r == 0) info[b] = z == INT_MAX ? 0 : z;
+}
+
+// LDS: T[ldl x n] doubles, then qpos[BT_MAXN] (where each row stands after the interchanges), pv[BT_MAXN], ctl[4] (the first zero of
+// U's diagonal)
+static size_t bt_getri_wg_lds(int n) { return (size_t)(n | 1) * n * sizeof(double) + (2 * BT_MAXN + 4) * sizeof(int); }
+
+template <int H>
+__global__ __launch_bounds__(H == 1 ? 256 : 1024) void bt_getri_wg_kernel(const double *LU, long long ldlu, long long strideLU, int n,
+                                                                         const int *ipiv, long long strideP, double *inv, long long ldinv,
+                                                                         long long strideInv, int *info) {
+    constexpr int NT = H == 1 ? 256 : 1024, NW = NT / 64, CB = 4;
+    const int ldl = n | 1;
+    double *T = (double *)bt_smem;
+    int *qpos = (int *)(T + (size_t)ldl * n), *pv = qpos + BT_MAXN, *ctl = pv + BT_MAXN;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long long b = blockIdx.x;
+    bt_load_matrix(LU + b * strideLU, ldlu, n, T, ldl, tid, NT);
+    if (tid < n) {
+        int p = ipiv[b * strideP + tid] - 1;
+        if (p < 0 || p >= n) p = tid;                            // (as bt_getrs_kernel: keeps every access in range)
+        pv[tid] = p;
+    }
+    if (tid == 0) ctl[0] = INT_MAX;
+    __syncthreads();
+    if (tid < n) {
+        int cpos = tid;
+        for (int j = 0; j < n; ++j) { const int p = pv[j]; cpos = cpos == j ? p : (cpos == p ? j : cpos); }
+        qpos[tid] = cpos;
+        if (T[tid + tid * ldl] == 0.0) atomicMin(&ctl[0], tid + 1);
+    }
+    __syncthreads();
+    const int z = ctl[0];
+    if (info && tid == 0) info[b] = z == INT_MAX ? 0 : z;
+    if (z != INT_MAX) return;                                    // (the whole workgroup: nothing is stored)
+    double *o = inv + b * strideInv;
+    for (int kb = w * CB; kb < n; kb += NW * CB) {               // columns kb .. kb + 3 of X (those past n: all zero, not stored)
+        double x[CB][H], xj[CB];
+        int q0 = n;
+#pragma unroll
+        for (int c = 0; c < CB; ++c) {
+            const int qc = kb + c < n ? qpos[kb + c] : n;
+            q0 = qc < q0 ? qc : q0;
+#pragma unroll
+            for (int h = 0; h < H; ++h) x[c][h] = lane + 64 * h == qc ? 1.0 : 0.0;
+        }
+        q0 = __builtin_amdgcn_readfirstlane(q0);                 // (the same in every lane: keeps the step counter scalar)
+        for (int j = q0; j < n - 1; ++j) {                       // L: x_i -= l_ij x_j; the steps before q0 meet zeros only
+#pragma unroll
+            for (int c = 0; c < CB; ++c) xj[c] = bt_bcast<H>(x[c], j);
+#pragma unroll
+            for (int h = 0; h < H; ++h) {
+                if (64 * h + 63 > j) {                           // (uniform)
+                    const int r = lane + 64 * h;
+                    const bool low = r > j && r < n;
+                    const double l = low ? T[r + j * ldl] : 0.0;
+#pragma unroll
+                    for (int c = 0; c < CB; ++c) {               // (selects, not branches: the other lanes' differences are dropped)
+                        const double t = l * xj[c];
+                        const double v = x[c][h] - t;
+                        x[c][h] = low ? v : x[c][h];
+                    }
+                }
+            }
+        }
+        for (int j = n - 1; j >= 0; --j) {                       // U: x_j /= u_jj, then x_i -= u_ij x_j
+            double dv = 1.0;
+#pragma unroll
+            for (int c = 0; c < CB; ++c) { const double v = bt_bcast<H>(x[c], j); if (lane == c) dv = v; }
+            dv = dv / T[j + j * ldl];                            // the four divisions of the step, in lanes 0 .. 3
+#pragma unroll
+            for (int c = 0; c < CB; ++c) xj[c] = bt_readlane(dv, c);
+#pragma unroll
+            for (int h = 0; h < H; ++h) {
+                if (64 * h <= j) {                               // (uniform)
+                    const int r = lane + 64 * h;
+                    const bool up = r < j;
+                    const double u = up ? T[r + j * ldl] : 0.0;
+#pragma unroll
+                    for (int c = 0; c < CB; ++c) {
+                        const double t = u * xj[c];
+                        const double v = x[c][h] - t;
+                        x[c][h] = r == j ? xj[c] : (up ? v : x[c][h]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CB; ++c) {
+            if (kb + c < n) {
+                double *col = o + (long long)(kb + c) * ldinv;
+#pragma unroll
+                for (int h = 0; h < H; ++h) {
+                    const int r = lane + 64 * h;
+                    if (r < n) col[r] = x[c][h];
+                }
+            }
+        }
+    }
+}
+
+// ---- determinant from the factors -------------------------------------------------------------------------------------------------
+// mpf_getdet's order on one chunk (n <= 128 < 256): (m_i, e_i) = frexp(u_ii); from p = 1, e = 0: p = p m_i, (p, k) = frexp(p),
+// e += k + e_i, i ascending; the one combining step from (1, 0); the sign flips once per ipiv[i] != i + 1.  The chain is serial by
+// contract.  TS = 1: a thread per matrix (n <= 32); TS = 64: a wave per matrix, the diagonal and the pivots loaded by lane = row, the
+// pivot count and the special cases by ballot, the chain on v_readlane values (every lane runs it; lane 0 stores).
+template <int TS>
+__global__ __launch_bounds__(BT_T) void bt_getdet_kernel(const double *LU, long long ldlu, long long strideLU, int n, long long batch,
+                                                        const int *ipiv, long long strideP, double *mant, int *expo) {
+    double p = 1.0;
+    int e = 0, flips = 0;
+    bool zero = false, bad = false;
+    long long b;
+    if (TS == 1) {
+        b = (long long)blockIdx.x * BT_T + threadIdx.x;
+        if (b >= batch) return;
+        const double *a = LU + b * strideLU;
+        const int *pv = ipiv + b * strideP;
+        for (int i = 0; i < n; ++i) {
+            const double u = a[i + (long long)i * ldlu];
+            zero |= u == 0.0;
+            bad |= !(fabs(u) <= 1.7976931348623157e308);
+            flips ^= pv[i] != i + 1 ? 1 : 0;
+            int ei, k;
+            const double m = frexp(u, &ei);
+            p = frexp(p * m, &k);
+            e += k + ei;
+        }
+    } else {
+        const int lane = threadIdx.x & 63;
+        b = (long long)blockIdx.x * (BT_T / 64) + (threadIdx.x >> 6);
+        if (b >= batch) return;                                  // (the whole wave)
+        const double *a = LU + b * strideLU;
+        const int *pv = ipiv + b * strideP;
+        double m[2];
+        int ex[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int r = lane + 64 * h;
+            const double u = r < n ? a[r + (long long)r * ldlu] : 1.0;
+            const bool f = r < n && pv[r] != r + 1;
+            zero |= __any(u == 0.0) != 0;
+            bad |= __any(!(fabs(u) <= 1.7976931348623157e308)) != 0;
+            flips += __popcll(__ballot(f));
+            m[h] = frexp(u, &ex[h]);
+        }
+        for (int i = 0; i < n; ++i) {
+            const double mi = bt_bcast<2>(m, i);
+            const int ei = i < 64 ? __builtin_amdgcn_readlane(ex[0], i) : __builtin_amdgcn_readlane(ex[1], i - 64);
+            int k;
+            p = frexp(p * mi, &k);
+            e += k + ei;
+        }
+        if (lane != 0) return;
+    }
+    int k;
+    double P = frexp(1.0 * p, &k);                               // the combining step of the one chunk
+    int E = k + e;
+    if (flips & 1) P = -P;
+    if (bad) { P = __builtin_nan(""); E = 0; }
+    else if (zero) { P = 0.0; E = 0; }
+    mant[b] = P;
+    expo[b] = E;
+}
+
 // ---- launchers: one launch each, batch <= BT_MAX_LAUNCH matrices (the host splits longer batches) -----------------------------------
 static int bt_attrs(mpf_ctx *c) {
     if (c->attr_done & ATTR_BATCHED) return 0;
     const void *ks[] = {(const void *)bt_getrf_wg_kernel<false, 1>, (const void *)bt_getrf_wg_kernel<true, 1>,
                         (const void *)bt_getrf_wg_kernel<false, 2>, (const void *)bt_getrf_wg_kernel<true, 2>,
+                        (const void *)bt_getri_wg_kernel<1>, (const void *)bt_getri_wg_kernel<2>,
                         (const void *)bt_getrs_kernel<1, 32>, (const void *)bt_getrs_kernel<1, 256>, (const void *)bt_getrs_kernel<2, 256>};
     for (const void *k : ks) MPF_HIP_TRY(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     c->attr_done |= ATTR_BATCHED;
@@ -407,6 +670,46 @@ int launch_getrs_batched(mpf_ctx *c, int trans, const double *LU, int64_t ldlu, 
     else if (n <= 64) BT_SOLVE(1, 256);
     else BT_SOLVE(2, 256);
 #undef BT_SOLVE
+    MPF_HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int launch_getri_batched(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv, int64_t strideP,
+                         double *inv, int64_t ldinv, int64_t strideInv, int *info) {
+    if (n < 1 || batch < 1) return 0;
+    if (n > BT_MAXN || batch > BT_MAX_LAUNCH) { c->err = "launch_getri_batched: size out of range"; return -1; }
+    if (n <= 32) {
+#define BT_INV(W_)                                                                                                                   \
+        do {                                                                                                                         \
+            const long long per = (BT_T / W_);                                                                                       \
+            const unsigned g = (unsigned)((batch + per - 1) / per);                                                                  \
+            bt_getri_wave_kernel<W_><<<g, BT_T, 0, c->stream>>>(LU, ldlu, strideLU, n, batch, ipiv, strideP, inv, ldinv, strideInv, info); \
+        } while (0)
+        if (n <= 8) BT_INV(8);
+        else if (n <= 16) BT_INV(16);
+        else BT_INV(32);
+#undef BT_INV
+    } else {
+        { const int e = bt_attrs(c); if (e) return e; }
+        const size_t lds = bt_getri_wg_lds(n);
+        if (n <= 64) bt_getri_wg_kernel<1><<<(unsigned)batch, 256, lds, c->stream>>>(LU, ldlu, strideLU, n, ipiv, strideP, inv, ldinv, strideInv, info);
+        else bt_getri_wg_kernel<2><<<(unsigned)batch, 1024, lds, c->stream>>>(LU, ldlu, strideLU, n, ipiv, strideP, inv, ldinv, strideInv, info);
+    }
+    MPF_HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int launch_getdet_batched(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv, int64_t strideP,
+                          double *mant, int *expo) {
+    if (n < 1 || batch < 1) return 0;
+    if (n > BT_MAXN || batch > BT_MAX_LAUNCH) { c->err = "launch_getdet_batched: size out of range"; return -1; }
+    if (n <= 32) {
+        const unsigned g = (unsigned)((batch + BT_T - 1) / BT_T);
+        bt_getdet_kernel<1><<<g, BT_T, 0, c->stream>>>(LU, ldlu, strideLU, n, batch, ipiv, strideP, mant, expo);
+    } else {
+        const unsigned g = (unsigned)((batch + BT_T / 64 - 1) / (BT_T / 64));
+        bt_getdet_kernel<64><<<g, BT_T, 0, c->stream>>>(LU, ldlu, strideLU, n, batch, ipiv, strideP, mant, expo);
+    }
     MPF_HIP_TRY(c, hipGetLastError());
     return 0;
 }

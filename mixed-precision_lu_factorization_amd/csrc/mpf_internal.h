@@ -520,6 +520,12 @@ int launch_getrf_batched(mpf_ctx *c, double *A, int64_t lda, int64_t strideA, in
                          int fused);
 int launch_getrs_batched(mpf_ctx *c, int trans, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv,
                          int64_t strideP, int nrhs, double *B, int64_t ldb, int64_t strideB);
+// launch_getri_batched: inv[b] = launch_getrs_batched(trans = 0)'s bits on an identity, out of place; a matrix with a zero on U's
+// diagonal is left untouched, info[b] (when not null) = the first such i + 1 or 0.  launch_getdet_batched: mpf_getdet's order per matrix
+int launch_getri_batched(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv, int64_t strideP,
+                         double *inv, int64_t ldinv, int64_t strideInv, int *info);
+int launch_getdet_batched(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv, int64_t strideP,
+                          double *mant, int *expo);
 // mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
 int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 
