@@ -683,7 +683,7 @@ int mpf_getdet(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, const int32_t *d_
  * Every other entry point works on ONE matrix and is tuned for N >= 4096; these take `batch` matrices of one size n <= 128 in one
  * launch (csrc/batched.hip).  fp64 only, LAPACK partial pivoting: the fp16-image pivot rule and the fp16 trailing modes have no meaning
  * at these sizes.  No driver uses them; the inverse and the determinant from the factors are mpf_getri_batched and mpf_getdet_batched
- * below; there is no batched refinement.
+ * below; matrices of different orders in one call: the mpf_*_vbatched entries after them; there is no batched refinement.
  *
  * Layout: A[b] = d_A + b * strideA, n x n column-major, lda >= n, strideA >= lda * n (or batch == 1);
  * ipiv[b] = d_ipiv + b * strideP, strideP >= n (or batch == 1), 1-based as LAPACK; d_info: batch int32 on the device, optional.
@@ -753,6 +753,56 @@ int mpf_getri_batched(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t st
 int mpf_getdet_batched(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                        const int32_t *d_ipiv, int64_t strideP,
                        double *d_mant, int32_t *d_expo /* device, batch each */);
+
+/* ---- the same for matrices of DIFFERENT orders (vbatched; csrc/vbatched.hip, host plan in csrc/vbatch_plan.h) ---------------------------
+ * One descriptor says where `batch` matrices of orders 0 <= n[b] <= 128 lie inside ONE allocation; four entry points then factor, solve,
+ * invert and take determinants of all of them in a handful of ordinary launches (one per size class that is not empty).  For every b the
+ * result equals, bit for bit, what the fixed-size entry above returns for that matrix alone with n = n[b]: a matrix's bits do not depend
+ * on the batch, its position, the orders of its neighbours (the matrices that share its wave included), ld, off, the class order or the
+ * kernel form.
+ *
+ * Matrix layout (A / LU, and the inverse): matrix b is n[b] x n[b] column-major at base + off[b] (an element offset) with leading
+ * dimension ld[b].  ld == NULL: ld[b] = n[b].  off == NULL: packed, off[b] = sum_{i<b} ld[i] n[i].  extent = the doubles the operand
+ * spans = max_b off[b] + (n[b] - 1) ld[b] + n[b] (matrices of order 0 span nothing).
+ * Vector layout (always packed): offV[b] = sum_{i<b} n[i], total_n = sum n.  Pivots of matrix b: d_ipiv + offV[b] (1-based).  The
+ * right-hand sides of all matrices form one tall total_n x nrhs column-major matrix, ldb >= total_n; B[b] is its rows offV[b] ..
+ * offV[b] + n[b] - 1: the block-diagonal solve D^-1 B.  d_info, d_mant, d_expo: one entry per matrix.
+ *
+ * mpf_vbatch_create checks on the host and refuses with a message (< 0): negative batch or n[b]; n[b] > 128 (use mpf_factor_dev);
+ * ld[b] < n[b]; off[b] < 0; an extent past 2^62; two matrices whose footprints [off, off + (n-1) ld + n) overlap (footprints that only
+ * touch are accepted); batch >= 2^31.  n[b] == 0 and batch == 0 are allowed.  It then bins the matrices into size classes by n[b] alone --
+ * n <= 8, 16, 32: 8, 16 or 32 lanes of a wave per matrix; n <= 48, 64: a 256-thread workgroup per matrix; n <= 96, 128: a 1024-thread
+ * one (two classes per workgroup form, so that a launch asks only for the LDS its largest matrix needs) -- orders every class by n
+ * (stable) and uploads n, off, ld, offV and the class lists (synchronous copies; the descriptor owns the device memory).  Matrices of
+ * order 0 are in no class: they are kept in a list of their own, for d_info and the determinant.
+ * mpf_vbatch_destroy synchronises the context's stream first; destroy every descriptor before its context.
+ * mpf_vbatch_info / mpf_vbatch_offsets: what creation computed (any output may be NULL); offM = the matrix offsets, offV the vector ones.
+ *
+ * Not here: pointer arrays to separate allocations, n > 128, a per-matrix nrhs, sizes given on the device, a block-diagonal
+ * matrix-vector product with the inverses, fp16, refinement.  No driver uses these. */
+typedef struct mpf_vbatch mpf_vbatch;
+int mpf_vbatch_create(mpf_ctx *ctx, int64_t batch, const int32_t *n /* host */, const int64_t *ld /* host, optional */,
+                      const int64_t *off /* host, optional */, mpf_vbatch **out);
+void mpf_vbatch_destroy(mpf_vbatch *vb);
+int mpf_vbatch_info(const mpf_vbatch *vb, int64_t *batch, int64_t *total_n, int64_t *extent);
+int mpf_vbatch_offsets(const mpf_vbatch *vb, int64_t *offM /* host, batch */, int64_t *offV /* host, batch */);
+/* mpf_getrf_batched's contract per matrix (pivots and bits of mpf_dgetf2_piv, fused or not); d_info[b] (optional) = the first zero
+ * pivot or 0, 0 for n[b] == 0.  Rows n[b] .. ld[b]-1 and every byte between matrices are not touched.  Returns 0, or < 0 with a message
+ * (NULL ctx, descriptor, d_A or d_ipiv; a descriptor of another context).  batch == 0 or total_n == 0: no work on the matrices.
+ * These four calls are asynchronous on the context's stream, use no workspace beyond the descriptor and read nothing back; a class
+ * with more matrices than one grid takes is launched in chunks. */
+int mpf_getrf_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, double *d_A, int32_t *d_ipiv, int32_t *d_info /* optional */, int32_t fused);
+/* mpf_getrs_batched's chains per matrix on rows offV[b] .. of the tall B, in place; rows of B outside 0 .. total_n-1 are not touched.
+ * Refused: NULL pointers, trans not 0 or 1, nrhs < 0, ldb < total_n, a descriptor of another context.  nrhs == 0: no work. */
+int mpf_getrs_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, int32_t trans, const double *d_LU, const int32_t *d_ipiv, int32_t nrhs,
+                       double *d_B, int64_t ldb);
+/* mpf_getri_batched's contract per matrix, the inverse in the descriptor's matrix layout at d_inv, out of place: refused when
+ * [d_LU, + extent) and [d_inv, + extent) overlap.  A matrix with a zero on U's diagonal: d_info[b] = the first such i + 1, its inverse
+ * is left untouched, no neighbour is affected; ipiv entries out of range read as "no interchange".  d_info[b] = 0 for n[b] == 0. */
+int mpf_getri_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, const double *d_LU, const int32_t *d_ipiv, double *d_inv,
+                       int32_t *d_info /* optional */);
+/* mpf_getdet_batched's (mant, expo) per matrix; n[b] == 0 gives (0.5, 1), mpf_getdet's N = 0 case. */
+int mpf_getdet_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, const double *d_LU, const int32_t *d_ipiv, double *d_mant, int32_t *d_expo);
 
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block

@@ -39,6 +39,8 @@ C_ABI_SYMBOLS = [
     "mpf_getri", "mpf_getdet",
     "mpf_getrf_batched", "mpf_getrs_batched",
     "mpf_getri_batched", "mpf_getdet_batched",
+    "mpf_vbatch_create", "mpf_vbatch_destroy", "mpf_vbatch_info", "mpf_vbatch_offsets",
+    "mpf_getrf_vbatched", "mpf_getrs_vbatched", "mpf_getri_vbatched", "mpf_getdet_vbatched",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -210,6 +212,15 @@ def load_library(probe=False):
     L.mpf_getrs_batched.argtypes = [vp, i32, vp, i64, i64, i32, i64, vp, i64, i32, vp, i64, i64]
     L.mpf_getri_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, i64, i64, vp]
     L.mpf_getdet_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, vp]
+    L.mpf_vbatch_create.argtypes = [vp, i64, vp, vp, vp, C.POINTER(vp)]
+    L.mpf_vbatch_destroy.argtypes = [vp]
+    L.mpf_vbatch_destroy.restype = None
+    L.mpf_vbatch_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.mpf_vbatch_offsets.argtypes = [vp, vp, vp]
+    L.mpf_getrf_vbatched.argtypes = [vp, vp, vp, vp, vp, i32]
+    L.mpf_getrs_vbatched.argtypes = [vp, vp, i32, vp, vp, i32, vp, i64]
+    L.mpf_getri_vbatched.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mpf_getdet_vbatched.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -334,6 +345,8 @@ class MPFContext:
 
     def close(self):
         if self.h:
+            for vb in list(getattr(self, "_vbatches", ())):      # a descriptor is destroyed before its context
+                vb.close()
             self.L.mpf_destroy(self.h)
             self.h = C.c_void_p()
 
@@ -1171,3 +1184,188 @@ class MPFContext:
         mant, expo = self.getdet_batched(A_or_LU, ipiv)
         sign = t.where(t.isnan(mant), mant, t.sign(mant))         # (sign(0) is 0; sign(nan) is not nan on every backend)
         return sign, t.log(t.abs(mant)) + expo.to(t.float64) * math.log(2.0)  # (expo is 0 beside log(0) = -inf and log(nan) = nan)
+
+
+    # ---- the same for matrices of different orders (include/mpf_c.h: mpf_vbatch_create, mpf_getrf_vbatched, ...) --------------------------
+    def vbatch(self, n, ld=None, off=None):
+        """mpf_vbatch_create: the descriptor of a batch of matrices of orders n[b] <= 128 inside one allocation -- matrix b column-major
+        at element offset off[b] with leading dimension ld[b] (ld=None: n[b]; off=None: packed).  Returns a VBatch."""
+        return VBatch(self, n, ld, off)
+
+
+class VBatch:
+    """A variable-size batch (mpf_vbatch): `batch` matrices of orders n[b] in one flat float64 device tensor of `extent` elements; the
+    pivots of all matrices in one int32 tensor of total_n, matrix b's at offv[b]; right-hand sides as one tall (total_n, nrhs)
+    column-major matrix.  Attributes: batch, total_n, extent, n, ld, off, offv (numpy).  Every method is asynchronous on the context's
+    stream except solve / inv, which read info back."""
+
+    def __init__(self, ctx, n, ld=None, off=None):
+        import weakref
+        import numpy as np
+        ctx._bind()
+        self.ctx, self.h = ctx, C.c_void_p()
+        self.n = np.ascontiguousarray(n, dtype=np.int32).reshape(-1)
+        batch = self.n.size
+        args = []
+        for name, a in (("ld", ld), ("off", off)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+                assert a.size == batch, f"{name}: one entry per matrix"
+            args.append(a)
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None   # noqa: E731
+        rc = ctx.L.mpf_vbatch_create(ctx.h, batch, ptr(self.n), ptr(args[0]), ptr(args[1]), C.byref(self.h))
+        ctx._check(rc, "mpf_vbatch_create")
+        b, tn, ext = C.c_int64(), C.c_int64(), C.c_int64()
+        ctx.L.mpf_vbatch_info(self.h, C.byref(b), C.byref(tn), C.byref(ext))
+        self.batch, self.total_n, self.extent = b.value, tn.value, ext.value
+        self.off, self.offv = np.zeros(batch, dtype=np.int64), np.zeros(batch, dtype=np.int64)
+        ctx.L.mpf_vbatch_offsets(self.h, ptr(self.off), ptr(self.offv))
+        self.ld = args[0] if args[0] is not None else self.n.astype(np.int64)
+        if not hasattr(ctx, "_vbatches"):
+            ctx._vbatches = weakref.WeakSet()
+        ctx._vbatches.add(self)
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.L.mpf_vbatch_destroy(self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- layout helpers -------------------------------------------------------------------------------------------------------------
+    def pack(self, mats, fill=0.0):
+        """A flat float64 device tensor of `extent` elements holding the matrices (numpy arrays or tensors, n[b] x n[b]) in this layout;
+        the elements between them are `fill`."""
+        import numpy as np
+        assert len(mats) == self.batch
+        flat = np.full(self.extent, fill, dtype=np.float64)
+        for b, M in enumerate(mats):
+            nb, l, o = int(self.n[b]), int(self.ld[b]), int(self.off[b])
+            if nb == 0:
+                continue
+            M = M.cpu().numpy() if hasattr(M, "cpu") else np.asarray(M, dtype=np.float64)
+            assert M.shape == (nb, nb), f"matrix {b}: ({nb}, {nb})"
+            np.lib.stride_tricks.as_strided(flat[o:], (nb, nb), (8, 8 * l))[...] = M
+        return self.ctx.torch.from_numpy(flat).to(self.ctx.device)
+
+    def unpack(self, flat):
+        """The matrices of a flat tensor in this layout: a list of n[b] x n[b] column-major views of `flat`."""
+        assert flat.dim() == 1 and flat.numel() >= self.extent
+        return [flat.as_strided((int(nb), int(nb)), (1, int(l)), int(o)) if nb else flat.new_zeros((0, 0))
+                for nb, l, o in zip(self.n, self.ld, self.off)]
+
+    def _flat(self, x, what):
+        t = self.ctx.torch
+        assert x.dim() == 1 and x.dtype == t.float64 and x.is_cuda and x.is_contiguous() and x.numel() >= self.extent, \
+            f"{what}: a flat float64 device tensor of at least extent = {self.extent} elements"
+        return x
+
+    def _pivots(self, ipiv):
+        t = self.ctx.torch
+        assert ipiv.dim() == 1 and ipiv.dtype == t.int32 and ipiv.is_cuda and ipiv.is_contiguous() and ipiv.numel() >= self.total_n
+        return ipiv
+
+    def _info(self, info):
+        t = self.ctx.torch
+        if info is None:
+            info = t.zeros(self.batch, dtype=t.int32, device=self.ctx.device)
+        assert info.dtype == t.int32 and info.is_cuda and info.shape == (self.batch,) and info.is_contiguous()
+        return info
+
+    # ---- the four operations ----------------------------------------------------------------------------------------------------------
+    def getrf(self, A, fused=False, overwrite=False, ipiv=None, info=None):
+        """mpf_getrf_vbatched: (LU, ipiv, info) -- LU flat in this layout (A itself with overwrite=True, else a copy), ipiv int32
+        (total_n,), 1-based, matrix b's at offv[b]; info int32 (batch,): the first zero pivot of each matrix or 0."""
+        ctx, t = self.ctx, self.ctx.torch
+        ctx._bind()
+        LU = self._flat(A, "getrf") if overwrite else self._flat(A, "getrf").clone()
+        if ipiv is None:
+            ipiv = t.zeros(self.total_n, dtype=t.int32, device=ctx.device)
+        info = self._info(info)
+        rc = ctx.L.mpf_getrf_vbatched(ctx.h, self.h, _ptr(LU), _ptr(self._pivots(ipiv)), _ptr(info), int(bool(fused)))
+        ctx._check(rc, "mpf_getrf_vbatched")
+        return LU, ipiv, info
+
+    def getrs(self, LU, ipiv, B, trans=False, overwrite=False):
+        """mpf_getrs_vbatched: the block-diagonal solve X = D^-1 B (or D^-T B); B is (total_n,) or a column-major (total_n, nrhs)
+        tensor (MPFContext.colmajor).  Returns a new X unless overwrite=True (B itself, solved in place)."""
+        ctx = self.ctx
+        ctx._bind()
+        if B.dim() == 1:
+            assert B.is_contiguous()
+            return self.getrs(LU, ipiv, B.unsqueeze(1), trans, overwrite).squeeze(1)
+        assert B.dim() == 2 and B.shape[0] == self.total_n and B.dtype == ctx.torch.float64 and B.is_cuda, "B: (total_n, nrhs) float64"
+        nrhs = B.shape[1]
+        colmajor = (B.shape[0] <= 1 or B.stride(0) == 1) and (nrhs <= 1 or B.stride(1) >= max(self.total_n, 1))
+        if overwrite:
+            if not colmajor:
+                raise MPFError("getrs: overwrite=True needs a column-major B (MPFContext.colmajor); this tensor would be copied")
+            X = B
+        else:
+            X = ctx.colmajor(self.total_n, nrhs)
+            X.copy_(B)
+        ldb = X.stride(1) if nrhs > 1 else max(self.total_n, 1)
+        rc = ctx.L.mpf_getrs_vbatched(ctx.h, self.h, int(bool(trans)), _ptr(self._flat(LU, "getrs")), _ptr(self._pivots(ipiv)), nrhs,
+                                      _ptr(X), ldb)
+        ctx._check(rc, "mpf_getrs_vbatched")
+        return X
+
+    def getri(self, LU, ipiv, out=None, info=None):
+        """mpf_getri_vbatched: (inv, info) -- the inverses flat in this layout, out of place (out: a flat tensor to receive them; a
+        zero-filled one when None); info[b] = i + 1 when u_ii is the first zero on U[b]'s diagonal -- inv[b] is then untouched."""
+        ctx, t = self.ctx, self.ctx.torch
+        ctx._bind()
+        if out is None:
+            out = t.zeros(max(self.extent, 1), dtype=t.float64, device=ctx.device)
+        info = self._info(info)
+        rc = ctx.L.mpf_getri_vbatched(ctx.h, self.h, _ptr(self._flat(LU, "getri")), _ptr(self._pivots(ipiv)), _ptr(self._flat(out, "getri out")),
+                                      _ptr(info))
+        ctx._check(rc, "mpf_getri_vbatched")
+        return out, info
+
+    def getdet(self, LU, ipiv):
+        """mpf_getdet_vbatched: (mant float64 (batch,), expo int32 (batch,)) on the device, det(A[b]) = mant[b] * 2**expo[b]."""
+        ctx, t = self.ctx, self.ctx.torch
+        ctx._bind()
+        mant = t.zeros(self.batch, dtype=t.float64, device=ctx.device)
+        expo = t.zeros(self.batch, dtype=t.int32, device=ctx.device)
+        rc = ctx.L.mpf_getdet_vbatched(ctx.h, self.h, _ptr(self._flat(LU, "getdet")), _ptr(self._pivots(ipiv)), _ptr(mant), _ptr(expo))
+        ctx._check(rc, "mpf_getdet_vbatched")
+        return mant, expo
+
+    def _raise_singular(self, what, infos):
+        for inf in infos:
+            bad = self.ctx.torch.nonzero(inf)
+            if bad.numel():
+                b = int(bad[0])
+                raise MPFError(f"{what}: matrix {b} of the batch is singular (zero pivot {int(inf[b])})")
+
+    def solve(self, A, B, trans=False):
+        """X = D^-1 B (or D^-T B) for the matrices in the flat tensor A: getrf on a copy, then getrs.  Raises MPFError naming the first
+        singular matrix."""
+        LU, ipiv, info = self.getrf(A)
+        self._raise_singular("solve_batched", (info,))
+        return self.getrs(LU, ipiv, B, trans=trans)
+
+    def inv(self, A):
+        """The inverses of the matrices in the flat tensor A, flat in this layout: getrf on a copy, then getri.  Raises MPFError naming
+        the first singular matrix."""
+        LU, ipiv, info = self.getrf(A)
+        X, info2 = self.getri(LU, ipiv)
+        self._raise_singular("inv_batched", (info, info2))
+        return X
+
+    def slogdet(self, A_or_LU, ipiv=None):
+        """(sign, log|det A[b]|) as MPFContext.slogdet_batched returns them, device tensors of (batch,).  ipiv=None: A_or_LU holds the
+        matrices, and a copy is factored first; otherwise it holds getrf's factors."""
+        import math
+        t = self.ctx.torch
+        if ipiv is None:
+            A_or_LU, ipiv, _ = self.getrf(A_or_LU)
+        mant, expo = self.getdet(A_or_LU, ipiv)
+        sign = t.where(t.isnan(mant), mant, t.sign(mant))
+        return sign, t.log(t.abs(mant)) + expo.to(t.float64) * math.log(2.0)

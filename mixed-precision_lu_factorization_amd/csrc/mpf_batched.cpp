@@ -5,7 +5,19 @@
 //   mpf_getdet_batched  the determinant from those factors as mant 2^expo, mpf_getdet's order per matrix
 // The argument checks, the chunks of a batch longer than one grid and the error text; kernels and form choice in batched.hip; the
 // contracts are in include/mpf_c.h.
+// The same four for matrices of different orders (mpf_*_vbatched) on a descriptor, mpf_vbatch: the host plan of vbatch_plan.h (checks,
+// prefix sums, size classes) uploaded once; each call then launches one ragged kernel of vbatched.hip per class that is not empty.
 #include "mpf_internal.h"
+#include "vbatch_plan.h"
+#include <memory>
+
+// n, off, ld, offV by matrix and the class lists, on the host (the plan) and on the device
+struct mpf_vbatch {
+    mpf_ctx *ctx = nullptr;
+    vbatch::Plan plan;
+    Buf<int32_t> d_n, d_list;
+    Buf<int64_t> d_off, d_ld, d_offv;
+};
 
 namespace {
 constexpr int32_t BATCHED_MAXN = 128;
@@ -111,6 +123,160 @@ int mpf_getdet_batched(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t str
         if (rc) return rc;
     }
     return 0;
+}
+
+// ---- variable sizes -------------------------------------------------------------------------------------------------------------------
+int mpf_vbatch_create(mpf_ctx *c, int64_t batch, const int32_t *n, const int64_t *ld, const int64_t *off, mpf_vbatch **out) {
+    if (!c) return -1;
+    if (!out) { c->err = "vbatch_create: null pointer (out)"; return -1; }
+    *out = nullptr;
+    std::unique_ptr<mpf_vbatch> vb(new mpf_vbatch);
+    vb->ctx = c;
+    if (vbatch::plan(batch, n, ld, off, vb->plan, c->err)) return -1;
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    if (batch > 0) {
+        const vbatch::Plan &p = vb->plan;
+        MPF_HIP_TRY(c, vb->d_n.grow(batch));
+        MPF_HIP_TRY(c, vb->d_list.grow(batch));
+        MPF_HIP_TRY(c, vb->d_off.grow(batch));
+        MPF_HIP_TRY(c, vb->d_ld.grow(batch));
+        MPF_HIP_TRY(c, vb->d_offv.grow(batch));
+        // synchronous copies: complete before any later launch on any stream, and the plan's vectors need not be pinned
+        MPF_HIP_TRY(c, hipMemcpy(vb->d_n.get(), p.n.data(), (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice));
+        MPF_HIP_TRY(c, hipMemcpy(vb->d_list.get(), p.list.data(), (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice));
+        MPF_HIP_TRY(c, hipMemcpy(vb->d_off.get(), p.off.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice));
+        MPF_HIP_TRY(c, hipMemcpy(vb->d_ld.get(), p.ld.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice));
+        MPF_HIP_TRY(c, hipMemcpy(vb->d_offv.get(), p.offv.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    *out = vb.release();
+    return 0;
+}
+
+void mpf_vbatch_destroy(mpf_vbatch *vb) {
+    if (!vb) return;
+    if (vb->ctx) {   // launches that read the descriptor's device arrays may still be in flight
+        (void)hipSetDevice(vb->ctx->device);
+        (void)hipStreamSynchronize(vb->ctx->stream);
+    }
+    delete vb;
+}
+
+int mpf_vbatch_info(const mpf_vbatch *vb, int64_t *batch, int64_t *total_n, int64_t *extent) {
+    if (!vb) return -1;
+    if (batch) *batch = vb->plan.batch;
+    if (total_n) *total_n = vb->plan.total_n;
+    if (extent) *extent = vb->plan.extent;
+    return 0;
+}
+
+int mpf_vbatch_offsets(const mpf_vbatch *vb, int64_t *offM, int64_t *offV) {
+    if (!vb) return -1;
+    if (offM) std::copy(vb->plan.off.begin(), vb->plan.off.end(), offM);
+    if (offV) std::copy(vb->plan.offv.begin(), vb->plan.offv.end(), offV);
+    return 0;
+}
+
+} // extern "C"
+
+namespace {
+// what every vbatched entry point asks first
+int vb_enter(mpf_ctx *c, const mpf_vbatch *vb, const char *who) {
+    if (!vb) { c->err = std::string(who) + ": null pointer (descriptor)"; return -1; }
+    if (vb->ctx != c) { c->err = std::string(who) + ": the descriptor belongs to another context"; return -1; }
+    return 0;
+}
+// f(list + i0, count, top, nmax) for every chunk of every class that is not empty
+template <class F>
+int vb_classes(const mpf_vbatch *vb, F f) {
+    const vbatch::Plan &p = vb->plan;
+    for (int k = 0; k < vbatch::NCLASS; ++k)
+        for (int64_t i0 = 0; i0 < p.count[k]; i0 += BT_MAX_LAUNCH) {
+            const int64_t nb = p.count[k] - i0 < BT_MAX_LAUNCH ? p.count[k] - i0 : BT_MAX_LAUNCH;
+            const int rc = f(vb->d_list.get() + p.start[k] + i0, nb, vbatch::CLASS_TOP[k], p.nmax[k]);
+            if (rc) return rc;
+        }
+    return 0;
+}
+// the matrices of order 0: info = 0, determinant (0.5, 1)
+int vb_empty(mpf_ctx *c, const mpf_vbatch *vb, int32_t *info, double *mant, int32_t *expo) {
+    for (int64_t i0 = 0; i0 < vb->plan.zeros; i0 += BT_MAX_LAUNCH) {
+        const int64_t nb = vb->plan.zeros - i0 < BT_MAX_LAUNCH ? vb->plan.zeros - i0 : BT_MAX_LAUNCH;
+        const int rc = launch_vbatched_empty(c, vb->d_list.get() + i0, nb, info, mant, expo);
+        if (rc) return rc;
+    }
+    return 0;
+}
+BtRagged vb_arrays(const mpf_vbatch *vb) { return BtRagged{vb->d_n.get(), vb->d_off.get(), vb->d_ld.get(), vb->d_offv.get()}; }
+} // namespace
+
+extern "C" {
+
+int mpf_getrf_vbatched(mpf_ctx *c, const mpf_vbatch *vb, double *d_A, int32_t *d_ipiv, int32_t *d_info, int32_t fused) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "getrf_vbatched");
+    if (rc) return rc;
+    if (vb->plan.batch == 0) return 0;
+    if (vb->plan.total_n > 0 && (!d_A || !d_ipiv)) { c->err = "getrf_vbatched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    rc = vb_empty(c, vb, d_info, nullptr, nullptr);
+    if (rc) return rc;
+    const BtRagged v = vb_arrays(vb);
+    return vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
+        return launch_getrf_vbatched(c, v, idx, count, top, nmax, d_A, d_ipiv, d_info, fused != 0);
+    });
+}
+
+int mpf_getrs_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const double *d_LU, const int32_t *d_ipiv, int32_t nrhs, double *d_B,
+                       int64_t ldb) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "getrs_vbatched");
+    if (rc) return rc;
+    if (nrhs < 0) { c->err = "getrs_vbatched: nrhs must not be negative"; return -1; }
+    if (trans != 0 && trans != 1) { c->err = "getrs_vbatched: trans must be 0 or 1"; return -1; }
+    if (vb->plan.batch == 0 || vb->plan.total_n == 0 || nrhs == 0) return 0;
+    if (ldb < vb->plan.total_n) { c->err = "getrs_vbatched: leading dimension of B < total_n"; return -1; }
+    if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs_vbatched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const BtRagged v = vb_arrays(vb);
+    return vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
+        return launch_getrs_vbatched(c, v, idx, count, top, nmax, trans, d_LU, d_ipiv, nrhs, d_B, ldb);
+    });
+}
+
+int mpf_getri_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_LU, const int32_t *d_ipiv, double *d_inv, int32_t *d_info) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "getri_vbatched");
+    if (rc) return rc;
+    if (vb->plan.batch == 0) return 0;
+    if (vb->plan.total_n > 0) {
+        if (!d_LU || !d_ipiv || !d_inv) { c->err = "getri_vbatched: null pointer"; return -1; }
+        // the factors are still being read while the result is stored (mpf_getri_batched's rule, on the two operands' extents)
+        const uintptr_t a0 = (uintptr_t)d_LU, a1 = a0 + (size_t)vb->plan.extent * sizeof(double);
+        const uintptr_t b0 = (uintptr_t)d_inv, b1 = b0 + (size_t)vb->plan.extent * sizeof(double);
+        if (a0 < b1 && b0 < a1) { c->err = "getri_vbatched: d_inv overlaps d_LU (the inverse is formed out of place)"; return -1; }
+    }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    rc = vb_empty(c, vb, d_info, nullptr, nullptr);
+    if (rc) return rc;
+    const BtRagged v = vb_arrays(vb);
+    return vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
+        return launch_getri_vbatched(c, v, idx, count, top, nmax, d_LU, d_ipiv, d_inv, d_info);
+    });
+}
+
+int mpf_getdet_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_LU, const int32_t *d_ipiv, double *d_mant, int32_t *d_expo) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "getdet_vbatched");
+    if (rc) return rc;
+    if (vb->plan.batch == 0) return 0;
+    if (!d_mant || !d_expo || (vb->plan.total_n > 0 && (!d_LU || !d_ipiv))) { c->err = "getdet_vbatched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    rc = vb_empty(c, vb, nullptr, d_mant, d_expo);
+    if (rc) return rc;
+    const BtRagged v = vb_arrays(vb);
+    return vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
+        return launch_getdet_vbatched(c, v, idx, count, top, d_LU, d_ipiv, d_mant, d_expo);
+    });
 }
 
 } // extern "C"

@@ -279,7 +279,7 @@ inline int fail(mpf_ctx *c, int code, const std::string &msg) {
     return code;
 }
 
-enum { ATTR_HP = 1, ATTR_DGEMM = 2, ATTR_HGEMM = 4, ATTR_HGEMM256 = 8, ATTR_HGEMM_PP = 16, ATTR_HGEMM16_BIG32 = 32, ATTR_HGEMM16_BIG64 = 64, ATTR_BATCHED = 128 };
+enum { ATTR_HP = 1, ATTR_DGEMM = 2, ATTR_HGEMM = 4, ATTR_HGEMM256 = 8, ATTR_HGEMM_PP = 16, ATTR_HGEMM16_BIG32 = 32, ATTR_HGEMM16_BIG64 = 64, ATTR_BATCHED = 128, ATTR_VBATCHED = 256 };
 inline bool safe_pivots(const mpf_ctx *c) { return c->tune.safe_pivots != 0; }
 
 // ---- launchers implemented in the .hip files (all asynchronous on `s`) -----------------------
@@ -526,6 +526,21 @@ int launch_getri_batched(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t str
                          double *inv, int64_t ldinv, int64_t strideInv, int *info);
 int launch_getdet_batched(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv, int64_t strideP,
                           double *mant, int *expo);
+// The same for matrices of different orders (vbatched.hip; descriptor and chunks in mpf_batched.cpp, host plan in vbatch_plan.h): one
+// launch each on `count` <= BT_MAX_LAUNCH entries of one class list.  BtRagged: the descriptor's device arrays, indexed by matrix;
+// idx[i] = the matrix of list entry i; top = the class's largest order (8, 16, 32: wave forms; 48, 64, 96, 128: workgroup forms),
+// nmax = the largest order in the list (sizes the dynamic LDS).  The vectors (ipiv, B's rows) lie at offv[b].
+struct BtRagged { const int32_t *n; const int64_t *off, *ld, *offv; };
+int launch_getrf_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int top, int nmax, double *A, int *ipiv, int *info,
+                          int fused);
+int launch_getrs_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int top, int nmax, int trans, const double *LU,
+                          const int *ipiv, int nrhs, double *B, int64_t ldb);
+int launch_getri_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int top, int nmax, const double *LU,
+                          const int *ipiv, double *inv, int *info);
+int launch_getdet_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int top, const double *LU, const int *ipiv,
+                           double *mant, int *expo);
+// the matrices of order 0: info[b] = 0 (when info is not null), (mant[b], expo[b]) = (0.5, 1) (when mant is not null)
+int launch_vbatched_empty(mpf_ctx *c, const int32_t *idx, int64_t count, int *info, double *mant, int *expo);
 // mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
 int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 
