@@ -754,6 +754,34 @@ int mpf_getdet_batched(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t s
                        const int32_t *d_ipiv, int64_t strideP,
                        double *d_mant, int32_t *d_expo /* device, batch each */);
 
+/* ---- the same for ONE order up to 1024 (blocked; csrc/batched_blocked.hip) ----------------------------------------------------------------
+ * mpf_getrf_batched and mpf_getrs_batched above stop at n = 128, where a matrix still fits one workgroup's LDS, and stay as they are.
+ * These two take 0 <= n <= 1024 with the same layout, argument checks, error style and asynchrony; fp64 only, one n per call, no
+ * inverse, determinant or refinement above 128, no driver uses them, and the vbatched descriptor below stays at n <= 128.
+ *
+ * Factorization.  mpf_getrf_batched's contract, word for word, with the larger limit: for every b, A[b], ipiv[b][0 .. n-1] and
+ * d_info[b] equal, bit for bit, what mpf_dgetf2_piv(ctx, A[b], lda, n, n, fused, 0, ...) leaves; for n <= 128 that is also
+ * mpf_getrf_batched's result.  The kernels are a right-looking blocked LU -- panel (mpf_dgetf2_piv's rule), the panel's interchanges
+ * outside it, the U row block by forward substitution with k ascending, the trailing update with k ascending (fused = 1: a chain of
+ * v_mfma_f64_16x16x4_f64, contract C5; fused = 0: a rounded product and a rounded difference) -- which applies to every element the
+ * updates of contract C3 in their order, whatever the panel width (tests/batched_blocked_model.py restates the loop and checks it
+ * against the unblocked model).  So a matrix's bits depend on nothing but the matrix and `fused`: not on batch, position, lda, the
+ * strides, the panel width (option batched_blocked_nb: 8, 16, 32, or 0 = automatic) or the path (option batched_blocked_min_n,
+ * default 129: smaller n are handed to mpf_getrf_batched; 0 sends every n through the blocked kernels).  Rows n .. lda-1 and the
+ * bytes between matrices are neither written nor read.  Three ordinary launches per panel step for the whole batch: no kernel waits
+ * for another workgroup, no bounded spin, no co-residency requirement.
+ * Returns 0, or < 0 with a message: -1 for n > 1024 (use mpf_factor_dev), negative sizes, lda < n, strides too small, NULL d_A or
+ * d_ipiv.  n == 0 or batch == 0: returns 0, no work, nothing written.  Asynchronous on the context's stream. */
+int mpf_getrf_batched_blocked(mpf_ctx *ctx, double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                              int32_t *d_ipiv, int64_t strideP, int32_t *d_info /* optional */, int32_t fused);
+/* mpf_getrs_batched's chains, element orders and layout (above; tests/batched_model.py: getrs_model) for n <= 1024: always unfused,
+ * trans = 0 or 1, in place on B, rows n .. ldb-1 untouched.  Columns do not read each other: a column solved alone gives the same
+ * bits, as does any tiling of the columns.  n below option batched_blocked_min_n (and <= 128) is handed to mpf_getrs_batched.
+ * Returns 0, or < 0 with a message (n > 1024: use mpf_factor_dev and mpf_getrs; the other cases as there).  n == 0, batch == 0 or
+ * nrhs == 0: returns 0, no work.  Asynchronous on the context's stream. */
+int mpf_getrs_batched_blocked(mpf_ctx *ctx, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                              const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB);
+
 /* ---- the same for matrices of DIFFERENT orders (vbatched; csrc/vbatched.hip, host plan in csrc/vbatch_plan.h) ---------------------------
  * One descriptor says where `batch` matrices of orders 0 <= n[b] <= 128 lie inside ONE allocation; four entry points then factor, solve,
  * invert and take determinants of all of them in a handful of ordinary launches (one per size class that is not empty).  For every b the

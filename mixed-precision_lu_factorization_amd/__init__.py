@@ -39,6 +39,7 @@ C_ABI_SYMBOLS = [
     "mpf_getri", "mpf_getdet",
     "mpf_getrf_batched", "mpf_getrs_batched",
     "mpf_getri_batched", "mpf_getdet_batched",
+    "mpf_getrf_batched_blocked", "mpf_getrs_batched_blocked",
     "mpf_vbatch_create", "mpf_vbatch_destroy", "mpf_vbatch_info", "mpf_vbatch_offsets",
     "mpf_getrf_vbatched", "mpf_getrs_vbatched", "mpf_getri_vbatched", "mpf_getdet_vbatched",
 ]
@@ -211,6 +212,8 @@ def load_library(probe=False):
     L.mpf_getrf_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, i32]
     L.mpf_getrs_batched.argtypes = [vp, i32, vp, i64, i64, i32, i64, vp, i64, i32, vp, i64, i64]
     L.mpf_getri_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, i64, i64, vp]
+    L.mpf_getrf_batched_blocked.argtypes = L.mpf_getrf_batched.argtypes
+    L.mpf_getrs_batched_blocked.argtypes = L.mpf_getrs_batched.argtypes
     L.mpf_getdet_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, vp]
     L.mpf_vbatch_create.argtypes = [vp, i64, vp, vp, vp, C.POINTER(vp)]
     L.mpf_vbatch_destroy.argtypes = [vp]
@@ -1070,11 +1073,14 @@ class MPFContext:
         needs A's matrices column-major -- any other layout, torch's row-major default included, is copied), ipiv int32 (batch, n),
         1-based, info int32 (batch,) on the device: the first zero pivot of each matrix or 0.  ipiv / info: tensors to receive them
         (ipiv rows may be padded: stride(1) == 1, stride(0) >= n)."""
+        return self._getrf_batched(A, fused, overwrite, ipiv, info, "getrf_batched")
+
+    def _getrf_batched(self, A, fused, overwrite, ipiv, info, entry):
         self._bind()
         t = self.torch
         assert A.dim() == 3 and A.shape[1] == A.shape[2], "A: (batch, n, n)"
         batch, n = A.shape[0], A.shape[1]
-        LU, lda, stride = self._batch_arg(A, "getrf_batched", overwrite)
+        LU, lda, stride = self._batch_arg(A, entry, overwrite)
         if ipiv is None:
             ipiv = t.zeros((batch, n), dtype=t.int32, device=self.device)
         if info is None:
@@ -1082,28 +1088,31 @@ class MPFContext:
         assert ipiv.dtype == t.int32 and ipiv.is_cuda and ipiv.shape == (batch, n) and (n <= 1 or ipiv.stride(1) == 1)
         assert info.dtype == t.int32 and info.is_cuda and info.shape == (batch,) and info.is_contiguous()
         sp = ipiv.stride(0) if batch > 1 else max(n, 1)
-        rc = self.L.mpf_getrf_batched(self.h, _ptr(LU), lda, stride, n, batch, _ptr(ipiv), sp, _ptr(info), int(bool(fused)))
-        self._check(rc, "mpf_getrf_batched")
+        rc = getattr(self.L, "mpf_" + entry)(self.h, _ptr(LU), lda, stride, n, batch, _ptr(ipiv), sp, _ptr(info), int(bool(fused)))
+        self._check(rc, "mpf_" + entry)
         return LU, ipiv, info
 
     def getrs_batched(self, LU, ipiv, B, trans=False, overwrite=False):
         """mpf_getrs_batched: X[b] = A[b]^-1 B[b] (or A[b]^-T B[b]) with the factors of getrf_batched; B is (batch, n, nrhs), or
         (batch, n) for one right-hand side each.  Returns a new column-major X and leaves B untouched, unless overwrite=True: then B
         itself (column-major matrices) is solved in place and returned."""
+        return self._getrs_batched(LU, ipiv, B, trans, overwrite, "getrs_batched")
+
+    def _getrs_batched(self, LU, ipiv, B, trans, overwrite, entry):
         self._bind()
         t = self.torch
         if B.dim() == 2:
-            return self.getrs_batched(LU, ipiv, B.unsqueeze(2), trans, overwrite).squeeze(2)
+            return self._getrs_batched(LU, ipiv, B.unsqueeze(2), trans, overwrite, entry).squeeze(2)
         assert LU.dim() == 3 and LU.shape[1] == LU.shape[2] and B.dim() == 3 and B.shape[:2] == LU.shape[:2], "LU: (batch, n, n), B: (batch, n, nrhs)"
         batch, n, nrhs = B.shape
-        LUm, ldlu, slu = self._batch_arg(LU, "getrs_batched", False, copy=False)
+        LUm, ldlu, slu = self._batch_arg(LU, entry, False, copy=False)
         assert ipiv.dtype == t.int32 and ipiv.is_cuda and ipiv.shape == (batch, n)
         if n > 1 and ipiv.stride(1) != 1:
             ipiv = ipiv.contiguous()
         sp = ipiv.stride(0) if batch > 1 else max(n, 1)
-        X, ldb, sb = self._batch_arg(B, "getrs_batched", overwrite)
-        rc = self.L.mpf_getrs_batched(self.h, int(bool(trans)), _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, nrhs, _ptr(X), ldb, sb)
-        self._check(rc, "mpf_getrs_batched")
+        X, ldb, sb = self._batch_arg(B, entry, overwrite)
+        rc = getattr(self.L, "mpf_" + entry)(self.h, int(bool(trans)), _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, nrhs, _ptr(X), ldb, sb)
+        self._check(rc, "mpf_" + entry)
         return X
 
     def solve_batched(self, A, B, trans=False):
@@ -1115,6 +1124,27 @@ class MPFContext:
             b = int(bad[0])
             raise MPFError(f"solve_batched: matrix {b} of the batch is singular (zero pivot {int(info[b])})")
         return self.getrs_batched(LU, ipiv, B, trans=trans)
+
+    # ---- the same for one order up to 1024 (include/mpf_c.h: mpf_getrf_batched_blocked, mpf_getrs_batched_blocked) ------------------------
+    def getrf_batched_blocked(self, A, fused=False, overwrite=False, ipiv=None, info=None):
+        """mpf_getrf_batched_blocked: getrf_batched for n <= 1024 -- the same arguments, layout handling, results and bits (a
+        right-looking blocked LU, three launches per panel step for the whole batch).  Options batched_blocked_min_n (smaller n go to
+        getrf_batched's kernels) and batched_blocked_nb (panel width) change no bit."""
+        return self._getrf_batched(A, fused, overwrite, ipiv, info, "getrf_batched_blocked")
+
+    def getrs_batched_blocked(self, LU, ipiv, B, trans=False, overwrite=False):
+        """mpf_getrs_batched_blocked: getrs_batched for n <= 1024 with the factors of getrf_batched_blocked."""
+        return self._getrs_batched(LU, ipiv, B, trans, overwrite, "getrs_batched_blocked")
+
+    def solve_batched_blocked(self, A, B, trans=False):
+        """X[b] = A[b]^-1 B[b] (or A[b]^-T B[b]) for a (batch, n, n) tensor A, n <= 1024: getrf_batched_blocked on a copy, then
+        getrs_batched_blocked.  Raises MPFError naming the first singular matrix."""
+        LU, ipiv, info = self.getrf_batched_blocked(A)
+        bad = self.torch.nonzero(info)
+        if bad.numel():
+            b = int(bad[0])
+            raise MPFError(f"solve_batched_blocked: matrix {b} of the batch is singular (zero pivot {int(info[b])})")
+        return self.getrs_batched_blocked(LU, ipiv, B, trans=trans)
 
     def _batch_factors(self, LU, ipiv, what):
         """(LU, ldlu, strideLU, ipiv, strideP, batch, n) of a batch of factors as the library reads them (LU is copied only when its

@@ -5,6 +5,8 @@
 //   mpf_getdet_batched  the determinant from those factors as mant 2^expo, mpf_getdet's order per matrix
 // The argument checks, the chunks of a batch longer than one grid and the error text; kernels and form choice in batched.hip; the
 // contracts are in include/mpf_c.h.
+//   mpf_getrf_batched_blocked, mpf_getrs_batched_blocked   the first two for one n <= 1024: the same bits from a right-looking blocked
+//                       loop (batched_blocked.hip), three launches per panel step for the whole batch
 // The same four for matrices of different orders (mpf_*_vbatched) on a descriptor, mpf_vbatch: the host plan of vbatch_plan.h (checks,
 // prefix sums, size classes) uploaded once; each call then launches one ragged kernel of vbatched.hip per class that is not empty.
 #include "mpf_internal.h"
@@ -32,6 +34,16 @@ int check_sizes(mpf_ctx *c, const char *who, int32_t n, int64_t batch, int64_t s
     if (n < 0 || batch < 0) { c->err = std::string(who) + ": n and batch must not be negative"; return -1; }
     if (n > BATCHED_MAXN) {
         c->err = std::string(who) + ": n > 128 is not a small matrix: factor it with mpf_factor_dev (and solve with mpf_getrs)";
+        return -1;
+    }
+    if (batch > 1 && strideP < n) { c->err = std::string(who) + ": stride of ipiv < n"; return -1; }
+    return 0;
+}
+// the same for the blocked entry points: n <= 1024
+int check_sizes_blocked(mpf_ctx *c, const char *who, int32_t n, int64_t batch, int64_t strideP) {
+    if (n < 0 || batch < 0) { c->err = std::string(who) + ": n and batch must not be negative"; return -1; }
+    if (n > BB_MAXN) {
+        c->err = std::string(who) + ": n > 1024 is not a batch-sized matrix: factor it with mpf_factor_dev (and solve with mpf_getrs)";
         return -1;
     }
     if (batch > 1 && strideP < n) { c->err = std::string(who) + ": stride of ipiv < n"; return -1; }
@@ -120,6 +132,58 @@ int mpf_getdet_batched(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t str
     for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
         const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
         rc = launch_getdet_batched(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0, d_expo + b0);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---- blocked: one n <= 1024 per call ------------------------------------------------------------------------------------------------------
+// The checks are check_sizes' and check_strided's with the larger limit; n below option batched_blocked_min_n (and <= 128) goes to the
+// entry points above, whose bits are the same by contract.
+int mpf_getrf_batched_blocked(mpf_ctx *c, double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t *d_ipiv,
+                              int64_t strideP, int32_t *d_info, int32_t fused) {
+    if (!c) return -1;
+    int rc = check_sizes_blocked(c, "getrf_batched_blocked", n, batch, strideP);
+    if (rc) return rc;
+    if (n == 0 || batch == 0) return 0;
+    rc = check_strided(c, "getrf_batched_blocked", "A", lda, strideA, n, n, batch);
+    if (rc) return rc;
+    if (!d_A || !d_ipiv) { c->err = "getrf_batched_blocked: null pointer"; return -1; }
+    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n) return mpf_getrf_batched(c, d_A, lda, strideA, n, batch, d_ipiv, strideP, d_info, fused);
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    int valu = 0, stages = 7;
+#ifdef MPF_PROBE
+    valu = c->tune.batched_blocked_valu;
+    stages = c->tune.batched_blocked_stages;
+#endif
+    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
+        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
+        rc = launch_getrf_batched_blocked(c, d_A + b0 * strideA, lda, strideA, n, nb, d_ipiv + b0 * strideP, strideP,
+                                          d_info ? d_info + b0 : nullptr, fused != 0, c->tune.batched_blocked_nb, valu, stages);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_getrs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                              const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB) {
+    if (!c) return -1;
+    int rc = check_sizes_blocked(c, "getrs_batched_blocked", n, batch, strideP);
+    if (rc) return rc;
+    if (nrhs < 0) { c->err = "getrs_batched_blocked: nrhs must not be negative"; return -1; }
+    if (trans != 0 && trans != 1) { c->err = "getrs_batched_blocked: trans must be 0 or 1"; return -1; }
+    if (n == 0 || batch == 0 || nrhs == 0) return 0;
+    rc = check_strided(c, "getrs_batched_blocked", "LU", ldlu, strideLU, n, n, batch);
+    if (!rc) rc = check_strided(c, "getrs_batched_blocked", "B", ldb, strideB, n, nrhs, batch);
+    if (rc) return rc;
+    if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs_batched_blocked: null pointer"; return -1; }
+    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
+        return mpf_getrs_batched(c, trans, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, nrhs, d_B, ldb, strideB);
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
+        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
+        rc = launch_getrs_batched_blocked(c, trans, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, nrhs,
+                                          d_B + b0 * strideB, ldb, strideB);
         if (rc) return rc;
     }
     return 0;

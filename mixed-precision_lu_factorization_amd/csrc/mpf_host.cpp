@@ -67,7 +67,11 @@ const OptDesc kOpts[] = {
     OPT_L(host_sink_min_n, "MPF_HOST_SINK_MIN_N", 0, 1ll << 40),
     OPT_I(dist_solve_p2p, "MPF_DIST_SOLVE_P2P", 0, 1),
     OPT_I(gmres_group_tiles, "MPF_GMRES_GROUP_TILES", 0, 16),
+    OPT_I(batched_blocked_min_n, "MPF_BATCHED_BLOCKED_MIN_N", 0, 1025),
+    OPT_I(batched_blocked_nb, "MPF_BATCHED_BLOCKED_NB", 0, 32),
 #ifdef MPF_PROBE
+    OPT_I(batched_blocked_valu, "MPF_BATCHED_BLOCKED_VALU", 0, 1),
+    OPT_I(batched_blocked_stages, "MPF_BATCHED_BLOCKED_STAGES", 0, 7),
     OPT_I(hp_stamp, "MPF_HP_STAMP", 0, 1),
     OPT_I(hp_r256_upto, "MPF_HP_R256_UPTO", 0, 1 << 30),
     OPT_I(dgemm_w8, "MPF_DGEMM_W8", 0, 1),

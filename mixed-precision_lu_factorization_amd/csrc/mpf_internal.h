@@ -125,7 +125,12 @@ struct MpfTuning {
     int gmres_group_tiles = 0;           // MPF_GMRES_GROUP_TILES: 32-column tiles mpf_solve_gmres_ir_block takes through the device together: n >= 1 exactly n
                                          // (at most 16), 0 = automatic -- the most (<= 16, >= 1) whose restart + 1 basis sets and six working sets fit in
                                          // 2 GiB.  The results do not depend on it (every column's arithmetic is its own)
+    int batched_blocked_min_n = 129;     // MPF_BATCHED_BLOCKED_MIN_N: mpf_getrf_batched_blocked / mpf_getrs_batched_blocked hand matrices of n below this (and <= 128)
+                                         // to the one-workgroup kernels of batched.hip (same bits by contract); 0: every n through the blocked kernels
+    int batched_blocked_nb = 0;          // MPF_BATCHED_BLOCKED_NB: panel width of the blocked batched LU: 8, 16 or 32; 0 (or any other value) = automatic.  Same bits
 #ifdef MPF_PROBE                         // libmpf_probe.so only (tools/): measured-slower variants and diagnostics
+    int batched_blocked_valu = 0;        // MPF_BATCHED_BLOCKED_VALU=1: the blocked batched LU's fused trailing update on the VALU kernel instead of the MFMA one (cross-check)
+    int batched_blocked_stages = 7;      // MPF_BATCHED_BLOCKED_STAGES: stages the blocked batched LU launches, bit 0 panel, 1 row block, 2 update (per-stage timing; results wrong unless 7)
     int hp_stamp = 0;                    // MPF_HP_STAMP=1: cycle-stamped build of the pivot kernel
     int hp_r256_upto = 1 << 30;          // MPF_HP_R256_UPTO: panels above that many rows use 128-row workgroups
     int dgemm_w8 = 1;                    // MPF_DGEMM_W8=0: four-wave fp64 update kernel everywhere
@@ -541,6 +546,17 @@ int launch_getdet_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, in
                            double *mant, int *expo);
 // the matrices of order 0: info[b] = 0 (when info is not null), (mant[b], expo[b]) = (0.5, 1) (when mant is not null)
 int launch_vbatched_empty(mpf_ctx *c, const int32_t *idx, int64_t count, int *info, double *mant, int *expo);
+// Blocked LU of many matrices of 1 <= n <= 1024 (batched_blocked.hip; checks, chunks and forwarding in mpf_batched.cpp): at most
+// BB_MAX_LAUNCH matrices per call (the batch is a grid's second dimension).  launch_getrf_batched_blocked: the right-looking loop over
+// panels of nb = 8, 16 or 32 columns -- panel, row block, trailing update, each ONE launch for the whole batch; valu != 0: the fused
+// update on the VALU kernel; stages: bit 0 panel, 1 row block, 2 update (7 everywhere but in the probe library's per-stage timing).
+// launch_getrs_batched_blocked: launch_getrs_batched's chains, one workgroup per (matrix, column tile).
+constexpr int64_t BB_MAX_LAUNCH = 1 << 15;
+constexpr int BB_MAXN = 1024;
+int launch_getrf_batched_blocked(mpf_ctx *c, double *A, int64_t lda, int64_t strideA, int n, int64_t batch, int *ipiv, int64_t strideP,
+                                 int *info, int fused, int nb, int valu, int stages);
+int launch_getrs_batched_blocked(mpf_ctx *c, int trans, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch,
+                                 const int *ipiv, int64_t strideP, int nrhs, double *B, int64_t ldb, int64_t strideB);
 // mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
 int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 
