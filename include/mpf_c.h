@@ -756,8 +756,9 @@ int mpf_getdet_batched(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t s
 
 /* ---- the same for ONE order up to 1024 (blocked; csrc/batched_blocked.hip) ----------------------------------------------------------------
  * mpf_getrf_batched and mpf_getrs_batched above stop at n = 128, where a matrix still fits one workgroup's LDS, and stay as they are.
- * These two take 0 <= n <= 1024 with the same layout, argument checks, error style and asynchrony; fp64 only, one n per call, no
- * inverse, determinant or refinement above 128, no driver uses them, and the vbatched descriptor below stays at n <= 128.
+ * These take 0 <= n <= 1024 with the same layout, argument checks, error style and asynchrony, and mpf_getri_batched_blocked and
+ * mpf_getdet_batched_blocked below do the same for mpf_getri_batched and mpf_getdet_batched; fp64 only, one n per call, no refinement
+ * above 128, no driver uses them, and the vbatched descriptor below stays at n <= 128.
  *
  * Factorization.  mpf_getrf_batched's contract, word for word, with the larger limit: for every b, A[b], ipiv[b][0 .. n-1] and
  * d_info[b] equal, bit for bit, what mpf_dgetf2_piv(ctx, A[b], lda, n, n, fused, 0, ...) leaves; for n <= 128 that is also
@@ -781,6 +782,35 @@ int mpf_getrf_batched_blocked(mpf_ctx *ctx, double *d_A, int64_t lda, int64_t st
  * nrhs == 0: returns 0, no work.  Asynchronous on the context's stream. */
 int mpf_getrs_batched_blocked(mpf_ctx *ctx, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                               const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB);
+/* Inverse.  mpf_getri_batched's contract, word for word, with 0 <= n <= 1024: out of place (d_LU and d_ipiv are preserved; a d_inv
+ * batch whose address range overlaps the d_LU batch's is refused with -1), rows n .. ldinv-1 and the bytes between matrices neither
+ * written nor read.  For finite factors with no zero on U's diagonal inv[b] equals, bit for bit, mpf_getrs_batched_blocked(trans = 0)
+ * on B[b] = I (tests/batched_model.py: getrs_model(LU, ipiv, eye(n))); for n <= 128 that is also mpf_getri_batched's result.  Every
+ * step is unfused.  inv(A) = inv(U) inv(L) P: column k of the result is column q(k) of inv(L) -- q(k) the position row k reaches
+ * under the interchanges -- taken through the backward sweep, so the interchanges are no arithmetic: the workgroup that forms
+ * columns q .. q + ct - 1 of inv(L) stores them at columns k(q).  The forward sweep of a tile starts at the 32-row block that holds
+ * its smallest q (the steps before it subtract l (+0) from +0: +0 - (+-0) = +0); rows above a column's q are stored as +0; nothing
+ * is skipped in the backward sweep (tests/batched_blocked_inv_model.py restates the blocked algorithm).
+ * d_info[b] = i + 1 for the first u_ii == 0.0, else 0; such a matrix's inv[b] is left untouched whether or not d_info is given
+ * (every workgroup reads its matrix's diagonal before its first store; there is no workspace).  Non-finite factors: the values are
+ * not promised, every access stays in range (an ipiv entry outside 1 .. n reads as "no interchange") and no other matrix changes.
+ * A matrix's bits depend on nothing but its LU and ipiv: not on batch, position, any ld or stride, the tile width (option
+ * batched_blocked_inv_ct: 8, 16, or 0 = automatic) or the path (n <= 128 and n < option batched_blocked_min_n: handed to
+ * mpf_getri_batched).  One ordinary launch per 32768 matrices: no kernel waits for another workgroup.
+ * Returns 0, or < 0 with a message: -1 for n > 1024 (use mpf_factor_dev and mpf_getri), negative sizes, ld < n, strides too small,
+ * NULL d_LU, d_ipiv or d_inv, overlap.  n == 0 or batch == 0: returns 0, no work.  Asynchronous on the context's stream. */
+int mpf_getri_batched_blocked(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                              const int32_t *d_ipiv, int64_t strideP,
+                              double *d_inv, int64_t ldinv, int64_t strideInv, int32_t *d_info /* optional */);
+/* Determinant.  det(A[b]) = d_mant[b] * 2^d_expo[b] in mpf_getdet's order per matrix (no scales): for n <= 1024 up to four chunks of
+ * 256 consecutive diagonal entries, each from (1, 0) ascending, the chunk results combined ascending from (1, 0) by the same step;
+ * the sign flips once per ipiv[i] != i + 1 (tests/getri_model.py: getdet_model(diag(U), ipiv)) -- the bits of mpf_getdet on each
+ * matrix and, for n <= 128, of mpf_getdet_batched.  Any non-finite u_ii gives (NaN, 0), otherwise a zero gives (0, 0).  d_expo is
+ * int32 (|expo| <= 1024 * 1075).  Reads n of a matrix's n^2 doubles; one ordinary launch per 32768 matrices.  n <= 128 and n <
+ * option batched_blocked_min_n: handed to mpf_getdet_batched.  n == 0 or batch == 0: returns 0 and writes nothing.  Errors as above
+ * (n > 1024: use mpf_factor_dev and mpf_getdet). */
+int mpf_getdet_batched_blocked(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                               const int32_t *d_ipiv, int64_t strideP, double *d_mant, int32_t *d_expo);
 
 /* ---- the same for matrices of DIFFERENT orders (vbatched; csrc/vbatched.hip, host plan in csrc/vbatch_plan.h) ---------------------------
  * One descriptor says where `batch` matrices of orders 0 <= n[b] <= 128 lie inside ONE allocation; four entry points then factor, solve,

@@ -40,6 +40,7 @@ C_ABI_SYMBOLS = [
     "mpf_getrf_batched", "mpf_getrs_batched",
     "mpf_getri_batched", "mpf_getdet_batched",
     "mpf_getrf_batched_blocked", "mpf_getrs_batched_blocked",
+    "mpf_getri_batched_blocked", "mpf_getdet_batched_blocked",
     "mpf_vbatch_create", "mpf_vbatch_destroy", "mpf_vbatch_info", "mpf_vbatch_offsets",
     "mpf_getrf_vbatched", "mpf_getrs_vbatched", "mpf_getri_vbatched", "mpf_getdet_vbatched",
 ]
@@ -215,6 +216,8 @@ def load_library(probe=False):
     L.mpf_getrf_batched_blocked.argtypes = L.mpf_getrf_batched.argtypes
     L.mpf_getrs_batched_blocked.argtypes = L.mpf_getrs_batched.argtypes
     L.mpf_getdet_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, vp]
+    L.mpf_getri_batched_blocked.argtypes = L.mpf_getri_batched.argtypes
+    L.mpf_getdet_batched_blocked.argtypes = L.mpf_getdet_batched.argtypes
     L.mpf_vbatch_create.argtypes = [vp, i64, vp, vp, vp, C.POINTER(vp)]
     L.mpf_vbatch_destroy.argtypes = [vp]
     L.mpf_vbatch_destroy.restype = None
@@ -1163,57 +1166,89 @@ class MPFContext:
         out: a (batch, n, n) tensor of column-major matrices to receive the inverses (colmajor_batch; a new one when None); info:
         an int32 (batch,) device tensor.  Returns (inv, info): info[b] = i + 1 when u_ii is the first zero on U[b]'s diagonal --
         out[b] is then untouched -- else 0."""
+        return self._getri_batched(LU, ipiv, out, info, "getri_batched")
+
+    def _getri_batched(self, LU, ipiv, out, info, entry):
         self._bind()
         t = self.torch
-        LUm, ldlu, slu, ipiv, sp, batch, n = self._batch_factors(LU, ipiv, "getri_batched")
+        LUm, ldlu, slu, ipiv, sp, batch, n = self._batch_factors(LU, ipiv, entry)
         if out is None:
             out = self.colmajor_batch(batch, n, n)
         assert out.dim() == 3 and out.shape == (batch, n, n) and out.dtype == t.float64 and out.is_cuda
         lay = self._batch_layout(out)
         if lay is None:
-            raise MPFError("getri_batched: out needs column-major matrices (MPFContext.colmajor_batch)")
+            raise MPFError(f"{entry}: out needs column-major matrices (MPFContext.colmajor_batch)")
         if info is None:
             info = t.zeros(batch, dtype=t.int32, device=self.device)
         assert info.dtype == t.int32 and info.is_cuda and info.shape == (batch,) and info.is_contiguous()
-        rc = self.L.mpf_getri_batched(self.h, _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, _ptr(out), lay[0], lay[1], _ptr(info))
-        self._check(rc, "mpf_getri_batched")
+        rc = getattr(self.L, "mpf_" + entry)(self.h, _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, _ptr(out), lay[0], lay[1], _ptr(info))
+        self._check(rc, "mpf_" + entry)
         return out, info
 
     def getdet_batched(self, LU, ipiv):
         """mpf_getdet_batched: det(A[b]) = mant[b] * 2**expo[b] from the factors of getrf_batched, |mant| in [0.5, 1) or 0.  Returns
         (mant float64 (batch,), expo int32 (batch,)) on the device; (0, 0) for a singular U[b], (nan, 0) for a non-finite one."""
+        return self._getdet_batched(LU, ipiv, "getdet_batched")
+
+    def _getdet_batched(self, LU, ipiv, entry):
         self._bind()
         t = self.torch
-        LUm, ldlu, slu, ipiv, sp, batch, n = self._batch_factors(LU, ipiv, "getdet_batched")
+        LUm, ldlu, slu, ipiv, sp, batch, n = self._batch_factors(LU, ipiv, entry)
         mant = t.full((batch,), 0.5, dtype=t.float64, device=self.device)     # n == 0: the empty product, mpf_getdet's (0.5, 1)
         expo = t.ones(batch, dtype=t.int32, device=self.device)
-        rc = self.L.mpf_getdet_batched(self.h, _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, _ptr(mant), _ptr(expo))
-        self._check(rc, "mpf_getdet_batched")
+        rc = getattr(self.L, "mpf_" + entry)(self.h, _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, _ptr(mant), _ptr(expo))
+        self._check(rc, "mpf_" + entry)
         return mant, expo
 
     def inv_batched(self, A):
         """inv(A[b]) for a (batch, n, n) tensor A, n <= 128: getrf_batched on a copy, then getri_batched.  Raises MPFError naming the
         first singular matrix."""
-        LU, ipiv, info = self.getrf_batched(A)
-        X, info2 = self.getri_batched(LU, ipiv)
+        return self._inv_batched(A, "")
+
+    def _inv_batched(self, A, suffix):
+        LU, ipiv, info = getattr(self, "getrf_batched" + suffix)(A)
+        X, info2 = getattr(self, "getri_batched" + suffix)(LU, ipiv)
         for inf in (info, info2):
             bad = self.torch.nonzero(inf)
             if bad.numel():
                 b = int(bad[0])
-                raise MPFError(f"inv_batched: matrix {b} of the batch is singular (zero pivot {int(inf[b])})")
+                raise MPFError(f"inv_batched{suffix}: matrix {b} of the batch is singular (zero pivot {int(inf[b])})")
         return X
 
     def slogdet_batched(self, A_or_LU, ipiv=None):
         """(sign, log|det A[b]|) as torch.linalg.slogdet returns them, device tensors of (batch,): from getdet_batched,
         log|mant| + expo ln 2 -- one rounded logarithm per matrix.  (0, -inf) for a zero determinant, (nan, nan) for a non-finite one.
         ipiv=None: A_or_LU holds the matrices, and a copy is factored first; otherwise it holds getrf_batched's factors."""
+        return self._slogdet_batched(A_or_LU, ipiv, "")
+
+    def _slogdet_batched(self, A_or_LU, ipiv, suffix):
         import math
         t = self.torch
         if ipiv is None:
-            A_or_LU, ipiv, _ = self.getrf_batched(A_or_LU)
-        mant, expo = self.getdet_batched(A_or_LU, ipiv)
+            A_or_LU, ipiv, _ = getattr(self, "getrf_batched" + suffix)(A_or_LU)
+        mant, expo = getattr(self, "getdet_batched" + suffix)(A_or_LU, ipiv)
         sign = t.where(t.isnan(mant), mant, t.sign(mant))         # (sign(0) is 0; sign(nan) is not nan on every backend)
         return sign, t.log(t.abs(mant)) + expo.to(t.float64) * math.log(2.0)  # (expo is 0 beside log(0) = -inf and log(nan) = nan)
+
+    # ---- the same for one order up to 1024 (include/mpf_c.h: mpf_getri_batched_blocked, mpf_getdet_batched_blocked) -----------------------
+    def getri_batched_blocked(self, LU, ipiv, out=None, info=None):
+        """mpf_getri_batched_blocked: getri_batched for n <= 1024 with the factors of getrf_batched_blocked -- the same arguments,
+        results and bits (bit for bit getrs_batched_blocked on an identity that is never formed).  Options batched_blocked_min_n
+        (smaller n go to getri_batched's kernels) and batched_blocked_inv_ct (columns per workgroup) change no bit."""
+        return self._getri_batched(LU, ipiv, out, info, "getri_batched_blocked")
+
+    def getdet_batched_blocked(self, LU, ipiv):
+        """mpf_getdet_batched_blocked: getdet_batched for n <= 1024 (mpf_getdet's chunks of 256 per matrix)."""
+        return self._getdet_batched(LU, ipiv, "getdet_batched_blocked")
+
+    def inv_batched_blocked(self, A):
+        """inv(A[b]) for a (batch, n, n) tensor A, n <= 1024: getrf_batched_blocked on a copy, then getri_batched_blocked.  Raises
+        MPFError naming the first singular matrix."""
+        return self._inv_batched(A, "_blocked")
+
+    def slogdet_batched_blocked(self, A_or_LU, ipiv=None):
+        """slogdet_batched for n <= 1024: from getdet_batched_blocked (and getrf_batched_blocked when ipiv is None)."""
+        return self._slogdet_batched(A_or_LU, ipiv, "_blocked")
 
 
     # ---- the same for matrices of different orders (include/mpf_c.h: mpf_vbatch_create, mpf_getrf_vbatched, ...) --------------------------

@@ -567,10 +567,9 @@ __global__ __launch_bounds__(BT_T) void bt_getdet_kernel(const double *LU, long 
             zero |= u == 0.0;
             bad |= !(fabs(u) <= 1.7976931348623157e308);
             flips ^= pv[i] != i + 1 ? 1 : 0;
-            int ei, k;
+            int ei;
             const double m = frexp(u, &ei);
-            p = frexp(p * m, &k);
-            e += k + ei;
+            mpf_det_step(p, e, m, ei);
         }
     } else {
         const int lane = threadIdx.x & 63;
@@ -593,9 +592,7 @@ __global__ __launch_bounds__(BT_T) void bt_getdet_kernel(const double *LU, long 
         for (int i = 0; i < n; ++i) {
             const double mi = bt_bcast<2>(m, i);
             const int ei = i < 64 ? __builtin_amdgcn_readlane(ex[0], i) : __builtin_amdgcn_readlane(ex[1], i - 64);
-            int k;
-            p = frexp(p * mi, &k);
-            e += k + ei;
+            mpf_det_step(p, e, mi, ei);
         }
         if (lane != 0) return;
     }

@@ -1,5 +1,6 @@
 // Blocked LU of many matrices of order up to 1024 (mpf_getrf_batched_blocked, mpf_getrs_batched_blocked; contracts in
-// include/mpf_c.h, host side in mpf_batched.cpp).
+// include/mpf_c.h, host side in mpf_batched.cpp), and from its factors the inverse and the determinant
+// (mpf_getri_batched_blocked, mpf_getdet_batched_blocked; bb_getri_kernel and bb_getdet_kernel below).
 //
 // The numeric contract is batched.hip's, unchanged: mpf_dgetf2_piv on the whole n x n matrix.  Per element that is one update per k in
 // ascending order (contract C3), and for fused = 1 the update is c = fma(-l_ik, u_kj, c) -- the chain of v_mfma_f64_16x16x4_f64
@@ -356,6 +357,195 @@ __global__ __launch_bounds__(1024) void bb_getrs_kernel(int trans, const double 
     }
 }
 
+// ---- inverse ----------------------------------------------------------------------------------------------------------------------------
+// inv(A) = inv(U) inv(L) P: column k of the result is column q(k) of inv(L) taken through the backward sweep, so the interchanges are
+// no arithmetic -- the workgroup that owns columns q .. q + CT - 1 of inv(L) stores them at columns k(q) = map[q], bb_getrs_kernel's
+// composed map.  One workgroup per (matrix, tile of CT consecutive q), thread = row, the row's CT values in registers, both sweeps in
+// blocks of 32 rows as bb_sweep has them.  What differs from the solve:
+//   - the tile's columns start as e_q, never read; the forward sweep starts at the block that holds the tile's smallest q (the steps
+//     before it subtract l * (+0) from +0);
+//   - the 32 x 32 diagonal block is solved with lane = COLUMN: the block's rows go through LDS (xs, with the block's factor rows in
+//     ds), lane c of the block's wave takes column c in groups of BB_IG rows -- the terms of the rows already solved first, then the
+//     group's triangle -- with the factor elements as LDS broadcasts: one division per (row, column) instead of one per (row, column,
+//     lane), 496 multiply-subtract pairs per column instead of 32 x 32 selects;
+//   - the rows outside the block then apply its 32 steps in the chain's order, the factor elements BB_IG at a time.
+// Rows past n inside the last block publish zeros that the solve never writes back, and columns past n of the factors read as zero,
+// so the 32 steps of a block need no bound checks: x - 0 * 0 = x.  A zero on U's diagonal is found by every workgroup of the matrix
+// before its first store; such a workgroup returns, the tile-0 workgroup writes info.
+constexpr int BB_IG = 8;    // rows per register group of the diagonal solve
+constexpr int BB_UG = 16;   // factor elements per load group of the update
+template <int CT, bool ASC>
+__device__ __forceinline__ void bb_inv_sweep(const double *T, long long ld, int n, int t, bool valid, int kb0, double (&x)[CT],
+                                             double (*xs)[32][CT + 1], double (*ds)[32][33], int &ph) {
+    const int nblk = (n + 31) >> 5, lane = t & 63;
+    for (int s = ASC ? kb0 : 0; s < nblk; ++s, ++ph) {
+        const int kb = ASC ? s : nblk - 1 - s, r0 = kb * 32, buf = ph & 1, rr = t - r0;
+        const int cnt = n - r0 < 32 ? n - r0 : 32;
+        const bool mine = rr >= 0 && rr < 32;                       // (rows past n included: they publish zeros)
+        const bool part = valid && (ASC ? t >= r0 + 32 : t < r0);
+        if (mine) {
+#pragma unroll
+            for (int c = 0; c < CT; ++c) xs[buf][rr][c] = x[c];
+#pragma unroll 16
+            for (int j = 0; j < 32; ++j) ds[buf][rr][j] = (valid && j < cnt) ? T[t + (long long)(r0 + j) * ld] : 0.0;
+        }
+        __syncthreads();
+        if ((t >> 6) == (kb >> 1) && lane < CT) {                   // the block's wave, lane = column
+#pragma unroll 1
+            for (int gg = 0; gg < 32 / BB_IG; ++gg) {
+                const int i0 = (ASC ? gg : 32 / BB_IG - 1 - gg) * BB_IG;
+                if (i0 < cnt) {                                     // (uniform)
+                    double y[BB_IG];
+#pragma unroll
+                    for (int i = 0; i < BB_IG; ++i) y[i] = xs[buf][i0 + i][lane];
+                    if (ASC) {
+#pragma unroll 2
+                        for (int j = 0; j < i0; ++j) {              // (j < i0 < cnt)
+                            const double xj = xs[buf][j][lane];
+#pragma unroll
+                            for (int i = 0; i < BB_IG; ++i) { const double p = ds[buf][i0 + i][j] * xj; y[i] = y[i] - p; }
+                        }
+#pragma unroll
+                        for (int j = 0; j < BB_IG; ++j)
+#pragma unroll
+                            for (int i = j + 1; i < BB_IG; ++i) { const double p = ds[buf][i0 + i][i0 + j] * y[j]; y[i] = y[i] - p; }
+                    } else {
+#pragma unroll 2
+                        for (int j = cnt - 1; j >= i0 + BB_IG; --j) {
+                            const double xj = xs[buf][j][lane];
+#pragma unroll
+                            for (int i = 0; i < BB_IG; ++i) { const double p = ds[buf][i0 + i][j] * xj; y[i] = y[i] - p; }
+                        }
+#pragma unroll
+                        for (int j = BB_IG - 1; j >= 0; --j) {
+                            if (i0 + j < cnt) {                     // (uniform)
+                                y[j] = y[j] / ds[buf][i0 + j][i0 + j];
+#pragma unroll
+                                for (int i = 0; i < j; ++i) { const double p = ds[buf][i0 + i][i0 + j] * y[j]; y[i] = y[i] - p; }
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < BB_IG; ++i)
+                        if (i0 + i < cnt) xs[buf][i0 + i][lane] = y[i];
+                }
+            }
+        }
+        __syncthreads();
+        if (part) {
+#pragma unroll 1
+            for (int g = 0; g < 32 / BB_UG; ++g) {
+                const int j0 = (ASC ? g : 32 / BB_UG - 1 - g) * BB_UG;
+                double l[BB_UG];
+#pragma unroll
+                for (int j = 0; j < BB_UG; ++j) l[j] = j0 + j < cnt ? T[t + (long long)(r0 + j0 + j) * ld] : 0.0;
+#pragma unroll
+                for (int jj = 0; jj < BB_UG; ++jj) {
+                    const int j = ASC ? jj : BB_UG - 1 - jj;
+#pragma unroll
+                    for (int c = 0; c < CT; ++c) { const double p = l[j] * xs[buf][j0 + j][c]; x[c] = x[c] - p; }
+                }
+            }
+        } else if (mine && valid) {
+#pragma unroll
+            for (int c = 0; c < CT; ++c) x[c] = xs[buf][rr][c];
+        }
+    }
+}
+
+// blockDim.x = n rounded up to whole waves; blockIdx.x = tile of CT columns of inv(L), blockIdx.y = matrix
+template <int CT>
+__global__ __launch_bounds__(1024) void bb_getri_kernel(const double *LU, long long ldlu, long long strideLU, int n, const int *ipiv,
+                                                        long long strideP, double *inv, long long ldinv, long long strideInv, int *info) {
+    __shared__ int pv[BB_MAXN], map[BB_MAXN];
+    __shared__ double xs[2][32][CT + 1], ds[2][32][33];
+    __shared__ int zfirst;
+    const int t = threadIdx.x;
+    const long long b = blockIdx.y;
+    const int q0 = (int)blockIdx.x * CT;
+    const double *T = LU + b * strideLU;
+    const bool valid = t < n;
+    if (t == 0) zfirst = INT_MAX;
+    if (valid) {
+        int p = ipiv[b * strideP + t] - 1;
+        if (p < 0 || p >= n) p = t;                                 // (as bb_getrs_kernel: keeps every access in range)
+        pv[t] = p;
+    }
+    __syncthreads();
+    if (valid) {
+        int cpos = t;
+        for (int j = 0; j < n; ++j) { const int p = pv[j]; cpos = cpos == j ? p : (cpos == p ? j : cpos); }
+        map[cpos] = t;                                              // position cpos holds row t: column t of the result starts as e_cpos
+        if (T[t + (long long)t * ldlu] == 0.0) atomicMin(&zfirst, t + 1);
+    }
+    __syncthreads();
+    const int z = zfirst;
+    if (info && blockIdx.x == 0 && t == 0) info[b] = z == INT_MAX ? 0 : z;
+    if (z != INT_MAX) return;                                       // (the whole workgroup: nothing is stored)
+    double x[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) x[c] = (valid && t == q0 + c) ? 1.0 : 0.0;   // (columns past n: zeros, never stored)
+    int ph = 0;
+    bb_inv_sweep<CT, true>(T, ldlu, n, t, valid, q0 >> 5, x, xs, ds, ph);     // L from the tile's first block: x_i -= l_ij x_j
+    bb_inv_sweep<CT, false>(T, ldlu, n, t, valid, 0, x, xs, ds, ph);          // U in full: x_i -= u_ij x_j, then x_i /= u_ii
+    if (valid) {
+        double *o = inv + b * strideInv;
+#pragma unroll
+        for (int c = 0; c < CT; ++c)
+            if (q0 + c < n) o[t + (long long)map[q0 + c] * ldinv] = x[c];
+    }
+}
+
+// ---- determinant -----------------------------------------------------------------------------------------------------------------------
+// mpf_getdet's order for n <= 1024: up to four chunks of 256 consecutive diagonal entries.  One workgroup per matrix: thread = diagonal
+// entry for the loads ((m_i, e_i) = frexp(u_ii) into LDS, the pivot count and the special cases by LDS atomics), thread = chunk for the
+// serial chains, thread 0 for the combining chain.  Reads n of the matrix's n^2 doubles.
+__global__ __launch_bounds__(256) void bb_getdet_kernel(const double *LU, long long ldlu, long long strideLU, int n, const int *ipiv,
+                                                        long long strideP, double *mant, int *expo) {
+    constexpr int DCH = 256;
+    __shared__ double sm[BB_MAXN], cp[BB_MAXN / DCH];
+    __shared__ int se[BB_MAXN], ce[BB_MAXN / DCH];
+    __shared__ int s_zero, s_bad, s_flips;
+    const int t = threadIdx.x, nch = (n + DCH - 1) / DCH;
+    const long long b = blockIdx.x;
+    const double *a = LU + b * strideLU;
+    const int *pvt = ipiv + b * strideP;
+    if (t == 0) { s_zero = 0; s_bad = 0; s_flips = 0; }
+    __syncthreads();
+    int zero = 0, bad = 0, flips = 0;
+    for (int i = t; i < n; i += 256) {
+        const double u = a[i + (long long)i * ldlu];
+        zero |= u == 0.0;
+        bad |= !(fabs(u) <= 1.7976931348623157e308);
+        flips ^= pvt[i] != i + 1 ? 1 : 0;
+        int ei;
+        sm[i] = frexp(u, &ei);
+        se[i] = ei;
+    }
+    if (zero) atomicOr(&s_zero, 1);
+    if (bad) atomicOr(&s_bad, 1);
+    if (flips) atomicXor(&s_flips, 1);
+    __syncthreads();
+    if (t < nch) {
+        const int i1 = (t + 1) * DCH < n ? (t + 1) * DCH : n;
+        double p = 1.0;
+        int e = 0;
+        for (int i = t * DCH; i < i1; ++i) mpf_det_step(p, e, sm[i], se[i]);
+        cp[t] = p;
+        ce[t] = e;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    double P = 1.0;
+    int E = 0;
+    for (int ch = 0; ch < nch; ++ch) mpf_det_step(P, E, cp[ch], ce[ch]);
+    if (s_flips) P = -P;
+    if (s_bad) { P = __builtin_nan(""); E = 0; }
+    else if (s_zero) { P = 0.0; E = 0; }
+    mant[b] = P;
+    expo[b] = E;
+}
+
 // ---- launchers: batch <= BB_MAX_LAUNCH matrices (the host splits longer batches) ---------------------------------------------------------
 template <int NB>
 static void bb_factor_loop(mpf_ctx *c, double *A, int64_t lda, int64_t strideA, int n, int64_t batch, int *ipiv, int64_t strideP, int *info,
@@ -409,6 +599,28 @@ int launch_getrs_batched_blocked(mpf_ctx *c, int trans, const double *LU, int64_
         const dim3 g((unsigned)((nrhs + 7) / 8), (unsigned)batch);
         bb_getrs_kernel<8><<<g, th, 0, c->stream>>>(trans, LU, ldlu, strideLU, n, ipiv, strideP, nrhs, B, ldb, strideB);
     }
+    MPF_HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int launch_getri_batched_blocked(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv,
+                                 int64_t strideP, double *inv, int64_t ldinv, int64_t strideInv, int *info, int ct) {
+    if (n < 1 || batch < 1) return 0;
+    if (n > BB_MAXN || batch > BB_MAX_LAUNCH) { c->err = "launch_getri_batched_blocked: size out of range"; return -1; }
+    const unsigned th = (unsigned)((n + 63) / 64 * 64);
+    if (ct != 8 && ct != 16) ct = 16;                              // automatic
+    const dim3 g((unsigned)((n + ct - 1) / ct), (unsigned)batch);
+    if (ct == 8) bb_getri_kernel<8><<<g, th, 0, c->stream>>>(LU, ldlu, strideLU, n, ipiv, strideP, inv, ldinv, strideInv, info);
+    else bb_getri_kernel<16><<<g, th, 0, c->stream>>>(LU, ldlu, strideLU, n, ipiv, strideP, inv, ldinv, strideInv, info);
+    MPF_HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int launch_getdet_batched_blocked(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv,
+                                  int64_t strideP, double *mant, int *expo) {
+    if (n < 1 || batch < 1) return 0;
+    if (n > BB_MAXN || batch > BB_MAX_LAUNCH) { c->err = "launch_getdet_batched_blocked: size out of range"; return -1; }
+    bb_getdet_kernel<<<(unsigned)batch, 256, 0, c->stream>>>(LU, ldlu, strideLU, n, ipiv, strideP, mant, expo);
     MPF_HIP_TRY(c, hipGetLastError());
     return 0;
 }

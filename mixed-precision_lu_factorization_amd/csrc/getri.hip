@@ -147,13 +147,12 @@ __global__ __launch_bounds__(256) void getdet_kernel(const double *__restrict__ 
             if (u == 0.0) zero = 1;
             if (!(fabs(u) <= 1.7976931348623157e308)) bad = 1;
             flips ^= (ipiv[i] != (int)(i + 1)) ? 1 : 0;
-            int ei, k;
+            int ei;
             const double m = frexp(u, &ei);
             long long es = ei;
             if (r) { int er; (void)frexp(r[i], &er); es -= er - 1; }
             if (cs) { int ec; (void)frexp(cs[i], &ec); es -= ec - 1; }
-            p = frexp(p * m, &k);
-            e += k + es;
+            mpf_det_step(p, e, m, es);
         }
         part[2 * ch] = p;
         ((long long *)part)[2 * ch + 1] = e;
@@ -166,9 +165,7 @@ __global__ __launch_bounds__(256) void getdet_kernel(const double *__restrict__ 
     double P = 1.0;
     long long E = 0;
     for (long long ch = 0; ch < nch; ++ch) {
-        int k;
-        P = frexp(P * part[2 * ch], &k);
-        E += k + ((const long long *)part)[2 * ch + 1];
+        mpf_det_step(P, E, part[2 * ch], ((const long long *)part)[2 * ch + 1]);
     }
     if (s_flips) P = -P;
     if (s_bad) { P = __builtin_nan(""); E = 0; }

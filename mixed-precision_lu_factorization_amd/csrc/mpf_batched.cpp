@@ -7,6 +7,7 @@
 // contracts are in include/mpf_c.h.
 //   mpf_getrf_batched_blocked, mpf_getrs_batched_blocked   the first two for one n <= 1024: the same bits from a right-looking blocked
 //                       loop (batched_blocked.hip), three launches per panel step for the whole batch
+//   mpf_getri_batched_blocked, mpf_getdet_batched_blocked   the other two for one n <= 1024: one launch each, no workspace
 // The same four for matrices of different orders (mpf_*_vbatched) on a descriptor, mpf_vbatch: the host plan of vbatch_plan.h (checks,
 // prefix sums, size classes) uploaded once; each call then launches one ragged kernel of vbatched.hip per class that is not empty.
 #include "mpf_internal.h"
@@ -40,10 +41,10 @@ int check_sizes(mpf_ctx *c, const char *who, int32_t n, int64_t batch, int64_t s
     return 0;
 }
 // the same for the blocked entry points: n <= 1024
-int check_sizes_blocked(mpf_ctx *c, const char *who, int32_t n, int64_t batch, int64_t strideP) {
+int check_sizes_blocked(mpf_ctx *c, const char *who, int32_t n, int64_t batch, int64_t strideP, const char *then = "solve with mpf_getrs") {
     if (n < 0 || batch < 0) { c->err = std::string(who) + ": n and batch must not be negative"; return -1; }
     if (n > BB_MAXN) {
-        c->err = std::string(who) + ": n > 1024 is not a batch-sized matrix: factor it with mpf_factor_dev (and solve with mpf_getrs)";
+        c->err = std::string(who) + ": n > 1024 is not a batch-sized matrix: factor it with mpf_factor_dev (and " + then + ")";
         return -1;
     }
     if (batch > 1 && strideP < n) { c->err = std::string(who) + ": stride of ipiv < n"; return -1; }
@@ -184,6 +185,57 @@ int mpf_getrs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_LU, int
         const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
         rc = launch_getrs_batched_blocked(c, trans, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, nrhs,
                                           d_B + b0 * strideB, ldb, strideB);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// mpf_getri_batched's checks with the larger limit.  The kernels need no flag buffer: every workgroup reads its matrix's diagonal and
+// knows the first zero before its first store, whether or not d_info is given.
+int mpf_getri_batched_blocked(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                              const int32_t *d_ipiv, int64_t strideP, double *d_inv, int64_t ldinv, int64_t strideInv, int32_t *d_info) {
+    if (!c) return -1;
+    int rc = check_sizes_blocked(c, "getri_batched_blocked", n, batch, strideP, "invert with mpf_getri");
+    if (rc) return rc;
+    if (n == 0 || batch == 0) return 0;
+    rc = check_strided(c, "getri_batched_blocked", "LU", ldlu, strideLU, n, n, batch);
+    if (!rc) rc = check_strided(c, "getri_batched_blocked", "inv", ldinv, strideInv, n, n, batch);
+    if (rc) return rc;
+    if (!d_LU || !d_ipiv || !d_inv) { c->err = "getri_batched_blocked: null pointer"; return -1; }
+    {   // mpf_getri_batched's rule and text
+        const uintptr_t a0 = (uintptr_t)d_LU, a1 = a0 + (size_t)((batch - 1) * strideLU + (n - 1) * ldlu + n) * sizeof(double);
+        const uintptr_t b0 = (uintptr_t)d_inv, b1 = b0 + (size_t)((batch - 1) * strideInv + (n - 1) * ldinv + n) * sizeof(double);
+        if (a0 < b1 && b0 < a1) { c->err = "getri_batched_blocked: d_inv overlaps d_LU (the inverse is formed out of place)"; return -1; }
+    }
+    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
+        return mpf_getri_batched(c, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_inv, ldinv, strideInv, d_info);
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
+        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
+        rc = launch_getri_batched_blocked(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP,
+                                          d_inv + b0 * strideInv, ldinv, strideInv, d_info ? d_info + b0 : nullptr,
+                                          c->tune.batched_blocked_inv_ct);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_getdet_batched_blocked(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                               const int32_t *d_ipiv, int64_t strideP, double *d_mant, int32_t *d_expo) {
+    if (!c) return -1;
+    int rc = check_sizes_blocked(c, "getdet_batched_blocked", n, batch, strideP, "take the determinant with mpf_getdet");
+    if (rc) return rc;
+    if (n == 0 || batch == 0) return 0;
+    rc = check_strided(c, "getdet_batched_blocked", "LU", ldlu, strideLU, n, n, batch);
+    if (rc) return rc;
+    if (!d_LU || !d_ipiv || !d_mant || !d_expo) { c->err = "getdet_batched_blocked: null pointer"; return -1; }
+    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
+        return mpf_getdet_batched(c, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_mant, d_expo);
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
+        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
+        rc = launch_getdet_batched_blocked(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0,
+                                           d_expo + b0);
         if (rc) return rc;
     }
     return 0;

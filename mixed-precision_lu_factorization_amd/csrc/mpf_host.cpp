@@ -69,6 +69,7 @@ const OptDesc kOpts[] = {
     OPT_I(gmres_group_tiles, "MPF_GMRES_GROUP_TILES", 0, 16),
     OPT_I(batched_blocked_min_n, "MPF_BATCHED_BLOCKED_MIN_N", 0, 1025),
     OPT_I(batched_blocked_nb, "MPF_BATCHED_BLOCKED_NB", 0, 32),
+    OPT_I(batched_blocked_inv_ct, "MPF_BATCHED_BLOCKED_INV_CT", 0, 16),
 #ifdef MPF_PROBE
     OPT_I(batched_blocked_valu, "MPF_BATCHED_BLOCKED_VALU", 0, 1),
     OPT_I(batched_blocked_stages, "MPF_BATCHED_BLOCKED_STAGES", 0, 7),

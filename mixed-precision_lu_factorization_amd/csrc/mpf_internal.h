@@ -128,6 +128,7 @@ struct MpfTuning {
     int batched_blocked_min_n = 129;     // MPF_BATCHED_BLOCKED_MIN_N: mpf_getrf_batched_blocked / mpf_getrs_batched_blocked hand matrices of n below this (and <= 128)
                                          // to the one-workgroup kernels of batched.hip (same bits by contract); 0: every n through the blocked kernels
     int batched_blocked_nb = 0;          // MPF_BATCHED_BLOCKED_NB: panel width of the blocked batched LU: 8, 16 or 32; 0 (or any other value) = automatic.  Same bits
+    int batched_blocked_inv_ct = 0;      // MPF_BATCHED_BLOCKED_INV_CT: columns per workgroup of the blocked batched inverse: 8 or 16; 0 (or any other value) = automatic.  Same bits
 #ifdef MPF_PROBE                         // libmpf_probe.so only (tools/): measured-slower variants and diagnostics
     int batched_blocked_valu = 0;        // MPF_BATCHED_BLOCKED_VALU=1: the blocked batched LU's fused trailing update on the VALU kernel instead of the MFMA one (cross-check)
     int batched_blocked_stages = 7;      // MPF_BATCHED_BLOCKED_STAGES: stages the blocked batched LU launches, bit 0 panel, 1 row block, 2 update (per-stage timing; results wrong unless 7)
@@ -516,6 +517,13 @@ int launch_getri_tri(mpf_ctx *c, bool right, const double *G, double *W, int64_t
 int launch_getri_permute(mpf_ctx *c, double *W, int64_t ld, int64_t n, const int *src, const double *r, const double *cs, double *T);
 int launch_getdet(mpf_ctx *c, const double *LU, int64_t ld, const int *ipiv, int64_t n, const double *r, const double *cs, double *part,
                   double *out);
+// the one step of every determinant's running product (mpf_getdet's order, include/mpf_c.h): (p, e) times m 2^em, p back in [0.5, 1)
+template <class E>
+__device__ __forceinline__ void mpf_det_step(double &p, E &e, double m, E em) {
+    int k;
+    p = frexp(p * m, &k);
+    e += k + em;
+}
 // LU of many small matrices (batched.hip; argument checks and chunks in mpf_batched.cpp): one launch each on at most BT_MAX_LAUNCH
 // matrices of 1 <= n <= 128.  launch_getrf_batched: mpf_dgetf2_piv's pivots and bits per matrix (n <= 32: 8, 16 or 32 lanes per matrix from
 // registers; above: a workgroup per matrix from LDS), info[b] = first zero pivot or 0 when info is not null.  launch_getrs_batched:
@@ -557,6 +565,14 @@ int launch_getrf_batched_blocked(mpf_ctx *c, double *A, int64_t lda, int64_t str
                                  int *info, int fused, int nb, int valu, int stages);
 int launch_getrs_batched_blocked(mpf_ctx *c, int trans, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch,
                                  const int *ipiv, int64_t strideP, int nrhs, double *B, int64_t ldb, int64_t strideB);
+// launch_getri_batched_blocked: launch_getrs_batched_blocked(trans = 0)'s bits on an identity that is never formed, out of place, one
+// workgroup per (matrix, tile of ct = 8 or 16 columns of inv(L); anything else: automatic); a matrix with a zero on U's diagonal is
+// left untouched, info[b] (when not null) = the first such i + 1 or 0.  launch_getdet_batched_blocked: mpf_getdet's order per matrix
+// (up to four chunks of 256), one workgroup per matrix.
+int launch_getri_batched_blocked(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv,
+                                 int64_t strideP, double *inv, int64_t ldinv, int64_t strideInv, int *info, int ct);
+int launch_getdet_batched_blocked(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv,
+                                  int64_t strideP, double *mant, int *expo);
 // mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
 int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 

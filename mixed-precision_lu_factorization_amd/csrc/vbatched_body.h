@@ -517,10 +517,9 @@ __device__ __forceinline__ void bt_getdet_body(const double *a, long long ldlu, 
             zero |= u == 0.0;
             bad |= !(fabs(u) <= 1.7976931348623157e308);
             flips ^= pv[i] != i + 1 ? 1 : 0;
-            int ei, k;
+            int ei;
             const double m = frexp(u, &ei);
-            p = frexp(p * m, &k);
-            e += k + ei;
+            mpf_det_step(p, e, m, ei);
         }
     } else {
         const int lane = threadIdx.x & 63;
@@ -539,9 +538,7 @@ __device__ __forceinline__ void bt_getdet_body(const double *a, long long ldlu, 
         for (int i = 0; i < n; ++i) {
             const double mi = bt_bcast<2>(m, i);
             const int ei = i < 64 ? __builtin_amdgcn_readlane(ex[0], i) : __builtin_amdgcn_readlane(ex[1], i - 64);
-            int k;
-            p = frexp(p * mi, &k);
-            e += k + ei;
+            mpf_det_step(p, e, mi, ei);
         }
         if (lane != 0) return;
     }
