@@ -758,7 +758,8 @@ int mpf_getdet_batched(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t s
  * mpf_getrf_batched and mpf_getrs_batched above stop at n = 128, where a matrix still fits one workgroup's LDS, and stay as they are.
  * These take 0 <= n <= 1024 with the same layout, argument checks, error style and asynchrony, and mpf_getri_batched_blocked and
  * mpf_getdet_batched_blocked below do the same for mpf_getri_batched and mpf_getdet_batched; fp64 only, one n per call, no refinement
- * above 128, no driver uses them, and the vbatched descriptor below stays at n <= 128.
+ * above 128, no driver uses them.  Matrices of different orders up to 1024 in one call: a descriptor from mpf_vbatch_create_blocked
+ * below (the descriptor from mpf_vbatch_create stays at n <= 128).
  *
  * Factorization.  mpf_getrf_batched's contract, word for word, with the larger limit: for every b, A[b], ipiv[b][0 .. n-1] and
  * d_info[b] equal, bit for bit, what mpf_dgetf2_piv(ctx, A[b], lda, n, n, fused, 0, ...) leaves; for n <= 128 that is also
@@ -836,11 +837,34 @@ int mpf_getdet_batched_blocked(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, i
  * mpf_vbatch_destroy synchronises the context's stream first; destroy every descriptor before its context.
  * mpf_vbatch_info / mpf_vbatch_offsets: what creation computed (any output may be NULL); offM = the matrix offsets, offV the vector ones.
  *
- * Not here: pointer arrays to separate allocations, n > 128, a per-matrix nrhs, sizes given on the device, a block-diagonal
- * matrix-vector product with the inverses, fp16, refinement.  No driver uses these. */
+ * Not here: pointer arrays to separate allocations, n > 128 (mpf_vbatch_create_blocked below), a per-matrix nrhs, sizes given on the
+ * device, a block-diagonal matrix-vector product with the inverses, fp16, refinement.  No driver uses these. */
 typedef struct mpf_vbatch mpf_vbatch;
 int mpf_vbatch_create(mpf_ctx *ctx, int64_t batch, const int32_t *n /* host */, const int64_t *ld /* host, optional */,
                       const int64_t *off /* host, optional */, mpf_vbatch **out);
+/* The same descriptor for orders 0 <= n[b] <= 1024 (csrc/vbatched_blocked.hip, bodies in csrc/batched_blocked_body.h): the same layout
+ * rules, checks, messages and descriptor type; n[b] > 1024 is refused (use mpf_factor_dev).  The four mpf_*_vbatched entries below take
+ * either kind of descriptor; for one from mpf_vbatch_create they issue exactly the launches they always did.
+ * Contract: for every b the result equals, bit for bit, what the fixed-size BLOCKED entry above (mpf_getrf_batched_blocked,
+ * mpf_getrs_batched_blocked, mpf_getri_batched_blocked, mpf_getdet_batched_blocked) returns for that matrix alone with n = n[b] -- A / LU,
+ * pivots, d_info, the in-place solve on rows offV[b] .. of the tall B, the inverse in the descriptor's layout, (mant, expo).  A matrix's
+ * bits depend on nothing but the matrix and `fused`: not on the batch, its position, the orders of the matrices launched with it, ld,
+ * off, the panel width (option batched_blocked_nb), the inverse tile (option batched_blocked_inv_ct) or the path it took.  Rows n[b] ..
+ * ld[b]-1 and every byte between matrices are neither read nor written; a matrix with a zero on U's diagonal leaves its inverse
+ * untouched and disturbs no neighbour; out-of-range pivots read as "no interchange".
+ * Path: a matrix with n[b] <= 128 and n[b] < option batched_blocked_min_n goes into the seven size classes above and runs their
+ * kernels -- the rule by which the fixed-size blocked entries forward.  Every other matrix goes into the large list, ordered by n
+ * (stable) and cut into launch groups by order (tops 256, 512, 1024), and runs the ragged forms of the blocked kernels: grids and
+ * blocks sized for the largest matrix of a launch, and each panel step of the factorization launched only over the matrices still
+ * active at that column (a suffix of the ordered group).  The option is read ONCE, at creation, and stored in the descriptor: changing
+ * it later does not move a matrix of an existing descriptor.  batched_blocked_min_n = 0 sends every order >= 1 through the blocked
+ * kernels; matrices of order 0 stay in the list of their own.
+ * Asynchronous on the context's stream, no workspace beyond the descriptor, nothing read back; every launch is an ordinary launch (no
+ * kernel waits for another workgroup, no bounded spin, no co-residency requirement); a group with more than 32768 matrices is launched
+ * in chunks.
+ * Not here: pointer arrays, a per-matrix nrhs, sizes given on the device, fp16, refinement; no driver uses it. */
+int mpf_vbatch_create_blocked(mpf_ctx *ctx, int64_t batch, const int32_t *n /* host */, const int64_t *ld /* host, optional */,
+                              const int64_t *off /* host, optional */, mpf_vbatch **out);
 void mpf_vbatch_destroy(mpf_vbatch *vb);
 int mpf_vbatch_info(const mpf_vbatch *vb, int64_t *batch, int64_t *total_n, int64_t *extent);
 int mpf_vbatch_offsets(const mpf_vbatch *vb, int64_t *offM /* host, batch */, int64_t *offV /* host, batch */);

@@ -41,7 +41,7 @@ C_ABI_SYMBOLS = [
     "mpf_getri_batched", "mpf_getdet_batched",
     "mpf_getrf_batched_blocked", "mpf_getrs_batched_blocked",
     "mpf_getri_batched_blocked", "mpf_getdet_batched_blocked",
-    "mpf_vbatch_create", "mpf_vbatch_destroy", "mpf_vbatch_info", "mpf_vbatch_offsets",
+    "mpf_vbatch_create", "mpf_vbatch_create_blocked", "mpf_vbatch_destroy", "mpf_vbatch_info", "mpf_vbatch_offsets",
     "mpf_getrf_vbatched", "mpf_getrs_vbatched", "mpf_getri_vbatched", "mpf_getdet_vbatched",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
@@ -219,6 +219,7 @@ def load_library(probe=False):
     L.mpf_getri_batched_blocked.argtypes = L.mpf_getri_batched.argtypes
     L.mpf_getdet_batched_blocked.argtypes = L.mpf_getdet_batched.argtypes
     L.mpf_vbatch_create.argtypes = [vp, i64, vp, vp, vp, C.POINTER(vp)]
+    L.mpf_vbatch_create_blocked.argtypes = L.mpf_vbatch_create.argtypes
     L.mpf_vbatch_destroy.argtypes = [vp]
     L.mpf_vbatch_destroy.restype = None
     L.mpf_vbatch_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
@@ -1257,6 +1258,12 @@ class MPFContext:
         at element offset off[b] with leading dimension ld[b] (ld=None: n[b]; off=None: packed).  Returns a VBatch."""
         return VBatch(self, n, ld, off)
 
+    def vbatch_blocked(self, n, ld=None, off=None):
+        """mpf_vbatch_create_blocked: vbatch for orders n[b] <= 1024 -- the same arguments and the same VBatch.  Every matrix's results
+        are bit for bit those of the *_batched_blocked methods on that matrix alone.  Option batched_blocked_min_n (which matrices of
+        order <= 128 take the small kernels) is read here, once."""
+        return VBatch(self, n, ld, off, blocked=True)
+
 
 class VBatch:
     """A variable-size batch (mpf_vbatch): `batch` matrices of orders n[b] in one flat float64 device tensor of `extent` elements; the
@@ -1264,7 +1271,7 @@ class VBatch:
     column-major matrix.  Attributes: batch, total_n, extent, n, ld, off, offv (numpy).  Every method is asynchronous on the context's
     stream except solve / inv, which read info back."""
 
-    def __init__(self, ctx, n, ld=None, off=None):
+    def __init__(self, ctx, n, ld=None, off=None, blocked=False):
         import weakref
         import numpy as np
         ctx._bind()
@@ -1278,8 +1285,9 @@ class VBatch:
                 assert a.size == batch, f"{name}: one entry per matrix"
             args.append(a)
         ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None   # noqa: E731
-        rc = ctx.L.mpf_vbatch_create(ctx.h, batch, ptr(self.n), ptr(args[0]), ptr(args[1]), C.byref(self.h))
-        ctx._check(rc, "mpf_vbatch_create")
+        create = "mpf_vbatch_create_blocked" if blocked else "mpf_vbatch_create"
+        rc = getattr(ctx.L, create)(ctx.h, batch, ptr(self.n), ptr(args[0]), ptr(args[1]), C.byref(self.h))
+        ctx._check(rc, create)
         b, tn, ext = C.c_int64(), C.c_int64(), C.c_int64()
         ctx.L.mpf_vbatch_info(self.h, C.byref(b), C.byref(tn), C.byref(ext))
         self.batch, self.total_n, self.extent = b.value, tn.value, ext.value

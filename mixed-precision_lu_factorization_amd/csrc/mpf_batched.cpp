@@ -10,6 +10,8 @@
 //   mpf_getri_batched_blocked, mpf_getdet_batched_blocked   the other two for one n <= 1024: one launch each, no workspace
 // The same four for matrices of different orders (mpf_*_vbatched) on a descriptor, mpf_vbatch: the host plan of vbatch_plan.h (checks,
 // prefix sums, size classes) uploaded once; each call then launches one ragged kernel of vbatched.hip per class that is not empty.
+// A descriptor from mpf_vbatch_create_blocked (orders up to 1024) also has the plan's large list: its matrices take the ragged blocked
+// kernels of vbatched_blocked.hip, launch group by launch group, the factorization panel step by panel step over the active suffix.
 #include "mpf_internal.h"
 #include "vbatch_plan.h"
 #include <memory>
@@ -241,14 +243,19 @@ int mpf_getdet_batched_blocked(mpf_ctx *c, const double *d_LU, int64_t ldlu, int
     return 0;
 }
 
+} // extern "C"
+
 // ---- variable sizes -------------------------------------------------------------------------------------------------------------------
-int mpf_vbatch_create(mpf_ctx *c, int64_t batch, const int32_t *n, const int64_t *ld, const int64_t *off, mpf_vbatch **out) {
+namespace {
+// both creators: the plan with the limit and forwarding threshold in force, then the upload
+int vb_create(mpf_ctx *c, const char *who, int maxn, int min_n, int64_t batch, const int32_t *n, const int64_t *ld, const int64_t *off,
+              mpf_vbatch **out) {
     if (!c) return -1;
-    if (!out) { c->err = "vbatch_create: null pointer (out)"; return -1; }
+    if (!out) { c->err = std::string(who) + ": null pointer (out)"; return -1; }
     *out = nullptr;
     std::unique_ptr<mpf_vbatch> vb(new mpf_vbatch);
     vb->ctx = c;
-    if (vbatch::plan(batch, n, ld, off, vb->plan, c->err)) return -1;
+    if (vbatch::plan(batch, n, ld, off, vb->plan, c->err, maxn, min_n)) return -1;
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     if (batch > 0) {
         const vbatch::Plan &p = vb->plan;
@@ -266,6 +273,19 @@ int mpf_vbatch_create(mpf_ctx *c, int64_t batch, const int32_t *n, const int64_t
     }
     *out = vb.release();
     return 0;
+}
+} // namespace
+
+extern "C" {
+
+int mpf_vbatch_create(mpf_ctx *c, int64_t batch, const int32_t *n, const int64_t *ld, const int64_t *off, mpf_vbatch **out) {
+    return vb_create(c, "vbatch_create", vbatch::MAXN, vbatch::MAXN + 1, batch, n, ld, off, out);
+}
+
+// the forwarding threshold is read here, once, and kept in the descriptor's plan
+int mpf_vbatch_create_blocked(mpf_ctx *c, int64_t batch, const int32_t *n, const int64_t *ld, const int64_t *off, mpf_vbatch **out) {
+    if (!c) return -1;
+    return vb_create(c, "vbatch_create_blocked", vbatch::MAXN_BLOCKED, c->tune.batched_blocked_min_n, batch, n, ld, off, out);
 }
 
 void mpf_vbatch_destroy(mpf_vbatch *vb) {
@@ -322,6 +342,21 @@ int vb_empty(mpf_ctx *c, const mpf_vbatch *vb, int32_t *info, double *mant, int3
     }
     return 0;
 }
+// f(device list + first, count, nmax, host orders of those entries) for every chunk of every launch group of the large list
+template <class F>
+int vb_large(const mpf_vbatch *vb, F f) {
+    const vbatch::Plan &p = vb->plan;
+    std::vector<int32_t> ns;
+    for (int g = 0; g < vbatch::NGROUP; ++g)
+        for (int64_t i0 = 0; i0 < p.gcount[g]; i0 += BB_MAX_LAUNCH) {
+            const int64_t nb = p.gcount[g] - i0 < BB_MAX_LAUNCH ? p.gcount[g] - i0 : BB_MAX_LAUNCH, at = p.gstart[g] + i0;
+            ns.resize((size_t)nb);
+            for (int64_t i = 0; i < nb; ++i) ns[(size_t)i] = p.n[(size_t)p.list[(size_t)(at + i)]];
+            const int rc = f(vb->d_list.get() + at, nb, (int)ns.back(), ns.data());
+            if (rc) return rc;
+        }
+    return 0;
+}
 BtRagged vb_arrays(const mpf_vbatch *vb) { return BtRagged{vb->d_n.get(), vb->d_off.get(), vb->d_ld.get(), vb->d_offv.get()}; }
 } // namespace
 
@@ -337,8 +372,23 @@ int mpf_getrf_vbatched(mpf_ctx *c, const mpf_vbatch *vb, double *d_A, int32_t *d
     rc = vb_empty(c, vb, d_info, nullptr, nullptr);
     if (rc) return rc;
     const BtRagged v = vb_arrays(vb);
-    return vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
+    rc = vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
         return launch_getrf_vbatched(c, v, idx, count, top, nmax, d_A, d_ipiv, d_info, fused != 0);
+    });
+    if (rc || vb->plan.large_count == 0) return rc;
+    int valu = 0, stages = 7;
+#ifdef MPF_PROBE
+    valu = c->tune.batched_blocked_valu;
+    stages = c->tune.batched_blocked_stages;
+#endif
+    const int nb = vbatched_blocked_nb(c->tune.batched_blocked_nb);
+    return vb_large(vb, [&](const int32_t *idx, int64_t count, int nmax, const int32_t *ns) {
+        for (const vbatch::Step &s : vbatch::factor_steps(ns, count, nb)) {   // nmax - s.j0 == s.rows
+            const int e = launch_getrf_vbatched_blocked_step(c, v, idx + s.first, count - s.first, nmax, s.j0, nb, d_A, d_ipiv, d_info,
+                                                             fused != 0, valu, stages);
+            if (e) return e;
+        }
+        return 0;
     });
 }
 
@@ -354,8 +404,12 @@ int mpf_getrs_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const do
     if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs_vbatched: null pointer"; return -1; }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     const BtRagged v = vb_arrays(vb);
-    return vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
+    rc = vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
         return launch_getrs_vbatched(c, v, idx, count, top, nmax, trans, d_LU, d_ipiv, nrhs, d_B, ldb);
+    });
+    if (rc) return rc;
+    return vb_large(vb, [&](const int32_t *idx, int64_t count, int nmax, const int32_t *) {
+        return launch_getrs_vbatched_blocked(c, v, idx, count, nmax, trans, d_LU, d_ipiv, nrhs, d_B, ldb);
     });
 }
 
@@ -375,8 +429,12 @@ int mpf_getri_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_LU, con
     rc = vb_empty(c, vb, d_info, nullptr, nullptr);
     if (rc) return rc;
     const BtRagged v = vb_arrays(vb);
-    return vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
+    rc = vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
         return launch_getri_vbatched(c, v, idx, count, top, nmax, d_LU, d_ipiv, d_inv, d_info);
+    });
+    if (rc) return rc;
+    return vb_large(vb, [&](const int32_t *idx, int64_t count, int nmax, const int32_t *) {
+        return launch_getri_vbatched_blocked(c, v, idx, count, nmax, d_LU, d_ipiv, d_inv, d_info, c->tune.batched_blocked_inv_ct);
     });
 }
 
@@ -390,8 +448,12 @@ int mpf_getdet_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_LU, co
     rc = vb_empty(c, vb, nullptr, d_mant, d_expo);
     if (rc) return rc;
     const BtRagged v = vb_arrays(vb);
-    return vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
+    rc = vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
         return launch_getdet_vbatched(c, v, idx, count, top, d_LU, d_ipiv, d_mant, d_expo);
+    });
+    if (rc) return rc;
+    return vb_large(vb, [&](const int32_t *idx, int64_t count, int, const int32_t *) {
+        return launch_getdet_vbatched_blocked(c, v, idx, count, d_LU, d_ipiv, d_mant, d_expo);
     });
 }
 

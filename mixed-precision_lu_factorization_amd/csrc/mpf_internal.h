@@ -126,7 +126,8 @@ struct MpfTuning {
                                          // (at most 16), 0 = automatic -- the most (<= 16, >= 1) whose restart + 1 basis sets and six working sets fit in
                                          // 2 GiB.  The results do not depend on it (every column's arithmetic is its own)
     int batched_blocked_min_n = 129;     // MPF_BATCHED_BLOCKED_MIN_N: mpf_getrf_batched_blocked / mpf_getrs_batched_blocked hand matrices of n below this (and <= 128)
-                                         // to the one-workgroup kernels of batched.hip (same bits by contract); 0: every n through the blocked kernels
+                                         // to the one-workgroup kernels of batched.hip (same bits by contract); 0: every n through the blocked kernels.
+                                         // mpf_vbatch_create_blocked reads it once, at creation: which matrices go into the small classes
     int batched_blocked_nb = 0;          // MPF_BATCHED_BLOCKED_NB: panel width of the blocked batched LU: 8, 16 or 32; 0 (or any other value) = automatic.  Same bits
     int batched_blocked_inv_ct = 0;      // MPF_BATCHED_BLOCKED_INV_CT: columns per workgroup of the blocked batched inverse: 8 or 16; 0 (or any other value) = automatic.  Same bits
 #ifdef MPF_PROBE                         // libmpf_probe.so only (tools/): measured-slower variants and diagnostics
@@ -573,6 +574,20 @@ int launch_getri_batched_blocked(mpf_ctx *c, const double *LU, int64_t ldlu, int
                                  int64_t strideP, double *inv, int64_t ldinv, int64_t strideInv, int *info, int ct);
 int launch_getdet_batched_blocked(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv,
                                   int64_t strideP, double *mant, int *expo);
+// The same for matrices of different orders (vbatched_blocked.hip, bodies in batched_blocked_body.h; descriptor, groups and chunks in
+// mpf_batched.cpp): `count` <= BB_MAX_LAUNCH entries of a list ordered by n, idx[i] = the matrix of entry i, nmax = the largest order
+// among them.  launch_getrf_vbatched_blocked_step: ONE panel step of the right-looking loop at column j0 (a multiple of nb = 8, 16 or
+// 32, as vbatched_blocked_nb resolves the option) over the entries still active there (n > j0; vbatch_plan.h: factor_steps) -- panel,
+// row block, trailing update, each one launch sized for nmax.  The other three: one launch each, sized for nmax.
+int vbatched_blocked_nb(int nb);
+int launch_getrf_vbatched_blocked_step(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int nmax, int j0, int nb, double *A,
+                                       int *ipiv, int *info, int fused, int valu, int stages);
+int launch_getrs_vbatched_blocked(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int nmax, int trans, const double *LU,
+                                  const int *ipiv, int nrhs, double *B, int64_t ldb);
+int launch_getri_vbatched_blocked(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int nmax, const double *LU,
+                                  const int *ipiv, double *inv, int *info, int ct);
+int launch_getdet_vbatched_blocked(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, const double *LU, const int *ipiv,
+                                   double *mant, int *expo);
 // mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
 int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 

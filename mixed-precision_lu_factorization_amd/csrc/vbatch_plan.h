@@ -1,6 +1,9 @@
 // The host plan of a variable-size batch (mpf_vbatch_create; contract in include/mpf_c.h): validation, prefix sums, the overlap test,
 // the size classes and their order.  Plain C++ with no HIP and no context, so that a stand-alone program can exercise it
 // (tests/vbatch_plan_driver.cpp, under AddressSanitizer and UBSan); tests/vbatched_model.py restates it in numpy.
+// mpf_vbatch_create_blocked uses the same function with the larger limit and a forwarding threshold: the matrices that the fixed-size
+// blocked entries would hand to the small kernels stay in the classes, the others form the large list and its launch groups
+// (tests/vbatch_plan_blocked_driver.cpp, tests/vbatched_blocked_model.py).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -18,6 +21,13 @@ constexpr int MAXN = 128;
 constexpr int NCLASS = 7;
 constexpr int CLASS_TOP[NCLASS] = {8, 16, 32, 48, 64, 96, 128};
 
+// The limit of mpf_vbatch_create_blocked, and the launch groups of its large list by order: a launch's block size is sized for the
+// largest matrix of its group, so with the tops doubling it is never more than twice what the group's smallest matrix needs (as long as
+// the forwarding threshold keeps the orders below 129 out of the first group, which is the default).
+constexpr int MAXN_BLOCKED = 1024;
+constexpr int NGROUP = 3;
+constexpr int GROUP_TOP[NGROUP] = {256, 512, 1024};
+
 inline int class_of(int n) {   // 1 <= n <= MAXN
     int k = 0;
     while (CLASS_TOP[k] < n) ++k;
@@ -34,17 +44,44 @@ struct Plan {
     int64_t zeros = 0;                       // list[0 .. zeros): the matrices of order 0
     int64_t start[NCLASS] = {}, count[NCLASS] = {};
     int nmax[NCLASS] = {};                   // the largest order in each class (0: the class is empty)
+    // The large list (mpf_vbatch_create_blocked only): the matrices that take the blocked kernels, behind the classes in `list`, ordered
+    // by n (stable) like them.  A matrix is small, and in a class, when n <= MAXN and n < min_n -- the rule by which the fixed-size
+    // blocked entries forward.  list[gstart[g] .. gstart[g] + gcount[g]) is launch group g.
+    int maxn = MAXN, min_n = MAXN + 1;
+    int64_t large_start = 0, large_count = 0;
+    int64_t gstart[NGROUP] = {}, gcount[NGROUP] = {};
+    int gnmax[NGROUP] = {};                  // the largest order in each group (0: the group is empty)
 };
 
-// 0 and the plan, or -1 and a message
-inline int plan(int64_t batch, const int32_t *n, const int64_t *ld, const int64_t *off, Plan &p, std::string &err) {
-    const char *who = "vbatch_create: ";
+// One panel step of the blocked factorization of `count` list entries ordered by n: the matrices still active at column j0 (n > j0) are
+// a suffix of the entries; a step launches only over entries first .. count-1, sized for `rows` = the largest remaining row count.
+struct Step { int j0; int64_t first; int rows; };
+// ns[i] = the order of entry i, ascending, every one >= 1; nb = the panel width
+inline std::vector<Step> factor_steps(const int32_t *ns, int64_t count, int nb) {
+    std::vector<Step> steps;
+    if (count < 1 || nb < 1) return steps;
+    const int nmax = ns[count - 1];
+    int64_t first = 0;
+    for (int j0 = 0; j0 < nmax; j0 += nb) {
+        while (ns[first] <= j0) ++first;      // (ns[count - 1] = nmax > j0: stops inside)
+        steps.push_back(Step{j0, first, nmax - j0});
+    }
+    return steps;
+}
+
+// 0 and the plan, or -1 and a message.  maxn = MAXN: mpf_vbatch_create (every matrix in a class, min_n unused); maxn = MAXN_BLOCKED:
+// mpf_vbatch_create_blocked with the forwarding threshold min_n (option batched_blocked_min_n)
+inline int plan(int64_t batch, const int32_t *n, const int64_t *ld, const int64_t *off, Plan &p, std::string &err, int maxn = MAXN,
+                int min_n = MAXN + 1) {
+    const char *who = maxn > MAXN ? "vbatch_create_blocked: " : "vbatch_create: ";
     if (batch < 0) { err = std::string(who) + "batch must not be negative"; return -1; }
     if (batch >= ((int64_t)1 << 31)) { err = std::string(who) + "batch >= 2^31 matrices"; return -1; }
     if (batch > 0 && !n) { err = std::string(who) + "null pointer (n)"; return -1; }
     constexpr int64_t LIM = (int64_t)1 << 62;   // extents stay below it, so no sum below overflows
     p = Plan();
     p.batch = batch;
+    p.maxn = maxn;
+    p.min_n = maxn > MAXN ? min_n : MAXN + 1;
     p.n.assign(n, n + batch);
     p.ld.resize((size_t)batch);
     p.off.resize((size_t)batch);
@@ -54,13 +91,14 @@ inline int plan(int64_t batch, const int32_t *n, const int64_t *ld, const int64_
         const std::string at = " (matrix " + std::to_string(b) + ")";
         const int64_t nb = n[b];
         if (nb < 0) { err = std::string(who) + "n must not be negative" + at; return -1; }
-        if (nb > MAXN) {
-            err = std::string(who) + "n > 128 is not a small matrix: factor it with mpf_factor_dev (and solve with mpf_getrs)" + at;
+        if (nb > maxn) {
+            if (maxn > MAXN) err = std::string(who) + "n > 1024 is not a batch-sized matrix: factor it with mpf_factor_dev (and solve with mpf_getrs)" + at;
+            else err = std::string(who) + "n > 128 is not a small matrix: factor it with mpf_factor_dev (and solve with mpf_getrs)" + at;
             return -1;
         }
         const int64_t l = ld ? ld[b] : nb;
         if (l < nb) { err = std::string(who) + "leading dimension < n" + at; return -1; }
-        if (l >= LIM / (MAXN + 1)) { err = std::string(who) + "leading dimension out of range" + at; return -1; }
+        if (l >= LIM / (maxn + 1)) { err = std::string(who) + "leading dimension out of range" + at; return -1; }
         const int64_t o = off ? off[b] : run_m;
         if (o < 0) { err = std::string(who) + "offset must not be negative" + at; return -1; }
         const int64_t span = nb > 0 ? (nb - 1) * l + nb : 0;
@@ -91,21 +129,33 @@ inline int plan(int64_t batch, const int32_t *n, const int64_t *ld, const int64_
             if (e > end) { end = e; owner = b; }
         }
     }
-    // the classes: a counting sort by n is the stable order inside every class at once
-    int64_t by_n[MAXN + 2] = {};
-    for (int64_t b = 0; b < batch; ++b) ++by_n[n[b] + 1];
-    for (int v = 0; v <= MAXN; ++v) by_n[v + 1] += by_n[v];   // by_n[v]: where order v starts
+    // the classes and the large list: a counting sort by n is the stable order inside every class and group at once, and the small
+    // matrices (n < thr) come before the large ones
+    std::vector<int64_t> by_n((size_t)maxn + 2, 0);
+    for (int64_t b = 0; b < batch; ++b) ++by_n[(size_t)n[b] + 1];
+    for (int v = 0; v <= maxn; ++v) by_n[(size_t)v + 1] += by_n[(size_t)v];   // by_n[v]: where order v starts
     p.zeros = by_n[1];
+    const int thr = std::max(1, std::min(p.min_n, MAXN + 1));   // orders 1 .. thr-1 are small
     for (int k = 0; k < NCLASS; ++k) {
-        const int lo = k ? CLASS_TOP[k - 1] + 1 : 1, hi = CLASS_TOP[k];
-        p.start[k] = by_n[lo];
-        p.count[k] = by_n[hi + 1] - by_n[lo];
+        const int lo = k ? CLASS_TOP[k - 1] + 1 : 1, hi = std::min(CLASS_TOP[k], thr - 1);
+        p.start[k] = by_n[(size_t)std::min(lo, thr)];
+        p.count[k] = hi >= lo ? by_n[(size_t)hi + 1] - by_n[(size_t)lo] : 0;
         p.nmax[k] = 0;
         for (int v = lo; v <= hi; ++v)
-            if (by_n[v + 1] > by_n[v]) p.nmax[k] = v;
+            if (by_n[(size_t)v + 1] > by_n[(size_t)v]) p.nmax[k] = v;
+    }
+    p.large_start = thr <= maxn ? by_n[(size_t)thr] : batch;
+    p.large_count = batch - p.large_start;
+    for (int g = 0; g < NGROUP; ++g) {
+        const int lo = std::max(thr, g ? GROUP_TOP[g - 1] + 1 : 1), hi = std::min(GROUP_TOP[g], maxn);
+        p.gstart[g] = lo <= maxn ? by_n[(size_t)lo] : batch;
+        p.gcount[g] = hi >= lo ? by_n[(size_t)hi + 1] - by_n[(size_t)lo] : 0;
+        p.gnmax[g] = 0;
+        for (int v = lo; v <= hi; ++v)
+            if (by_n[(size_t)v + 1] > by_n[(size_t)v]) p.gnmax[g] = v;
     }
     p.list.resize((size_t)batch);
-    for (int64_t b = 0; b < batch; ++b) p.list[(size_t)by_n[n[b]]++] = (int32_t)b;
+    for (int64_t b = 0; b < batch; ++b) p.list[(size_t)by_n[(size_t)n[b]]++] = (int32_t)b;
     return 0;
 }
 
