@@ -683,7 +683,8 @@ int mpf_getdet(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, const int32_t *d_
  * Every other entry point works on ONE matrix and is tuned for N >= 4096; these take `batch` matrices of one size n <= 128 in one
  * launch (csrc/batched.hip).  fp64 only, LAPACK partial pivoting: the fp16-image pivot rule and the fp16 trailing modes have no meaning
  * at these sizes.  No driver uses them; the inverse and the determinant from the factors are mpf_getri_batched and mpf_getdet_batched
- * below; matrices of different orders in one call: the mpf_*_vbatched entries after them; there is no batched refinement.
+ * below; matrices of different orders in one call: the mpf_*_vbatched entries after them; refinement, error bounds and rcond for these
+ * batches: the mpf_*_batched expert entries after mpf_getdet_batched (there is none for the blocked or the vbatched forms).
  *
  * Layout: A[b] = d_A + b * strideA, n x n column-major, lda >= n, strideA >= lda * n (or batch == 1);
  * ipiv[b] = d_ipiv + b * strideP, strideP >= n (or batch == 1), 1-based as LAPACK; d_info: batch int32 on the device, optional.
@@ -753,6 +754,68 @@ int mpf_getri_batched(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t st
 int mpf_getdet_batched(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                        const int32_t *d_ipiv, int64_t strideP,
                        double *d_mant, int32_t *d_expo /* device, batch each */);
+
+/* ---- the expert layer for the same batches (build extension; csrc/batched_refine.hip) -----------------------------------------------------
+ * A reciprocal condition number per matrix, dgerfs's refinement with berr and ferr per matrix and column, and the two step operators
+ * they need, for strided batches of ONE order n <= 128.  The layout rules, argument checks, error style and asynchrony are
+ * mpf_getrs_batched's: everything runs on the device in ordinary launches on the context's stream, nothing is read back, every result
+ * is a device array.  n > 128 is refused with -1 (use mpf_gecon / mpf_gerfs on one matrix at a time); n == 0, batch == 0 or nrhs == 0
+ * return 0 with no work; rows n .. ld-1 and the bytes between matrices are neither read nor written.
+ *
+ * THESE ARE NOT LAPACK'S ESTIMATES.  dgecon and dgerfs estimate || A^-1 || and || |op(A)^-1| g || with dlacn2, 4 to 11 single-vector
+ * solves each.  At these sizes one such solve is bound by the latency of a 2 n-step chain, and all n columns of the inverse, side by
+ * side, cost about as much.  So both quantities are computed EXACTLY: the kernels form the columns or rows of the inverse in registers
+ * by the chains of mpf_getrs_batched / mpf_getri_batched, reduce them on the fly and never store them.  Both are true norms of the
+ * computed inverse, not lower bounds: rcond is <= dgecon's (by a factor of at most about n) and ferr is >= dgerfs's.
+ *
+ * Shared rules (tests/batched_refine_model.py restates every entry in numpy, bit for bit):
+ *   tree sum   every sum over a row or column index is a halving tree, + rounded once per step: the terms are padded to 128 with +0,
+ *              then v = v[0..63] + v[64..127], v[0..31] + v[32..63], and so on down to one element.  Every term is >= +0, so the
+ *              padding is exact and the result depends on neither n's padding nor the kernel form.
+ *   maxima     order-free; a NaN among the terms gives NaN.
+ *   fusion     every multiply-subtract and multiply-add is unfused: the product is rounded, then the sum or difference.
+ *   constants  mpf_gerfs's: eps = 2^-53, safmin = DBL_MIN, nz = n + 1, safe1 = nz safmin, safe2 = safe1 / eps.
+ * A matrix's (and a column's) results depend on nothing but its own data: not on batch, its position, nrhs, any ld or stride, or the
+ * kernel form (n <= 8, 16, 32: that many lanes of a wave per matrix; above: one workgroup per matrix).  Non-finite data stays inside
+ * its own matrix.  Two calls return the same bits.
+ *
+ * mpf_lange_batched: d_out[b] = '1' / 'O': max_j tree_i |a_ij|; 'I': max_i tree_j |a_ij|; 'M': max |a_ij|.  Any other letter: -1. */
+int mpf_lange_batched(mpf_ctx *ctx, char norm, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                      double *d_out /* device, batch */);
+/* d_rcond[b] = (1 / ainvnm) / d_anorm[b] with ainvnm the norm of (L[b] U[b])^-1 from the packed factors; like mpf_gecon it takes no P.
+ *   '1' / 'O': ainvnm = max_k tree_i |x_ik|, column k formed from e_k by the trans = 0 chains of mpf_getrs_batched without
+ *              interchanges (as a set, mpf_getri_batched's columns for ipiv = 1 .. n);
+ *   'I':       ainvnm = max_i tree_k |y_k|, y the trans = 1 chains from e_i without interchanges (row i of the same inverse).
+ * A kernel may skip the forward steps before a chain's one, as mpf_getri_batched does (they meet zeros only; finite factors).
+ * d_rcond[b] = 0, never NaN, when d_anorm[b] == 0, when U[b] has a zero on its diagonal (checked before any arithmetic; d_ainvnm[b]
+ * is then +Inf) or when ainvnm is not finite (or 0, as mpf_gecon has it).  d_ainvnm (optional): ainvnm per matrix.  d_anorm: what mpf_lange_batched returns for
+ * the same letter on the matrices that were factored. */
+int mpf_gecon_batched(mpf_ctx *ctx, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                      const double *d_anorm /* device, batch */, double *d_rcond /* device, batch */,
+                      double *d_ainvnm /* optional: device, batch */);
+/* The step operator.  R[b] = B[b] - op(A[b]) X[b] and, when d_W is given (R's layout: ldr, strideR), W[b] = |B[b]| + |op(A[b])| |X[b]|
+ * (op(A) = A for trans = 0, A^T for trans = 1; X, B, R are n x nrhs as mpf_getrs_batched's B).  Per element, for j ascending:
+ * r_i starts as b_i and has op(A)_ij x_j subtracted; w_i starts as |b_i| and has |op(A)_ij| |x_j| added.  One pass over A serves both.
+ * d_R may be d_B (same layout); d_R and d_W must not overlap d_A or d_X. */
+int mpf_residual_batched(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                         int32_t nrhs, const double *d_X, int64_t ldx, int64_t strideX, const double *d_B, int64_t ldb, int64_t strideB,
+                         double *d_R, int64_t ldr, int64_t strideR, double *d_W /* optional */);
+/* dgerfs per (matrix, column), exactly as mpf_gerfs's text above states it, with the factors and pivots mpf_getrf_batched leaves:
+ * d_X holds a solution of op(A[b]) X[b] = B[b] on entry (from mpf_getrs_batched) and is refined in place.
+ *   r and w are the step operator's; berr = max_i (w_i > safe2 ? |r_i| / w_i : (|r_i| + safe1) / (w_i + safe1));
+ *   while berr > eps, 2 berr <= the previous berr (3 at first) and fewer than itmax corrections: x <- x + dx, dx = the chain of
+ *   mpf_getrs_batched with the same trans applied to r.  itmax <= 0 means 5; larger values are clamped to 31.  A NaN berr stops the column and
+ *   is returned.
+ * With d_ferr given, from the last r and w: g_i = |r_i| + (nz eps) w_i, plus safe1 where w_i <= safe2; for every i,
+ * f_i = tree_k |y_k| g_k with y what the chain of mpf_getrs_batched with the other trans (1 - trans) leaves for e_i, interchanges
+ * included, so that y_k = (op(A)^-1)_ik; ferr = max_i f_i / max_i |x_i|, or the numerator alone when the denominator is 0.
+ * Results per (matrix b, column c) at index b * nrhs + c of d_berr, d_ferr (optional) and d_iters (optional: the corrections made).
+ * d_A, d_LU, d_ipiv and d_B are preserved; rows n .. ldx-1 of X are not touched.  Without d_ferr the call costs one residual per
+ * column that is already converged; with it, n more chains per matrix (and per eight columns). */
+int mpf_gerfs_batched(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, const double *d_LU, int64_t ldlu,
+                      int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv, int64_t strideP, int32_t nrhs,
+                      const double *d_B, int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t itmax,
+                      double *d_ferr /* optional */, double *d_berr, int32_t *d_iters /* optional */);
 
 /* ---- the same for ONE order up to 1024 (blocked; csrc/batched_blocked.hip) ----------------------------------------------------------------
  * mpf_getrf_batched and mpf_getrs_batched above stop at n = 128, where a matrix still fits one workgroup's LDS, and stay as they are.

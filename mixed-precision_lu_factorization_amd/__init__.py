@@ -39,6 +39,7 @@ C_ABI_SYMBOLS = [
     "mpf_getri", "mpf_getdet",
     "mpf_getrf_batched", "mpf_getrs_batched",
     "mpf_getri_batched", "mpf_getdet_batched",
+    "mpf_lange_batched", "mpf_gecon_batched", "mpf_residual_batched", "mpf_gerfs_batched",
     "mpf_getrf_batched_blocked", "mpf_getrs_batched_blocked",
     "mpf_getri_batched_blocked", "mpf_getdet_batched_blocked",
     "mpf_vbatch_create", "mpf_vbatch_create_blocked", "mpf_vbatch_destroy", "mpf_vbatch_info", "mpf_vbatch_offsets",
@@ -217,6 +218,10 @@ def load_library(probe=False):
     L.mpf_getrs_batched_blocked.argtypes = L.mpf_getrs_batched.argtypes
     L.mpf_getdet_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, i64, vp, vp]
     L.mpf_getri_batched_blocked.argtypes = L.mpf_getri_batched.argtypes
+    L.mpf_lange_batched.argtypes = [vp, C.c_char, vp, i64, i64, i32, i64, vp]
+    L.mpf_gecon_batched.argtypes = [vp, C.c_char, vp, i64, i64, i32, i64, vp, vp, vp]
+    L.mpf_residual_batched.argtypes = [vp, i32, vp, i64, i64, i32, i64, i32, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp]
+    L.mpf_gerfs_batched.argtypes = [vp, i32, vp, i64, i64, vp, i64, i64, i32, i64, vp, i64, i32, vp, i64, i64, vp, i64, i64, i32, vp, vp, vp]
     L.mpf_getdet_batched_blocked.argtypes = L.mpf_getdet_batched.argtypes
     L.mpf_vbatch_create.argtypes = [vp, i64, vp, vp, vp, C.POINTER(vp)]
     L.mpf_vbatch_create_blocked.argtypes = L.mpf_vbatch_create.argtypes
@@ -1128,6 +1133,102 @@ class MPFContext:
             b = int(bad[0])
             raise MPFError(f"solve_batched: matrix {b} of the batch is singular (zero pivot {int(info[b])})")
         return self.getrs_batched(LU, ipiv, B, trans=trans)
+
+    # ---- the expert layer for those batches (include/mpf_c.h: mpf_lange_batched, mpf_gecon_batched, mpf_residual_batched, mpf_gerfs_batched) --
+    def lange_batched(self, A, norm="1"):
+        """mpf_lange_batched: the '1' / 'O', 'I' or 'M' norm of every matrix of the (batch, n, n) tensor A, n <= 128, as a float64
+        (batch,) device tensor; sums are the header's halving tree, a NaN in a matrix gives NaN for it."""
+        self._bind()
+        t = self.torch
+        assert A.dim() == 3 and A.shape[1] == A.shape[2], "A: (batch, n, n)"
+        batch, n = A.shape[0], A.shape[1]
+        Am, lda, sa = self._batch_arg(A, "lange_batched", False, copy=False)
+        out = t.zeros(batch, dtype=t.float64, device=self.device)
+        self._check(self.L.mpf_lange_batched(self.h, norm.encode()[:1], _ptr(Am), lda, sa, n, batch, _ptr(out)), "mpf_lange_batched")
+        return out
+
+    def gecon_batched(self, LU, anorm, norm="1", want_ainvnm=False):
+        """mpf_gecon_batched: rcond[b] = (1 / ||(L U)^-1||) / anorm[b] from getrf_batched's factors, the norm of the inverse computed
+        exactly (not dgecon's estimate).  anorm: a float64 (batch,) device tensor (lange_batched of the matrices, same norm).
+        Returns rcond, or (rcond, ainvnm) with want_ainvnm; rcond is 0 for anorm 0, a zero on U's diagonal or a non-finite inverse."""
+        self._bind()
+        t = self.torch
+        assert LU.dim() == 3 and LU.shape[1] == LU.shape[2], "LU: (batch, n, n)"
+        batch, n = LU.shape[0], LU.shape[1]
+        LUm, ldlu, slu = self._batch_arg(LU, "gecon_batched", False, copy=False)
+        assert anorm.dtype == t.float64 and anorm.is_cuda and anorm.shape == (batch,)
+        anorm = anorm.contiguous()
+        rcond = t.zeros(batch, dtype=t.float64, device=self.device)
+        ainv = t.zeros(batch, dtype=t.float64, device=self.device) if want_ainvnm else None
+        rc = self.L.mpf_gecon_batched(self.h, norm.encode()[:1], _ptr(LUm), ldlu, slu, n, batch, _ptr(anorm), _ptr(rcond),
+                                      _ptr(ainv) if want_ainvnm else None)
+        self._check(rc, "mpf_gecon_batched")
+        return (rcond, ainv) if want_ainvnm else rcond
+
+    def residual_batched(self, A, X, B, trans=False, want_w=True):
+        """mpf_residual_batched: (R, W) with R[b] = B[b] - op(A[b]) X[b] and W[b] = |B[b]| + |op(A[b])| |X[b]| (W None without
+        want_w), new column-major tensors; X and B are (batch, n, nrhs), or (batch, n) for one column each."""
+        self._bind()
+        if B.dim() == 2:
+            R, W = self.residual_batched(A, X.unsqueeze(2), B.unsqueeze(2), trans, want_w)
+            return R.squeeze(2), (W.squeeze(2) if want_w else None)
+        assert A.dim() == 3 and A.shape[1] == A.shape[2] and B.dim() == 3 and B.shape[:2] == A.shape[:2] and X.shape == B.shape, \
+            "A: (batch, n, n), X and B: (batch, n, nrhs)"
+        batch, n, nrhs = B.shape
+        Am, lda, sa = self._batch_arg(A, "residual_batched", False, copy=False)
+        Xm, ldx, sx = self._batch_arg(X, "residual_batched", False, copy=False)
+        Bm, ldb, sb = self._batch_arg(B, "residual_batched", False, copy=False)
+        R = self.colmajor_batch(batch, n, nrhs)
+        W = self.colmajor_batch(batch, n, nrhs) if want_w else None
+        ldr, sr = self._batch_layout(R)
+        rc = self.L.mpf_residual_batched(self.h, int(bool(trans)), _ptr(Am), lda, sa, n, batch, nrhs, _ptr(Xm), ldx, sx, _ptr(Bm), ldb, sb,
+                                         _ptr(R), ldr, sr, _ptr(W) if want_w else None)
+        self._check(rc, "mpf_residual_batched")
+        return R, W
+
+    def gerfs_batched(self, A, LU, ipiv, B, X, trans=False, itmax=0, overwrite=False, want_ferr=True):
+        """mpf_gerfs_batched: dgerfs per matrix and column with getrf_batched's factors.  X holds a solution (getrs_batched's) and
+        is refined: a new column-major tensor, or X itself with overwrite=True (column-major matrices).  Returns (X, ferr, berr,
+        iters): float64 / int32 (batch, nrhs) device tensors (ferr None without want_ferr).  ferr bounds max_i |x_i - xtrue_i| /
+        max_i |x_i| with the exact norm where dgerfs estimates it."""
+        self._bind()
+        t = self.torch
+        if B.dim() == 2:
+            Xr, ferr, berr, its = self.gerfs_batched(A, LU, ipiv, B.unsqueeze(2), X.unsqueeze(2), trans, itmax, overwrite, want_ferr)
+            return Xr.squeeze(2), ferr, berr, its
+        assert A.dim() == 3 and A.shape[1] == A.shape[2] and B.dim() == 3 and B.shape[:2] == A.shape[:2] and X.shape == B.shape, \
+            "A: (batch, n, n), B and X: (batch, n, nrhs)"
+        assert LU.shape == A.shape
+        nrhs = B.shape[2]
+        Am, lda, sa = self._batch_arg(A, "gerfs_batched", False, copy=False)
+        LUm, ldlu, slu, ipiv, sp, batch, n = self._batch_factors(LU, ipiv, "gerfs_batched")
+        Bm, ldb, sb = self._batch_arg(B, "gerfs_batched", False, copy=False)
+        Xm, ldx, sx = self._batch_arg(X, "gerfs_batched", overwrite)
+        ferr = t.zeros((batch, nrhs), dtype=t.float64, device=self.device) if want_ferr else None
+        berr = t.zeros((batch, nrhs), dtype=t.float64, device=self.device)
+        its = t.zeros((batch, nrhs), dtype=t.int32, device=self.device)
+        rc = self.L.mpf_gerfs_batched(self.h, int(bool(trans)), _ptr(Am), lda, sa, _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, nrhs,
+                                      _ptr(Bm), ldb, sb, _ptr(Xm), ldx, sx, int(itmax), _ptr(ferr) if want_ferr else None, _ptr(berr),
+                                      _ptr(its))
+        self._check(rc, "mpf_gerfs_batched")
+        return Xm, ferr, berr, its
+
+    def cond_batched(self, A, norm="1"):
+        """rcond of every matrix of the (batch, n, n) tensor A, n <= 128: getrf_batched on a copy, lange_batched, gecon_batched.  0
+        for a singular matrix; nothing is read back."""
+        LU, _, _ = self.getrf_batched(A)
+        return self.gecon_batched(LU, self.lange_batched(A, norm), norm)
+
+    def solvex_batched(self, A, B, trans=False, itmax=0):
+        """dgesvx's shape without equilibration for a batch, n <= 128: getrf_batched on a copy, lange_batched / gecon_batched (the
+        '1' norm, or 'I' with trans), getrs_batched, gerfs_batched.  Returns (X, rcond, ferr, berr, info), all on the device; never
+        raises on a singular matrix: info[b] is its first zero pivot and rcond[b] is 0 (its X, ferr and berr are not meaningful)."""
+        norm = "I" if trans else "1"
+        LU, ipiv, info = self.getrf_batched(A)
+        rcond = self.gecon_batched(LU, self.lange_batched(A, norm), norm)
+        X = self.getrs_batched(LU, ipiv, B, trans=trans)
+        X, ferr, berr, _ = self.gerfs_batched(A, LU, ipiv, B, X, trans=trans, itmax=itmax, overwrite=True)
+        return X, rcond, ferr, berr, info
 
     # ---- the same for one order up to 1024 (include/mpf_c.h: mpf_getrf_batched_blocked, mpf_getrs_batched_blocked) ------------------------
     def getrf_batched_blocked(self, A, fused=False, overwrite=False, ipiv=None, info=None):

@@ -3,6 +3,9 @@
 //   mpf_getrs_batched   dgetrs with those factors, in place on the right-hand sides
 //   mpf_getri_batched   the inverse from those factors, out of place: the solve's bits on an identity that is never formed
 //   mpf_getdet_batched  the determinant from those factors as mant 2^expo, mpf_getdet's order per matrix
+//   mpf_lange_batched, mpf_gecon_batched, mpf_residual_batched, mpf_gerfs_batched   the expert layer on those batches: a norm and an
+//                       exact reciprocal condition number per matrix, the residual step operator, dgerfs's refinement with berr and
+//                       an exact ferr per matrix and column (kernels in batched_refine.hip)
 // The argument checks, the chunks of a batch longer than one grid and the error text; kernels and form choice in batched.hip; the
 // contracts are in include/mpf_c.h.
 //   mpf_getrf_batched_blocked, mpf_getrs_batched_blocked   the first two for one n <= 1024: the same bits from a right-looking blocked
@@ -135,6 +138,113 @@ int mpf_getdet_batched(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t str
     for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
         const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
         rc = launch_getdet_batched(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0, d_expo + b0);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---- the expert layer, n <= 128 (kernels in batched_refine.hip) ---------------------------------------------------------------------------
+// check_sizes' rules with the message that names where larger matrices go
+static int check_sizes_refine(mpf_ctx *c, const char *who, int32_t n, int64_t batch, const char *use) {
+    if (n < 0 || batch < 0) { c->err = std::string(who) + ": n and batch must not be negative"; return -1; }
+    if (n > BATCHED_MAXN) { c->err = std::string(who) + ": n > 128 is not a small matrix: use " + use + " on one matrix at a time"; return -1; }
+    return 0;
+}
+
+int mpf_lange_batched(mpf_ctx *c, char norm, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_out) {
+    if (!c) return -1;
+    int rc = check_sizes_refine(c, "lange_batched", n, batch, "mpf_lange (and mpf_gecon / mpf_gerfs)");
+    if (rc) return rc;
+    int mode;
+    if (norm == '1' || norm == 'O' || norm == 'o') mode = 0;
+    else if (norm == 'I' || norm == 'i') mode = 1;
+    else if (norm == 'M' || norm == 'm') mode = 2;
+    else { c->err = "lange_batched: norm must be '1', 'O', 'I' or 'M'"; return -1; }
+    if (n == 0 || batch == 0) return 0;
+    rc = check_strided(c, "lange_batched", "A", lda, strideA, n, n, batch);
+    if (rc) return rc;
+    if (!d_A || !d_out) { c->err = "lange_batched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
+        const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
+        rc = launch_lange_batched(c, mode, d_A + b0 * strideA, lda, strideA, n, nb, d_out + b0);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_gecon_batched(mpf_ctx *c, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                      const double *d_anorm, double *d_rcond, double *d_ainvnm) {
+    if (!c) return -1;
+    int rc = check_sizes_refine(c, "gecon_batched", n, batch, "mpf_gecon (and mpf_gerfs)");
+    if (rc) return rc;
+    const bool one = norm == '1' || norm == 'O' || norm == 'o';
+    if (!one && norm != 'I' && norm != 'i') { c->err = "gecon_batched: norm must be '1', 'O' or 'I'"; return -1; }
+    if (n == 0 || batch == 0) return 0;
+    rc = check_strided(c, "gecon_batched", "LU", ldlu, strideLU, n, n, batch);
+    if (rc) return rc;
+    if (!d_LU || !d_anorm || !d_rcond) { c->err = "gecon_batched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
+        const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
+        rc = launch_gecon_batched(c, one ? 0 : 1, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_anorm + b0, d_rcond + b0,
+                                  d_ainvnm ? d_ainvnm + b0 : nullptr);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_residual_batched(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t nrhs,
+                         const double *d_X, int64_t ldx, int64_t strideX, const double *d_B, int64_t ldb, int64_t strideB, double *d_R,
+                         int64_t ldr, int64_t strideR, double *d_W) {
+    if (!c) return -1;
+    int rc = check_sizes_refine(c, "residual_batched", n, batch, "mpf_gerfs (and mpf_gecon)");
+    if (rc) return rc;
+    if (nrhs < 0) { c->err = "residual_batched: nrhs must not be negative"; return -1; }
+    if (trans != 0 && trans != 1) { c->err = "residual_batched: trans must be 0 or 1"; return -1; }
+    if (n == 0 || batch == 0 || nrhs == 0) return 0;
+    rc = check_strided(c, "residual_batched", "A", lda, strideA, n, n, batch);
+    if (!rc) rc = check_strided(c, "residual_batched", "X", ldx, strideX, n, nrhs, batch);
+    if (!rc) rc = check_strided(c, "residual_batched", "B", ldb, strideB, n, nrhs, batch);
+    if (!rc) rc = check_strided(c, "residual_batched", "R", ldr, strideR, n, nrhs, batch);
+    if (rc) return rc;
+    if (!d_A || !d_X || !d_B || !d_R) { c->err = "residual_batched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    int64_t step = BR_MAX_UNITS / nrhs;
+    if (step > BT_MAX_LAUNCH) step = BT_MAX_LAUNCH;
+    for (int64_t b0 = 0; b0 < batch; b0 += step) {
+        const int64_t nb = batch - b0 < step ? batch - b0 : step;
+        rc = launch_residual_batched(c, trans, d_A + b0 * strideA, lda, strideA, n, nb, nrhs, d_X + b0 * strideX, ldx, strideX,
+                                     d_B + b0 * strideB, ldb, strideB, d_R + b0 * strideR, ldr, strideR, d_W ? d_W + b0 * strideR : nullptr);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_gerfs_batched(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, const double *d_LU, int64_t ldlu,
+                      int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, const double *d_B,
+                      int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t itmax, double *d_ferr, double *d_berr,
+                      int32_t *d_iters) {
+    if (!c) return -1;
+    int rc = check_sizes_refine(c, "gerfs_batched", n, batch, "mpf_gerfs (and mpf_gecon)");
+    if (rc) return rc;
+    if (batch > 1 && strideP < n) { c->err = "gerfs_batched: stride of ipiv < n"; return -1; }
+    if (nrhs < 0) { c->err = "gerfs_batched: nrhs must not be negative"; return -1; }
+    if (trans != 0 && trans != 1) { c->err = "gerfs_batched: trans must be 0 or 1"; return -1; }
+    if (n == 0 || batch == 0 || nrhs == 0) return 0;
+    rc = check_strided(c, "gerfs_batched", "A", lda, strideA, n, n, batch);
+    if (!rc) rc = check_strided(c, "gerfs_batched", "LU", ldlu, strideLU, n, n, batch);
+    if (!rc) rc = check_strided(c, "gerfs_batched", "B", ldb, strideB, n, nrhs, batch);
+    if (!rc) rc = check_strided(c, "gerfs_batched", "X", ldx, strideX, n, nrhs, batch);
+    if (rc) return rc;
+    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !d_berr) { c->err = "gerfs_batched: null pointer"; return -1; }
+    const int it = itmax <= 0 ? 5 : (itmax > 31 ? 31 : itmax);   // mpf_gerfs's rule
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
+        const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
+        rc = launch_gerfs_batched(c, trans, d_A + b0 * strideA, lda, strideA, d_LU + b0 * strideLU, ldlu, strideLU, n, nb,
+                                  d_ipiv + b0 * strideP, strideP, nrhs, d_B + b0 * strideB, ldb, strideB, d_X + b0 * strideX, ldx, strideX, it,
+                                  d_ferr ? d_ferr + b0 * nrhs : nullptr, d_berr + b0 * nrhs, d_iters ? d_iters + b0 * nrhs : nullptr);
         if (rc) return rc;
     }
     return 0;

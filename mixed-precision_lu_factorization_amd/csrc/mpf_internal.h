@@ -286,7 +286,7 @@ inline int fail(mpf_ctx *c, int code, const std::string &msg) {
     return code;
 }
 
-enum { ATTR_HP = 1, ATTR_DGEMM = 2, ATTR_HGEMM = 4, ATTR_HGEMM256 = 8, ATTR_HGEMM_PP = 16, ATTR_HGEMM16_BIG32 = 32, ATTR_HGEMM16_BIG64 = 64, ATTR_BATCHED = 128, ATTR_VBATCHED = 256 };
+enum { ATTR_HP = 1, ATTR_DGEMM = 2, ATTR_HGEMM = 4, ATTR_HGEMM256 = 8, ATTR_HGEMM_PP = 16, ATTR_HGEMM16_BIG32 = 32, ATTR_HGEMM16_BIG64 = 64, ATTR_BATCHED = 128, ATTR_VBATCHED = 256, ATTR_BATCHED_REFINE = 512 };
 inline bool safe_pivots(const mpf_ctx *c) { return c->tune.safe_pivots != 0; }
 
 // ---- launchers implemented in the .hip files (all asynchronous on `s`) -----------------------
@@ -540,6 +540,20 @@ int launch_getri_batched(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t str
                          double *inv, int64_t ldinv, int64_t strideInv, int *info);
 int launch_getdet_batched(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv, int64_t strideP,
                           double *mant, int *expo);
+// The expert layer on the same strided batches (batched_refine.hip; checks and chunks in mpf_batched.cpp), 1 <= n <= 128, one launch each.
+// launch_lange_batched: mode 0 = '1', 1 = 'I', 2 = 'M'.  launch_gecon_batched: the exact norm of (L U)^-1 (inf = 0: '1', 1: 'I'), rcond
+// and, when not null, ainvnm per matrix.  launch_residual_batched: at most BR_MAX_UNITS (matrix, column) pairs; W may be null.
+// launch_gerfs_batched: itmax already resolved (1 .. 31); ferr and iters may be null.
+constexpr int64_t BR_MAX_UNITS = 1 << 30;
+int launch_lange_batched(mpf_ctx *c, int mode, const double *A, int64_t lda, int64_t strideA, int n, int64_t batch, double *out);
+int launch_gecon_batched(mpf_ctx *c, int inf, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const double *anorm,
+                         double *rcond, double *ainvnm);
+int launch_residual_batched(mpf_ctx *c, int trans, const double *A, int64_t lda, int64_t strideA, int n, int64_t batch, int nrhs,
+                            const double *X, int64_t ldx, int64_t strideX, const double *B, int64_t ldb, int64_t strideB, double *R,
+                            int64_t ldr, int64_t strideR, double *W);
+int launch_gerfs_batched(mpf_ctx *c, int trans, const double *A, int64_t lda, int64_t strideA, const double *LU, int64_t ldlu,
+                         int64_t strideLU, int n, int64_t batch, const int *ipiv, int64_t strideP, int nrhs, const double *B, int64_t ldb,
+                         int64_t strideB, double *X, int64_t ldx, int64_t strideX, int itmax, double *ferr, double *berr, int *iters);
 // The same for matrices of different orders (vbatched.hip; descriptor and chunks in mpf_batched.cpp, host plan in vbatch_plan.h): one
 // launch each on `count` <= BT_MAX_LAUNCH entries of one class list.  BtRagged: the descriptor's device arrays, indexed by matrix;
 // idx[i] = the matrix of list entry i; top = the class's largest order (8, 16, 32: wave forms; 48, 64, 96, 128: workgroup forms),
