@@ -684,7 +684,8 @@ int mpf_getdet(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, const int32_t *d_
  * launch (csrc/batched.hip).  fp64 only, LAPACK partial pivoting: the fp16-image pivot rule and the fp16 trailing modes have no meaning
  * at these sizes.  No driver uses them; the inverse and the determinant from the factors are mpf_getri_batched and mpf_getdet_batched
  * below; matrices of different orders in one call: the mpf_*_vbatched entries after them; refinement, error bounds and rcond for these
- * batches: the mpf_*_batched expert entries after mpf_getdet_batched (there is none for the blocked or the vbatched forms).
+ * batches: the mpf_*_batched expert entries after mpf_getdet_batched, and for one order up to 1024 the mpf_*_batched_blocked expert
+ * entries after mpf_getdet_batched_blocked (there is none for the vbatched forms).
  *
  * Layout: A[b] = d_A + b * strideA, n x n column-major, lda >= n, strideA >= lda * n (or batch == 1);
  * ipiv[b] = d_ipiv + b * strideP, strideP >= n (or batch == 1), 1-based as LAPACK; d_info: batch int32 on the device, optional.
@@ -820,8 +821,8 @@ int mpf_gerfs_batched(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t ld
 /* ---- the same for ONE order up to 1024 (blocked; csrc/batched_blocked.hip) ----------------------------------------------------------------
  * mpf_getrf_batched and mpf_getrs_batched above stop at n = 128, where a matrix still fits one workgroup's LDS, and stay as they are.
  * These take 0 <= n <= 1024 with the same layout, argument checks, error style and asynchrony, and mpf_getri_batched_blocked and
- * mpf_getdet_batched_blocked below do the same for mpf_getri_batched and mpf_getdet_batched; fp64 only, one n per call, no refinement
- * above 128, no driver uses them.  Matrices of different orders up to 1024 in one call: a descriptor from mpf_vbatch_create_blocked
+ * mpf_getdet_batched_blocked below do the same for mpf_getri_batched and mpf_getdet_batched; fp64 only, one n per call, no driver
+ * uses them; refinement, error bounds and rcond above 128: the mpf_*_batched_blocked expert entries after mpf_getdet_batched_blocked.  Matrices of different orders up to 1024 in one call: a descriptor from mpf_vbatch_create_blocked
  * below (the descriptor from mpf_vbatch_create stays at n <= 128).
  *
  * Factorization.  mpf_getrf_batched's contract, word for word, with the larger limit: for every b, A[b], ipiv[b][0 .. n-1] and
@@ -875,6 +876,48 @@ int mpf_getri_batched_blocked(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, in
  * (n > 1024: use mpf_factor_dev and mpf_getdet). */
 int mpf_getdet_batched_blocked(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                                const int32_t *d_ipiv, int64_t strideP, double *d_mant, int32_t *d_expo);
+/* The expert layer for ONE order up to 1024 (csrc/batched_refine_blocked.hip): mpf_lange_batched, mpf_gecon_batched,
+ * mpf_residual_batched and mpf_gerfs_batched above with 0 <= n <= 1024 -- the argument lists word for word, the layout rules, checks,
+ * error style and asynchrony of mpf_getrs_batched_blocked, the factors and pivots mpf_getrf_batched_blocked leaves.  Everything runs on
+ * the device in ordinary launches on the context's stream, nothing is read back, no kernel waits for another workgroup and nothing
+ * spins; rows n .. ld-1 and the bytes between matrices are neither read nor written; batches above 32768 go in chunks.
+ * The contract is the small layer's with the larger limit (tests/batched_refine_blocked_model.py restates every entry in numpy):
+ *   tree sum   the halving tree on the terms padded with +0 to 1024: v[0..511] + v[512..1023], then + 256, .. + 1.  Every term is
+ *              >= +0, so padding to any power of two >= n gives the same bits: for n <= 128 this IS the tree padded to 128.
+ *   maxima     order-free; a NaN among the terms gives NaN.
+ *   fusion     every multiply-subtract and multiply-add is unfused.
+ *   constants  mpf_gerfs's, nz = n + 1.
+ *   lange      '1' / 'O', 'I', 'M' as mpf_lange_batched; any other letter: -1.
+ *   gecon      no P.  '1': the columns the trans = 0 chains of mpf_getrs_batched_blocked leave for e_k without interchanges; 'I': the
+ *              vectors its trans = 1 chains leave for e_i.  rcond = 0, never NaN, for anorm == 0, a zero on U's diagonal (checked before
+ *              any arithmetic; ainvnm is then +Inf) or an ainvnm that is not finite (or 0).  d_ainvnm is optional.
+ *   residual   r_i from b_i, op(A)_ij x_j subtracted for j ascending; w_i from |b_i|, |op(A)_ij| |x_j| added; one pass over A serves
+ *              both; trans 0 or 1; d_R may be d_B, d_R and d_W must not overlap d_A or d_X.
+ *   gerfs      mpf_gerfs_batched's rule, stop reasons, itmax (<= 0 means 5, clamped to 31) and outputs (berr, optional ferr and iters
+ *              at b * nrhs + c).  The correction is the chain of mpf_getrs_batched_blocked with the same trans applied to r; ferr
+ *              comes from the last r and w with the chains of the other trans for every e_i, interchanges included, as a tree over k
+ *              of |y_k| g_k (the product rounded before the sum).  A NaN stops its column with berr = NaN and touches no neighbour.
+ * A kernel may skip steps that meet only zeros, as mpf_getri_batched_blocked does (finite factors; the sign of a zero reaches no
+ * | |).  A matrix's and a column's results depend on nothing but its own data: not on batch, position, nrhs, any ld or stride, a
+ * tile width or the path (n <= 128 and n < option batched_blocked_min_n: handed to the entry above).  For n <= 128 the results equal
+ * the small entries' bit for bit; two calls give the same bits.
+ * Workspace (the context's, grow-only): gecon one double per (matrix, tile of 16 chains); gerfs with d_ferr n + 1 doubles per
+ * (matrix, column) and one per (matrix, column, tile), at most 256 MB: a call with d_ferr goes in chunks of as many matrices as fit
+ * (and at most 32768).  Nothing is proportional to n^2.
+ * Return 0, or < 0 with a message (n > 1024: use mpf_lange, mpf_gecon / mpf_gerfs on one matrix at a time; negative sizes, a bad
+ * letter or trans, leading dimensions < n, strides too small, NULL pointers).  n == 0, batch == 0 or nrhs == 0: 0, no work. */
+int mpf_lange_batched_blocked(mpf_ctx *ctx, char norm, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                              double *d_out /* device, batch */);
+int mpf_gecon_batched_blocked(mpf_ctx *ctx, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                              const double *d_anorm /* device, batch */, double *d_rcond /* device, batch */,
+                              double *d_ainvnm /* optional: device, batch */);
+int mpf_residual_batched_blocked(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                                 int32_t nrhs, const double *d_X, int64_t ldx, int64_t strideX, const double *d_B, int64_t ldb,
+                                 int64_t strideB, double *d_R, int64_t ldr, int64_t strideR, double *d_W /* optional */);
+int mpf_gerfs_batched_blocked(mpf_ctx *ctx, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, const double *d_LU,
+                              int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv, int64_t strideP,
+                              int32_t nrhs, const double *d_B, int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX,
+                              int32_t itmax, double *d_ferr /* optional */, double *d_berr, int32_t *d_iters /* optional */);
 
 /* ---- the same for matrices of DIFFERENT orders (vbatched; csrc/vbatched.hip, host plan in csrc/vbatch_plan.h) ---------------------------
  * One descriptor says where `batch` matrices of orders 0 <= n[b] <= 128 lie inside ONE allocation; four entry points then factor, solve,

@@ -42,6 +42,7 @@ C_ABI_SYMBOLS = [
     "mpf_lange_batched", "mpf_gecon_batched", "mpf_residual_batched", "mpf_gerfs_batched",
     "mpf_getrf_batched_blocked", "mpf_getrs_batched_blocked",
     "mpf_getri_batched_blocked", "mpf_getdet_batched_blocked",
+    "mpf_lange_batched_blocked", "mpf_gecon_batched_blocked", "mpf_residual_batched_blocked", "mpf_gerfs_batched_blocked",
     "mpf_vbatch_create", "mpf_vbatch_create_blocked", "mpf_vbatch_destroy", "mpf_vbatch_info", "mpf_vbatch_offsets",
     "mpf_getrf_vbatched", "mpf_getrs_vbatched", "mpf_getri_vbatched", "mpf_getdet_vbatched",
 ]
@@ -223,6 +224,10 @@ def load_library(probe=False):
     L.mpf_residual_batched.argtypes = [vp, i32, vp, i64, i64, i32, i64, i32, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp]
     L.mpf_gerfs_batched.argtypes = [vp, i32, vp, i64, i64, vp, i64, i64, i32, i64, vp, i64, i32, vp, i64, i64, vp, i64, i64, i32, vp, vp, vp]
     L.mpf_getdet_batched_blocked.argtypes = L.mpf_getdet_batched.argtypes
+    L.mpf_lange_batched_blocked.argtypes = L.mpf_lange_batched.argtypes
+    L.mpf_gecon_batched_blocked.argtypes = L.mpf_gecon_batched.argtypes
+    L.mpf_residual_batched_blocked.argtypes = L.mpf_residual_batched.argtypes
+    L.mpf_gerfs_batched_blocked.argtypes = L.mpf_gerfs_batched.argtypes
     L.mpf_vbatch_create.argtypes = [vp, i64, vp, vp, vp, C.POINTER(vp)]
     L.mpf_vbatch_create_blocked.argtypes = L.mpf_vbatch_create.argtypes
     L.mpf_vbatch_destroy.argtypes = [vp]
@@ -1138,52 +1143,61 @@ class MPFContext:
     def lange_batched(self, A, norm="1"):
         """mpf_lange_batched: the '1' / 'O', 'I' or 'M' norm of every matrix of the (batch, n, n) tensor A, n <= 128, as a float64
         (batch,) device tensor; sums are the header's halving tree, a NaN in a matrix gives NaN for it."""
+        return self._lange_batched(A, norm, "lange_batched")
+
+    def _lange_batched(self, A, norm, entry):
         self._bind()
         t = self.torch
         assert A.dim() == 3 and A.shape[1] == A.shape[2], "A: (batch, n, n)"
         batch, n = A.shape[0], A.shape[1]
-        Am, lda, sa = self._batch_arg(A, "lange_batched", False, copy=False)
+        Am, lda, sa = self._batch_arg(A, entry, False, copy=False)
         out = t.zeros(batch, dtype=t.float64, device=self.device)
-        self._check(self.L.mpf_lange_batched(self.h, norm.encode()[:1], _ptr(Am), lda, sa, n, batch, _ptr(out)), "mpf_lange_batched")
+        self._check(getattr(self.L, "mpf_" + entry)(self.h, norm.encode()[:1], _ptr(Am), lda, sa, n, batch, _ptr(out)), "mpf_" + entry)
         return out
 
     def gecon_batched(self, LU, anorm, norm="1", want_ainvnm=False):
         """mpf_gecon_batched: rcond[b] = (1 / ||(L U)^-1||) / anorm[b] from getrf_batched's factors, the norm of the inverse computed
         exactly (not dgecon's estimate).  anorm: a float64 (batch,) device tensor (lange_batched of the matrices, same norm).
         Returns rcond, or (rcond, ainvnm) with want_ainvnm; rcond is 0 for anorm 0, a zero on U's diagonal or a non-finite inverse."""
+        return self._gecon_batched(LU, anorm, norm, want_ainvnm, "gecon_batched")
+
+    def _gecon_batched(self, LU, anorm, norm, want_ainvnm, entry):
         self._bind()
         t = self.torch
         assert LU.dim() == 3 and LU.shape[1] == LU.shape[2], "LU: (batch, n, n)"
         batch, n = LU.shape[0], LU.shape[1]
-        LUm, ldlu, slu = self._batch_arg(LU, "gecon_batched", False, copy=False)
+        LUm, ldlu, slu = self._batch_arg(LU, entry, False, copy=False)
         assert anorm.dtype == t.float64 and anorm.is_cuda and anorm.shape == (batch,)
         anorm = anorm.contiguous()
         rcond = t.zeros(batch, dtype=t.float64, device=self.device)
         ainv = t.zeros(batch, dtype=t.float64, device=self.device) if want_ainvnm else None
-        rc = self.L.mpf_gecon_batched(self.h, norm.encode()[:1], _ptr(LUm), ldlu, slu, n, batch, _ptr(anorm), _ptr(rcond),
-                                      _ptr(ainv) if want_ainvnm else None)
-        self._check(rc, "mpf_gecon_batched")
+        rc = getattr(self.L, "mpf_" + entry)(self.h, norm.encode()[:1], _ptr(LUm), ldlu, slu, n, batch, _ptr(anorm), _ptr(rcond),
+                                             _ptr(ainv) if want_ainvnm else None)
+        self._check(rc, "mpf_" + entry)
         return (rcond, ainv) if want_ainvnm else rcond
 
     def residual_batched(self, A, X, B, trans=False, want_w=True):
         """mpf_residual_batched: (R, W) with R[b] = B[b] - op(A[b]) X[b] and W[b] = |B[b]| + |op(A[b])| |X[b]| (W None without
         want_w), new column-major tensors; X and B are (batch, n, nrhs), or (batch, n) for one column each."""
+        return self._residual_batched(A, X, B, trans, want_w, "residual_batched")
+
+    def _residual_batched(self, A, X, B, trans, want_w, entry):
         self._bind()
         if B.dim() == 2:
-            R, W = self.residual_batched(A, X.unsqueeze(2), B.unsqueeze(2), trans, want_w)
+            R, W = self._residual_batched(A, X.unsqueeze(2), B.unsqueeze(2), trans, want_w, entry)
             return R.squeeze(2), (W.squeeze(2) if want_w else None)
         assert A.dim() == 3 and A.shape[1] == A.shape[2] and B.dim() == 3 and B.shape[:2] == A.shape[:2] and X.shape == B.shape, \
             "A: (batch, n, n), X and B: (batch, n, nrhs)"
         batch, n, nrhs = B.shape
-        Am, lda, sa = self._batch_arg(A, "residual_batched", False, copy=False)
-        Xm, ldx, sx = self._batch_arg(X, "residual_batched", False, copy=False)
-        Bm, ldb, sb = self._batch_arg(B, "residual_batched", False, copy=False)
+        Am, lda, sa = self._batch_arg(A, entry, False, copy=False)
+        Xm, ldx, sx = self._batch_arg(X, entry, False, copy=False)
+        Bm, ldb, sb = self._batch_arg(B, entry, False, copy=False)
         R = self.colmajor_batch(batch, n, nrhs)
         W = self.colmajor_batch(batch, n, nrhs) if want_w else None
         ldr, sr = self._batch_layout(R)
-        rc = self.L.mpf_residual_batched(self.h, int(bool(trans)), _ptr(Am), lda, sa, n, batch, nrhs, _ptr(Xm), ldx, sx, _ptr(Bm), ldb, sb,
-                                         _ptr(R), ldr, sr, _ptr(W) if want_w else None)
-        self._check(rc, "mpf_residual_batched")
+        rc = getattr(self.L, "mpf_" + entry)(self.h, int(bool(trans)), _ptr(Am), lda, sa, n, batch, nrhs, _ptr(Xm), ldx, sx, _ptr(Bm), ldb,
+                                             sb, _ptr(R), ldr, sr, _ptr(W) if want_w else None)
+        self._check(rc, "mpf_" + entry)
         return R, W
 
     def gerfs_batched(self, A, LU, ipiv, B, X, trans=False, itmax=0, overwrite=False, want_ferr=True):
@@ -1191,43 +1205,52 @@ class MPFContext:
         is refined: a new column-major tensor, or X itself with overwrite=True (column-major matrices).  Returns (X, ferr, berr,
         iters): float64 / int32 (batch, nrhs) device tensors (ferr None without want_ferr).  ferr bounds max_i |x_i - xtrue_i| /
         max_i |x_i| with the exact norm where dgerfs estimates it."""
+        return self._gerfs_batched(A, LU, ipiv, B, X, trans, itmax, overwrite, want_ferr, "gerfs_batched")
+
+    def _gerfs_batched(self, A, LU, ipiv, B, X, trans, itmax, overwrite, want_ferr, entry):
         self._bind()
         t = self.torch
         if B.dim() == 2:
-            Xr, ferr, berr, its = self.gerfs_batched(A, LU, ipiv, B.unsqueeze(2), X.unsqueeze(2), trans, itmax, overwrite, want_ferr)
+            Xr, ferr, berr, its = self._gerfs_batched(A, LU, ipiv, B.unsqueeze(2), X.unsqueeze(2), trans, itmax, overwrite, want_ferr, entry)
             return Xr.squeeze(2), ferr, berr, its
         assert A.dim() == 3 and A.shape[1] == A.shape[2] and B.dim() == 3 and B.shape[:2] == A.shape[:2] and X.shape == B.shape, \
             "A: (batch, n, n), B and X: (batch, n, nrhs)"
         assert LU.shape == A.shape
         nrhs = B.shape[2]
-        Am, lda, sa = self._batch_arg(A, "gerfs_batched", False, copy=False)
-        LUm, ldlu, slu, ipiv, sp, batch, n = self._batch_factors(LU, ipiv, "gerfs_batched")
-        Bm, ldb, sb = self._batch_arg(B, "gerfs_batched", False, copy=False)
-        Xm, ldx, sx = self._batch_arg(X, "gerfs_batched", overwrite)
+        Am, lda, sa = self._batch_arg(A, entry, False, copy=False)
+        LUm, ldlu, slu, ipiv, sp, batch, n = self._batch_factors(LU, ipiv, entry)
+        Bm, ldb, sb = self._batch_arg(B, entry, False, copy=False)
+        Xm, ldx, sx = self._batch_arg(X, entry, overwrite)
         ferr = t.zeros((batch, nrhs), dtype=t.float64, device=self.device) if want_ferr else None
         berr = t.zeros((batch, nrhs), dtype=t.float64, device=self.device)
         its = t.zeros((batch, nrhs), dtype=t.int32, device=self.device)
-        rc = self.L.mpf_gerfs_batched(self.h, int(bool(trans)), _ptr(Am), lda, sa, _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp, nrhs,
-                                      _ptr(Bm), ldb, sb, _ptr(Xm), ldx, sx, int(itmax), _ptr(ferr) if want_ferr else None, _ptr(berr),
-                                      _ptr(its))
-        self._check(rc, "mpf_gerfs_batched")
+        rc = getattr(self.L, "mpf_" + entry)(self.h, int(bool(trans)), _ptr(Am), lda, sa, _ptr(LUm), ldlu, slu, n, batch, _ptr(ipiv), sp,
+                                             nrhs, _ptr(Bm), ldb, sb, _ptr(Xm), ldx, sx, int(itmax), _ptr(ferr) if want_ferr else None,
+                                             _ptr(berr), _ptr(its))
+        self._check(rc, "mpf_" + entry)
         return Xm, ferr, berr, its
 
     def cond_batched(self, A, norm="1"):
         """rcond of every matrix of the (batch, n, n) tensor A, n <= 128: getrf_batched on a copy, lange_batched, gecon_batched.  0
         for a singular matrix; nothing is read back."""
-        LU, _, _ = self.getrf_batched(A)
-        return self.gecon_batched(LU, self.lange_batched(A, norm), norm)
+        return self._cond_batched(A, norm, "")
+
+    def _cond_batched(self, A, norm, suffix):
+        LU, _, _ = getattr(self, "getrf_batched" + suffix)(A)
+        return getattr(self, "gecon_batched" + suffix)(LU, getattr(self, "lange_batched" + suffix)(A, norm), norm)
 
     def solvex_batched(self, A, B, trans=False, itmax=0):
         """dgesvx's shape without equilibration for a batch, n <= 128: getrf_batched on a copy, lange_batched / gecon_batched (the
         '1' norm, or 'I' with trans), getrs_batched, gerfs_batched.  Returns (X, rcond, ferr, berr, info), all on the device; never
         raises on a singular matrix: info[b] is its first zero pivot and rcond[b] is 0 (its X, ferr and berr are not meaningful)."""
+        return self._solvex_batched(A, B, trans, itmax, "")
+
+    def _solvex_batched(self, A, B, trans, itmax, suffix):
         norm = "I" if trans else "1"
-        LU, ipiv, info = self.getrf_batched(A)
-        rcond = self.gecon_batched(LU, self.lange_batched(A, norm), norm)
-        X = self.getrs_batched(LU, ipiv, B, trans=trans)
-        X, ferr, berr, _ = self.gerfs_batched(A, LU, ipiv, B, X, trans=trans, itmax=itmax, overwrite=True)
+        LU, ipiv, info = getattr(self, "getrf_batched" + suffix)(A)
+        rcond = getattr(self, "gecon_batched" + suffix)(LU, getattr(self, "lange_batched" + suffix)(A, norm), norm)
+        X = getattr(self, "getrs_batched" + suffix)(LU, ipiv, B, trans=trans)
+        X, ferr, berr, _ = getattr(self, "gerfs_batched" + suffix)(A, LU, ipiv, B, X, trans=trans, itmax=itmax, overwrite=True)
         return X, rcond, ferr, berr, info
 
     # ---- the same for one order up to 1024 (include/mpf_c.h: mpf_getrf_batched_blocked, mpf_getrs_batched_blocked) ------------------------
@@ -1351,6 +1374,35 @@ class MPFContext:
     def slogdet_batched_blocked(self, A_or_LU, ipiv=None):
         """slogdet_batched for n <= 1024: from getdet_batched_blocked (and getrf_batched_blocked when ipiv is None)."""
         return self._slogdet_batched(A_or_LU, ipiv, "_blocked")
+
+    # ---- the expert layer for one order up to 1024 (include/mpf_c.h: mpf_lange_batched_blocked, mpf_gecon_batched_blocked, ...) ---------
+    def lange_batched_blocked(self, A, norm="1"):
+        """mpf_lange_batched_blocked: lange_batched for n <= 1024 -- the same arguments, results and bits (the tree padded to 1024)."""
+        return self._lange_batched(A, norm, "lange_batched_blocked")
+
+    def gecon_batched_blocked(self, LU, anorm, norm="1", want_ainvnm=False):
+        """mpf_gecon_batched_blocked: gecon_batched for n <= 1024 with the factors of getrf_batched_blocked; the norm of the inverse is
+        exact, its chains are reduced on the fly and never stored (no n x n workspace)."""
+        return self._gecon_batched(LU, anorm, norm, want_ainvnm, "gecon_batched_blocked")
+
+    def residual_batched_blocked(self, A, X, B, trans=False, want_w=True):
+        """mpf_residual_batched_blocked: residual_batched for n <= 1024."""
+        return self._residual_batched(A, X, B, trans, want_w, "residual_batched_blocked")
+
+    def gerfs_batched_blocked(self, A, LU, ipiv, B, X, trans=False, itmax=0, overwrite=False, want_ferr=True):
+        """mpf_gerfs_batched_blocked: gerfs_batched for n <= 1024 with the factors of getrf_batched_blocked and a solution from
+        getrs_batched_blocked; the same rule, outputs and, for n <= 128, bits."""
+        return self._gerfs_batched(A, LU, ipiv, B, X, trans, itmax, overwrite, want_ferr, "gerfs_batched_blocked")
+
+    def cond_batched_blocked(self, A, norm="1"):
+        """rcond of every matrix of the (batch, n, n) tensor A, n <= 1024: getrf_batched_blocked on a copy, lange_batched_blocked,
+        gecon_batched_blocked.  0 for a singular matrix; nothing is read back."""
+        return self._cond_batched(A, norm, "_blocked")
+
+    def solvex_batched_blocked(self, A, B, trans=False, itmax=0):
+        """solvex_batched for n <= 1024 from the blocked entries.  Returns (X, rcond, ferr, berr, info), all on the device; never
+        raises on a singular matrix: info[b] is its first zero pivot and rcond[b] is 0."""
+        return self._solvex_batched(A, B, trans, itmax, "_blocked")
 
 
     # ---- the same for matrices of different orders (include/mpf_c.h: mpf_vbatch_create, mpf_getrf_vbatched, ...) --------------------------

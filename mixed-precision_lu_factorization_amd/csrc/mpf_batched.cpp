@@ -11,6 +11,8 @@
 //   mpf_getrf_batched_blocked, mpf_getrs_batched_blocked   the first two for one n <= 1024: the same bits from a right-looking blocked
 //                       loop (batched_blocked.hip), three launches per panel step for the whole batch
 //   mpf_getri_batched_blocked, mpf_getdet_batched_blocked   the other two for one n <= 1024: one launch each, no workspace
+//   mpf_lange_batched_blocked, mpf_gecon_batched_blocked, mpf_residual_batched_blocked, mpf_gerfs_batched_blocked   the expert layer for
+//                       one n <= 1024 (batched_refine_blocked.hip): the small layer's arguments, rules and, for n <= 128, bits
 // The same four for matrices of different orders (mpf_*_vbatched) on a descriptor, mpf_vbatch: the host plan of vbatch_plan.h (checks,
 // prefix sums, size classes) uploaded once; each call then launches one ragged kernel of vbatched.hip per class that is not empty.
 // A descriptor from mpf_vbatch_create_blocked (orders up to 1024) also has the plan's large list: its matrices take the ragged blocked
@@ -348,6 +350,132 @@ int mpf_getdet_batched_blocked(mpf_ctx *c, const double *d_LU, int64_t ldlu, int
         const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
         rc = launch_getdet_batched_blocked(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0,
                                            d_expo + b0);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---- the expert layer, one n <= 1024 per call (kernels in batched_refine_blocked.hip) ---------------------------------------------------
+// The checks of the n <= 128 entries in their order with the larger limit; n below option batched_blocked_min_n (and <= 128) goes to
+// those entries, whose bits are the same by contract.
+static int check_sizes_refine_blocked(mpf_ctx *c, const char *who, int32_t n, int64_t batch) {
+    if (n < 0 || batch < 0) { c->err = std::string(who) + ": n and batch must not be negative"; return -1; }
+    if (n > BB_MAXN) {
+        c->err = std::string(who) + ": n > 1024 is not a batch-sized matrix: use mpf_lange, mpf_gecon / mpf_gerfs on one matrix at a time";
+        return -1;
+    }
+    return 0;
+}
+
+int mpf_lange_batched_blocked(mpf_ctx *c, char norm, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_out) {
+    if (!c) return -1;
+    int rc = check_sizes_refine_blocked(c, "lange_batched_blocked", n, batch);
+    if (rc) return rc;
+    int mode;
+    if (norm == '1' || norm == 'O' || norm == 'o') mode = 0;
+    else if (norm == 'I' || norm == 'i') mode = 1;
+    else if (norm == 'M' || norm == 'm') mode = 2;
+    else { c->err = "lange_batched_blocked: norm must be '1', 'O', 'I' or 'M'"; return -1; }
+    if (n == 0 || batch == 0) return 0;
+    rc = check_strided(c, "lange_batched_blocked", "A", lda, strideA, n, n, batch);
+    if (rc) return rc;
+    if (!d_A || !d_out) { c->err = "lange_batched_blocked: null pointer"; return -1; }
+    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n) return mpf_lange_batched(c, norm, d_A, lda, strideA, n, batch, d_out);
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
+        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
+        rc = launch_lange_batched_blocked(c, mode, d_A + b0 * strideA, lda, strideA, n, nb, d_out + b0);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_gecon_batched_blocked(mpf_ctx *c, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                              const double *d_anorm, double *d_rcond, double *d_ainvnm) {
+    if (!c) return -1;
+    int rc = check_sizes_refine_blocked(c, "gecon_batched_blocked", n, batch);
+    if (rc) return rc;
+    const bool one = norm == '1' || norm == 'O' || norm == 'o';
+    if (!one && norm != 'I' && norm != 'i') { c->err = "gecon_batched_blocked: norm must be '1', 'O' or 'I'"; return -1; }
+    if (n == 0 || batch == 0) return 0;
+    rc = check_strided(c, "gecon_batched_blocked", "LU", ldlu, strideLU, n, n, batch);
+    if (rc) return rc;
+    if (!d_LU || !d_anorm || !d_rcond) { c->err = "gecon_batched_blocked: null pointer"; return -1; }
+    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
+        return mpf_gecon_batched(c, norm, d_LU, ldlu, strideLU, n, batch, d_anorm, d_rcond, d_ainvnm);
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
+        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
+        rc = launch_gecon_batched_blocked(c, one ? 0 : 1, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_anorm + b0, d_rcond + b0,
+                                          d_ainvnm ? d_ainvnm + b0 : nullptr);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_residual_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                                 int32_t nrhs, const double *d_X, int64_t ldx, int64_t strideX, const double *d_B, int64_t ldb, int64_t strideB,
+                                 double *d_R, int64_t ldr, int64_t strideR, double *d_W) {
+    if (!c) return -1;
+    int rc = check_sizes_refine_blocked(c, "residual_batched_blocked", n, batch);
+    if (rc) return rc;
+    if (nrhs < 0) { c->err = "residual_batched_blocked: nrhs must not be negative"; return -1; }
+    if (trans != 0 && trans != 1) { c->err = "residual_batched_blocked: trans must be 0 or 1"; return -1; }
+    if (n == 0 || batch == 0 || nrhs == 0) return 0;
+    rc = check_strided(c, "residual_batched_blocked", "A", lda, strideA, n, n, batch);
+    if (!rc) rc = check_strided(c, "residual_batched_blocked", "X", ldx, strideX, n, nrhs, batch);
+    if (!rc) rc = check_strided(c, "residual_batched_blocked", "B", ldb, strideB, n, nrhs, batch);
+    if (!rc) rc = check_strided(c, "residual_batched_blocked", "R", ldr, strideR, n, nrhs, batch);
+    if (rc) return rc;
+    if (!d_A || !d_X || !d_B || !d_R) { c->err = "residual_batched_blocked: null pointer"; return -1; }
+    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
+        return mpf_residual_batched(c, trans, d_A, lda, strideA, n, batch, nrhs, d_X, ldx, strideX, d_B, ldb, strideB, d_R, ldr, strideR, d_W);
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
+        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
+        rc = launch_residual_batched_blocked(c, trans, d_A + b0 * strideA, lda, strideA, n, nb, nrhs, d_X + b0 * strideX, ldx, strideX,
+                                             d_B + b0 * strideB, ldb, strideB, d_R + b0 * strideR, ldr, strideR,
+                                             d_W ? d_W + b0 * strideR : nullptr);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_gerfs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, const double *d_LU, int64_t ldlu,
+                              int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv, int64_t strideP, int32_t nrhs,
+                              const double *d_B, int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t itmax,
+                              double *d_ferr, double *d_berr, int32_t *d_iters) {
+    if (!c) return -1;
+    int rc = check_sizes_refine_blocked(c, "gerfs_batched_blocked", n, batch);
+    if (rc) return rc;
+    if (batch > 1 && strideP < n) { c->err = "gerfs_batched_blocked: stride of ipiv < n"; return -1; }
+    if (nrhs < 0) { c->err = "gerfs_batched_blocked: nrhs must not be negative"; return -1; }
+    if (trans != 0 && trans != 1) { c->err = "gerfs_batched_blocked: trans must be 0 or 1"; return -1; }
+    if (n == 0 || batch == 0 || nrhs == 0) return 0;
+    rc = check_strided(c, "gerfs_batched_blocked", "A", lda, strideA, n, n, batch);
+    if (!rc) rc = check_strided(c, "gerfs_batched_blocked", "LU", ldlu, strideLU, n, n, batch);
+    if (!rc) rc = check_strided(c, "gerfs_batched_blocked", "B", ldb, strideB, n, nrhs, batch);
+    if (!rc) rc = check_strided(c, "gerfs_batched_blocked", "X", ldx, strideX, n, nrhs, batch);
+    if (rc) return rc;
+    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !d_berr) { c->err = "gerfs_batched_blocked: null pointer"; return -1; }
+    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
+        return mpf_gerfs_batched(c, trans, d_A, lda, strideA, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, nrhs, d_B, ldb, strideB, d_X,
+                                 ldx, strideX, itmax, d_ferr, d_berr, d_iters);
+    const int it = itmax <= 0 ? 5 : (itmax > 31 ? 31 : itmax);   // mpf_gerfs's rule
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    // with the bound, a chunk is also as many matrices as keep its workspace (n + 1 doubles per column, one per column and tile of
+    // 16 chains) within 256 MB; a matrix's results do not depend on the chunk
+    int64_t step = BB_MAX_LAUNCH;
+    if (d_ferr) {
+        const int64_t fit = ((int64_t)1 << 25) / ((int64_t)nrhs * (n + 1 + (n + 15) / 16));
+        step = fit < 1 ? 1 : (fit < step ? fit : step);
+    }
+    for (int64_t b0 = 0; b0 < batch; b0 += step) {
+        const int64_t nb = batch - b0 < step ? batch - b0 : step;
+        rc = launch_gerfs_batched_blocked(c, trans, d_A + b0 * strideA, lda, strideA, d_LU + b0 * strideLU, ldlu, strideLU, n, nb,
+                                          d_ipiv + b0 * strideP, strideP, nrhs, d_B + b0 * strideB, ldb, strideB, d_X + b0 * strideX, ldx,
+                                          strideX, it, d_ferr ? d_ferr + b0 * nrhs : nullptr, d_berr + b0 * nrhs,
+                                          d_iters ? d_iters + b0 * nrhs : nullptr);
         if (rc) return rc;
     }
     return 0;

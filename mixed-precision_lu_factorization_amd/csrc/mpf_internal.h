@@ -225,6 +225,9 @@ struct mpf_ctx {
     // inverse and determinant (mpf_getri.cpp, getri.hip): ceil(N / 256) x 256 x 256 doubles -- L's block inverses transposed, then the
     // 256-row panel of the interchange pass; mpf_getdet's chunk results
     Buf<double> getri_buf;
+    // blocked batched expert layer (batched_refine_blocked.hip): g per (matrix, column, row) and max |x| per (matrix, column) between
+    // the refinement and its bound; the tile maxima of the reduced chains per (matrix[, column], tile)
+    Buf<double> rb_g, rb_xm, rb_part;
     // factored 32x32 diagonal tiles of the fp64 panel, parked here until every workgroup of the sub-panel launches has
     // read the UNfactored tile from the matrix (dpanel.hip); one tile per 32 panel columns, grown on demand
     Buf<double> dtiles;
@@ -588,6 +591,20 @@ int launch_getri_batched_blocked(mpf_ctx *c, const double *LU, int64_t ldlu, int
                                  int64_t strideP, double *inv, int64_t ldinv, int64_t strideInv, int *info, int ct);
 int launch_getdet_batched_blocked(mpf_ctx *c, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch, const int *ipiv,
                                   int64_t strideP, double *mant, int *expo);
+// The expert layer on those batches (batched_refine_blocked.hip): launch_lange_batched's, launch_gecon_batched's,
+// launch_residual_batched's and launch_gerfs_batched's arguments and bits for 1 <= n <= 1024, at most BB_MAX_LAUNCH matrices per call.
+// Workspace (grow-only, in the context): gecon one double per (matrix, tile of chains); gerfs with ferr n + 1 doubles per (matrix,
+// column) and one per (matrix, column, tile).  Nothing is proportional to n^2.
+int launch_lange_batched_blocked(mpf_ctx *c, int mode, const double *A, int64_t lda, int64_t strideA, int n, int64_t batch, double *out);
+int launch_gecon_batched_blocked(mpf_ctx *c, int inf, const double *LU, int64_t ldlu, int64_t strideLU, int n, int64_t batch,
+                                 const double *anorm, double *rcond, double *ainvnm);
+int launch_residual_batched_blocked(mpf_ctx *c, int trans, const double *A, int64_t lda, int64_t strideA, int n, int64_t batch, int nrhs,
+                                    const double *X, int64_t ldx, int64_t strideX, const double *B, int64_t ldb, int64_t strideB, double *R,
+                                    int64_t ldr, int64_t strideR, double *W);
+int launch_gerfs_batched_blocked(mpf_ctx *c, int trans, const double *A, int64_t lda, int64_t strideA, const double *LU, int64_t ldlu,
+                                 int64_t strideLU, int n, int64_t batch, const int *ipiv, int64_t strideP, int nrhs, const double *B,
+                                 int64_t ldb, int64_t strideB, double *X, int64_t ldx, int64_t strideX, int itmax, double *ferr, double *berr,
+                                 int *iters);
 // The same for matrices of different orders (vbatched_blocked.hip, bodies in batched_blocked_body.h; descriptor, groups and chunks in
 // mpf_batched.cpp): `count` <= BB_MAX_LAUNCH entries of a list ordered by n, idx[i] = the matrix of entry i, nmax = the largest order
 // among them.  launch_getrf_vbatched_blocked_step: ONE panel step of the right-looking loop at column j0 (a multiple of nb = 8, 16 or
