@@ -1,14 +1,42 @@
-// The bodies of batched_blocked.hip's kernels as __device__ functions of (matrix base, leading dimension, n, the matrix's pivots, the
-// matrix's info entry), for the ragged kernels of vbatched_blocked.hip -- as vbatched_body.h holds batched.hip's.  The arithmetic is
-// copied statement for statement, so a matrix's bits are those of the fixed-size blocked entry on that matrix alone; batched_blocked.hip
-// itself is untouched and keeps its bits and its times (DESIGN 4.23 says why the bodies are copied and not shared).
+// The blocked batched kernels' bodies as __device__ functions of (matrix base, leading dimension, n, the matrix's pivots, the matrix's
+// info entry, the work item): the one copy of the arithmetic of the blocked family.  Three files wrap it: batched_blocked.hip (one order
+// per call: base = A + b stride), vbatched_blocked.hip (ragged lists: base from the descriptor) and batched_refine_blocked.hip (the two
+// sweeps).  A matrix's bits are therefore the same whichever entry it came through (DESIGN 4.23 has the resource table and the times
+// that allowed the sharing).
 //
-// What differs from the fixed-size kernels is only where a workgroup stands in its launch.  A ragged launch is sized for the largest
-// matrix of its list, so:
+// The numeric contract is batched.hip's, unchanged: mpf_dgetf2_piv on the whole n x n matrix.  Per element that is one update per k in
+// ascending order (contract C3), and for fused = 1 the update is c = fma(-l_ik, u_kj, c) -- the chain of v_mfma_f64_16x16x4_f64
+// (contract C5).  A right-looking blocked loop applies exactly those updates in exactly that order whatever the panel width, so the
+// width (8, 16 or 32) is a performance choice.  Per panel step three ordinary launches, each ONE grid over the whole batch:
+//   bb_panel_body<NB>        one workgroup per matrix, thread = row of A[j0:n, j0:j0+nb], the row's nb columns in registers (column loops
+//                            fully unrolled).  Rows never move while resident (batched.hip): a thread keeps its row's CURRENT position.
+//                            Pivot search: wave reduction over (|x| bits with NaN -> 0, position), the waves' bests combined through
+//                            LDS by every thread; the pivot row is broadcast through LDS; one division per row; rank-1 update fused or
+//                            not.  Two barriers per column, everything they guard double-buffered.  Writes ipiv (1-based, global), info
+//                            (the first panel's launch initialises it) and the rows at their final positions.
+//   bb_rowblk_body<NB>       workgroup = (column chunk, matrix), thread = one column left or right of the panel: the panel's nb
+//                            interchanges as ONE map (simulated once per workgroup on an index array in LDS), every load before the first
+//                            store; right of the panel then the forward substitution with the panel's unit-lower tile from LDS, k ascending.
+//   bb_update_mfma_body<NB>  workgroup = (64 x 64 tile of C, matrix), four waves of 32 x 32: C into the accumulators, nb / 4
+//                            v_mfma_f64_16x16x4_f64 with k ascending, the negation on the L operand (the instruction's NEG bit).  The
+//                            MFMA's row index is C's column (trailing_f64.hip): a lane's 16-lane group walks 16 consecutive rows of C.
+//                            Operands straight from global memory (K = nb: every operand element is used by two MFMAs of the wave).
+//   bb_update_valu_body<NB, FUSED>  the same tiling on the VALU: the unfused contract (rounded product, rounded difference); its fused
+//                            instantiation is the MFMA kernel's cross-check (probe library, option batched_blocked_valu).
+// A trailing matrix exists only behind a FULL panel, so K = nb always: no operand is padded along k.  Rows and columns past the matrix
+// are predicated loads of zeros whose results are never stored; an element inside the matrix never sees them.
+//   bb_getrs_body<CT>        one workgroup per (matrix, tile of CT right-hand-side columns), thread = row, the row's CT values in
+//                            registers.  The sweeps go in blocks of 32: a thread loads its 32 factor elements of the block first (all
+//                            in flight), the block's wave solves the 32 x 32 diagonal block with v_readlane broadcasts and publishes the
+//                            32 x CT results in LDS, one barrier, then every other row applies the 32 steps in the contract's order.
+//                            trans = 1 reads the same blocks transposed.  The interchanges are one composed map (bt_getrs_kernel).
+//
+// Where a workgroup stands in its launch is the caller's business.  A ragged launch is sized for the largest matrix of its list, so:
 //   - a body takes the work item's coordinates (column chunk, C tile, right-hand-side tile, inverse tile) as arguments and leaves as a
-//     whole, before its first barrier, when its matrix is exhausted (n <= j0) or the item lies outside its own matrix;
+//     whole, before its first barrier, when its matrix is exhausted (n <= j0) or the item lies outside its own matrix (uniform scalar
+//     compares that never hold in a fixed-size launch);
 //   - threads past the matrix's own rows stay in every barrier and reduction as valid = false; nw comes from blockDim, and the surplus
-//     waves publish the neutral key (0, INT_MAX) like the surplus lanes of the fixed-size kernels' last wave;
+//     waves publish the neutral key (0, INT_MAX) like the surplus lanes of a fixed-size launch's last wave;
 //   - every "rows and columns past the matrix read as zero" is a predicated load against the matrix's own n: in a packed descriptor the
 //     next matrix starts at the very next double.
 #pragma once
@@ -350,7 +378,21 @@ __device__ __forceinline__ void bb_getrs_body(int trans, const double *T, long l
     }
 }
 
-// ---- inverse (bb_inv_sweep, bb_getri_kernel; the scheme is described in batched_blocked.hip) --------------------------------------------
+// ---- inverse (bb_inv_sweep, bb_getri_kernel) --------------------------------------------------------------------------------------------
+// inv(A) = inv(U) inv(L) P: column k of the result is column q(k) of inv(L) taken through the backward sweep, so the interchanges are
+// no arithmetic -- the workgroup that owns columns q .. q + CT - 1 of inv(L) stores them at columns k(q) = map[q], bb_getrs_body's
+// composed map.  One workgroup per (matrix, tile of CT consecutive q), thread = row, the row's CT values in registers, both sweeps in
+// blocks of 32 rows as bb_sweep has them.  What differs from the solve:
+//   - the tile's columns start as e_q, never read; the forward sweep starts at the block that holds the tile's smallest q (the steps
+//     before it subtract l * (+0) from +0);
+//   - the 32 x 32 diagonal block is solved with lane = COLUMN: the block's rows go through LDS (xs, with the block's factor rows in
+//     ds), lane c of the block's wave takes column c in groups of BB_IG rows -- the terms of the rows already solved first, then the
+//     group's triangle -- with the factor elements as LDS broadcasts: one division per (row, column) instead of one per (row, column,
+//     lane), 496 multiply-subtract pairs per column instead of 32 x 32 selects;
+//   - the rows outside the block then apply its 32 steps in the chain's order, the factor elements BB_UG at a time.
+// Rows past n inside the last block publish zeros that the solve never writes back, and columns past n of the factors read as zero,
+// so the 32 steps of a block need no bound checks: x - 0 * 0 = x.  A zero on U's diagonal is found by every workgroup of the matrix
+// before its first store; such a workgroup returns, the tile-0 workgroup writes info.
 template <int CT, bool ASC>
 __device__ __forceinline__ void bb_inv_sweep(const double *T, long long ld, int n, int t, bool valid, int kb0, double (&x)[CT],
                                              double (*xs)[32][CT + 1], double (*ds)[32][33], int &ph) {
@@ -473,6 +515,9 @@ __device__ __forceinline__ void bb_getri_body(const double *T, long long ldlu, i
 }
 
 // ---- determinant (bb_getdet_kernel) ----------------------------------------------------------------------------------------------------
+// mpf_getdet's order for n <= 1024: up to four chunks of 256 consecutive diagonal entries.  One workgroup per matrix: thread = diagonal
+// entry for the loads ((m_i, e_i) = frexp(u_ii) into LDS, the pivot count and the special cases by LDS atomics), thread = chunk for the
+// serial chains, thread 0 for the combining chain.  Reads n of the matrix's n^2 doubles.
 // a: the matrix's factors; pvt: its pivots; mant, expo: its entries.  blockDim.x = 256
 __device__ __forceinline__ void bb_getdet_body(const double *a, long long ldlu, int n, const int *pvt, double *mant, int *expo) {
     constexpr int DCH = 256;

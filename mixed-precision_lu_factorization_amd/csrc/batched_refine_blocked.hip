@@ -11,7 +11,7 @@
 //   maxima     order-free, a NaN stays: rb_nanmax.
 //   fusion     every multiply-subtract and multiply-add is unfused (the file is compiled with -ffp-contract=off).
 // The chains are batched_blocked_body.h's: bb_sweep (mpf_getrs_batched_blocked's) and bb_inv_sweep (mpf_getri_batched_blocked's, the
-// trans = 0 chains from unit vectors).  batched_refine.hip, batched_blocked.hip and their kernels stay as they are.
+// trans = 0 chains from unit vectors), the same functions that batched_blocked.hip's and vbatched_blocked.hip's kernels call.
 //   rb_lange_kernel            one workgroup per matrix.  '1': a wave per column, lane l takes rows l + 64 m (coalesced), the tree over m
 //                              in registers, then the butterfly.  'I': thread = row (coalesced along every column); the row's tree runs
 //                              over the columns in BIT-REVERSED order, where the halving tree is the pairwise tree of neighbours: sixteen

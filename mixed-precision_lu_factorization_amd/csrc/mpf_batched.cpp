@@ -6,8 +6,8 @@
 //   mpf_lange_batched, mpf_gecon_batched, mpf_residual_batched, mpf_gerfs_batched   the expert layer on those batches: a norm and an
 //                       exact reciprocal condition number per matrix, the residual step operator, dgerfs's refinement with berr and
 //                       an exact ferr per matrix and column (kernels in batched_refine.hip)
-// The argument checks, the chunks of a batch longer than one grid and the error text; kernels and form choice in batched.hip; the
-// contracts are in include/mpf_c.h.
+// The argument checks, the chunks of a batch longer than one grid and the error text (the rules themselves: batch_args.h); kernels and
+// form choice in batched.hip; the contracts are in include/mpf_c.h.
 //   mpf_getrf_batched_blocked, mpf_getrs_batched_blocked   the first two for one n <= 1024: the same bits from a right-looking blocked
 //                       loop (batched_blocked.hip), three launches per panel step for the whole batch
 //   mpf_getri_batched_blocked, mpf_getdet_batched_blocked   the other two for one n <= 1024: one launch each, no workspace
@@ -18,6 +18,7 @@
 // A descriptor from mpf_vbatch_create_blocked (orders up to 1024) also has the plan's large list: its matrices take the ragged blocked
 // kernels of vbatched_blocked.hip, launch group by launch group, the factorization panel step by panel step over the active suffix.
 #include "mpf_internal.h"
+#include "batch_args.h"
 #include "vbatch_plan.h"
 #include <memory>
 
@@ -30,132 +31,110 @@ struct mpf_vbatch {
 };
 
 namespace {
-constexpr int32_t BATCHED_MAXN = 128;
+namespace ba = batch_args;
 
-// what both entry points ask of a strided batch of `rows` x `cols` column-major matrices
-int check_strided(mpf_ctx *c, const char *who, const char *what, int64_t ld, int64_t stride, int64_t rows, int64_t cols, int64_t batch) {
-    if (ld < rows) { c->err = std::string(who) + ": leading dimension of " + what + " < n"; return -1; }
-    if (batch > 1 && stride < ld * cols) { c->err = std::string(who) + ": stride of " + what + " is smaller than one matrix"; return -1; }
-    return 0;
-}
-int check_sizes(mpf_ctx *c, const char *who, int32_t n, int64_t batch, int64_t strideP) {
-    if (n < 0 || batch < 0) { c->err = std::string(who) + ": n and batch must not be negative"; return -1; }
-    if (n > BATCHED_MAXN) {
-        c->err = std::string(who) + ": n > 128 is not a small matrix: factor it with mpf_factor_dev (and solve with mpf_getrs)";
-        return -1;
-    }
-    if (batch > 1 && strideP < n) { c->err = std::string(who) + ": stride of ipiv < n"; return -1; }
-    return 0;
-}
-// the same for the blocked entry points: n <= 1024
-int check_sizes_blocked(mpf_ctx *c, const char *who, int32_t n, int64_t batch, int64_t strideP, const char *then = "solve with mpf_getrs") {
-    if (n < 0 || batch < 0) { c->err = std::string(who) + ": n and batch must not be negative"; return -1; }
-    if (n > BB_MAXN) {
-        c->err = std::string(who) + ": n > 1024 is not a batch-sized matrix: factor it with mpf_factor_dev (and " + then + ")";
-        return -1;
-    }
-    if (batch > 1 && strideP < n) { c->err = std::string(who) + ": stride of ipiv < n"; return -1; }
-    return 0;
+// where check_sizes' message sends a matrix that is too large for the family
+const char *const THEN_GETRS = "factor it with mpf_factor_dev (and solve with mpf_getrs)";
+const char *const ONE_AT_A_TIME = "use mpf_lange, mpf_gecon / mpf_gerfs on one matrix at a time";
+
+bool forwards_to_small(const mpf_ctx *c, int32_t n) { return ba::forwards_to_small(n, c->tune.batched_blocked_min_n); }
+// an optional per-matrix output of a chunk
+template <class T>
+T *opt(T *p, int64_t at) { return p ? p + at : nullptr; }
+// getri's rule: the factors are still being read while the result is stored (mpf_getri's rule, on the address ranges of the two batches)
+int check_out_of_place(mpf_ctx *c, const char *who, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                       const double *d_inv, int64_t ldinv, int64_t strideInv) {
+    if (!ba::ranges_overlap((uintptr_t)d_LU, ba::extent(n, batch, ldlu, strideLU), (uintptr_t)d_inv, ba::extent(n, batch, ldinv, strideInv))) return 0;
+    c->err = std::string(who) + ": d_inv overlaps d_LU (the inverse is formed out of place)";
+    return -1;
 }
 } // namespace
 
+// Every entry below reads: the checks in the contract's order, for a blocked entry the forward to the small one, then one launch per
+// chunk of the batch.
 extern "C" {
 
 int mpf_getrf_batched(mpf_ctx *c, double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t *d_ipiv, int64_t strideP,
                       int32_t *d_info, int32_t fused) {
     if (!c) return -1;
-    int rc = check_sizes(c, "getrf_batched", n, batch, strideP);
+    const char *who = "getrf_batched";
+    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, THEN_GETRS);
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
     if (n == 0 || batch == 0) return 0;
-    rc = check_strided(c, "getrf_batched", "A", lda, strideA, n, n, batch);
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
     if (rc) return rc;
     if (!d_A || !d_ipiv) { c->err = "getrf_batched: null pointer"; return -1; }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
-        rc = launch_getrf_batched(c, d_A + b0 * strideA, lda, strideA, n, nb, d_ipiv + b0 * strideP, strideP, d_info ? d_info + b0 : nullptr,
-                                  fused != 0);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_getrf_batched(c, d_A + b0 * strideA, lda, strideA, n, nb, d_ipiv + b0 * strideP, strideP, opt(d_info, b0), fused != 0);
+    });
 }
 
 int mpf_getrs_batched(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                       const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB) {
     if (!c) return -1;
-    int rc = check_sizes(c, "getrs_batched", n, batch, strideP);
+    const char *who = "getrs_batched";
+    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, THEN_GETRS);
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
     if (nrhs < 0) { c->err = "getrs_batched: nrhs must not be negative"; return -1; }
     if (trans != 0 && trans != 1) { c->err = "getrs_batched: trans must be 0 or 1"; return -1; }
     if (n == 0 || batch == 0 || nrhs == 0) return 0;
-    rc = check_strided(c, "getrs_batched", "LU", ldlu, strideLU, n, n, batch);
-    if (!rc) rc = check_strided(c, "getrs_batched", "B", ldb, strideB, n, nrhs, batch);
+    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
     if (rc) return rc;
     if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs_batched: null pointer"; return -1; }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
-        rc = launch_getrs_batched(c, trans, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, nrhs,
-                                  d_B + b0 * strideB, ldb, strideB);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_getrs_batched(c, trans, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, nrhs,
+                                    d_B + b0 * strideB, ldb, strideB);
+    });
 }
 
 int mpf_getri_batched(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv,
                       int64_t strideP, double *d_inv, int64_t ldinv, int64_t strideInv, int32_t *d_info) {
     if (!c) return -1;
-    int rc = check_sizes(c, "getri_batched", n, batch, strideP);
+    const char *who = "getri_batched";
+    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, THEN_GETRS);
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
     if (n == 0 || batch == 0) return 0;
-    rc = check_strided(c, "getri_batched", "LU", ldlu, strideLU, n, n, batch);
-    if (!rc) rc = check_strided(c, "getri_batched", "inv", ldinv, strideInv, n, n, batch);
+    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "inv", ldinv, strideInv, n, n, batch);
     if (rc) return rc;
     if (!d_LU || !d_ipiv || !d_inv) { c->err = "getri_batched: null pointer"; return -1; }
-    {   // the factors are still being read while the result is stored (mpf_getri's rule, on the address ranges of the two batches)
-        const uintptr_t a0 = (uintptr_t)d_LU, a1 = a0 + (size_t)((batch - 1) * strideLU + (n - 1) * ldlu + n) * sizeof(double);
-        const uintptr_t b0 = (uintptr_t)d_inv, b1 = b0 + (size_t)((batch - 1) * strideInv + (n - 1) * ldinv + n) * sizeof(double);
-        if (a0 < b1 && b0 < a1) { c->err = "getri_batched: d_inv overlaps d_LU (the inverse is formed out of place)"; return -1; }
-    }
+    rc = check_out_of_place(c, who, d_LU, ldlu, strideLU, n, batch, d_inv, ldinv, strideInv);
+    if (rc) return rc;
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
-        rc = launch_getri_batched(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_inv + b0 * strideInv,
-                                  ldinv, strideInv, d_info ? d_info + b0 : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_getri_batched(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_inv + b0 * strideInv,
+                                    ldinv, strideInv, opt(d_info, b0));
+    });
 }
 
 int mpf_getdet_batched(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv,
                        int64_t strideP, double *d_mant, int32_t *d_expo) {
     if (!c) return -1;
-    int rc = check_sizes(c, "getdet_batched", n, batch, strideP);
+    const char *who = "getdet_batched";
+    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, THEN_GETRS);
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
     if (n == 0 || batch == 0) return 0;
-    rc = check_strided(c, "getdet_batched", "LU", ldlu, strideLU, n, n, batch);
+    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
     if (rc) return rc;
     if (!d_LU || !d_ipiv || !d_mant || !d_expo) { c->err = "getdet_batched: null pointer"; return -1; }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
-        rc = launch_getdet_batched(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0, d_expo + b0);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_getdet_batched(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0, d_expo + b0);
+    });
 }
 
 // ---- the expert layer, n <= 128 (kernels in batched_refine.hip) ---------------------------------------------------------------------------
-// check_sizes' rules with the message that names where larger matrices go
-static int check_sizes_refine(mpf_ctx *c, const char *who, int32_t n, int64_t batch, const char *use) {
-    if (n < 0 || batch < 0) { c->err = std::string(who) + ": n and batch must not be negative"; return -1; }
-    if (n > BATCHED_MAXN) { c->err = std::string(who) + ": n > 128 is not a small matrix: use " + use + " on one matrix at a time"; return -1; }
-    return 0;
-}
-
 int mpf_lange_batched(mpf_ctx *c, char norm, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_out) {
     if (!c) return -1;
-    int rc = check_sizes_refine(c, "lange_batched", n, batch, "mpf_lange (and mpf_gecon / mpf_gerfs)");
+    const char *who = "lange_batched";
+    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, "use mpf_lange (and mpf_gecon / mpf_gerfs) on one matrix at a time");
     if (rc) return rc;
     int mode;
     if (norm == '1' || norm == 'O' || norm == 'o') mode = 0;
@@ -163,64 +142,54 @@ int mpf_lange_batched(mpf_ctx *c, char norm, const double *d_A, int64_t lda, int
     else if (norm == 'M' || norm == 'm') mode = 2;
     else { c->err = "lange_batched: norm must be '1', 'O', 'I' or 'M'"; return -1; }
     if (n == 0 || batch == 0) return 0;
-    rc = check_strided(c, "lange_batched", "A", lda, strideA, n, n, batch);
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
     if (rc) return rc;
     if (!d_A || !d_out) { c->err = "lange_batched: null pointer"; return -1; }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
-        rc = launch_lange_batched(c, mode, d_A + b0 * strideA, lda, strideA, n, nb, d_out + b0);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_lange_batched(c, mode, d_A + b0 * strideA, lda, strideA, n, nb, d_out + b0);
+    });
 }
 
 int mpf_gecon_batched(mpf_ctx *c, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                       const double *d_anorm, double *d_rcond, double *d_ainvnm) {
     if (!c) return -1;
-    int rc = check_sizes_refine(c, "gecon_batched", n, batch, "mpf_gecon (and mpf_gerfs)");
+    const char *who = "gecon_batched";
+    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, "use mpf_gecon (and mpf_gerfs) on one matrix at a time");
     if (rc) return rc;
     const bool one = norm == '1' || norm == 'O' || norm == 'o';
     if (!one && norm != 'I' && norm != 'i') { c->err = "gecon_batched: norm must be '1', 'O' or 'I'"; return -1; }
     if (n == 0 || batch == 0) return 0;
-    rc = check_strided(c, "gecon_batched", "LU", ldlu, strideLU, n, n, batch);
+    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
     if (rc) return rc;
     if (!d_LU || !d_anorm || !d_rcond) { c->err = "gecon_batched: null pointer"; return -1; }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
-        rc = launch_gecon_batched(c, one ? 0 : 1, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_anorm + b0, d_rcond + b0,
-                                  d_ainvnm ? d_ainvnm + b0 : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_gecon_batched(c, one ? 0 : 1, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_anorm + b0, d_rcond + b0, opt(d_ainvnm, b0));
+    });
 }
 
 int mpf_residual_batched(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t nrhs,
                          const double *d_X, int64_t ldx, int64_t strideX, const double *d_B, int64_t ldb, int64_t strideB, double *d_R,
                          int64_t ldr, int64_t strideR, double *d_W) {
     if (!c) return -1;
-    int rc = check_sizes_refine(c, "residual_batched", n, batch, "mpf_gerfs (and mpf_gecon)");
+    const char *who = "residual_batched";
+    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, "use mpf_gerfs (and mpf_gecon) on one matrix at a time");
     if (rc) return rc;
     if (nrhs < 0) { c->err = "residual_batched: nrhs must not be negative"; return -1; }
     if (trans != 0 && trans != 1) { c->err = "residual_batched: trans must be 0 or 1"; return -1; }
     if (n == 0 || batch == 0 || nrhs == 0) return 0;
-    rc = check_strided(c, "residual_batched", "A", lda, strideA, n, n, batch);
-    if (!rc) rc = check_strided(c, "residual_batched", "X", ldx, strideX, n, nrhs, batch);
-    if (!rc) rc = check_strided(c, "residual_batched", "B", ldb, strideB, n, nrhs, batch);
-    if (!rc) rc = check_strided(c, "residual_batched", "R", ldr, strideR, n, nrhs, batch);
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "X", ldx, strideX, n, nrhs, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "R", ldr, strideR, n, nrhs, batch);
     if (rc) return rc;
     if (!d_A || !d_X || !d_B || !d_R) { c->err = "residual_batched: null pointer"; return -1; }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    int64_t step = BR_MAX_UNITS / nrhs;
-    if (step > BT_MAX_LAUNCH) step = BT_MAX_LAUNCH;
-    for (int64_t b0 = 0; b0 < batch; b0 += step) {
-        const int64_t nb = batch - b0 < step ? batch - b0 : step;
-        rc = launch_residual_batched(c, trans, d_A + b0 * strideA, lda, strideA, n, nb, nrhs, d_X + b0 * strideX, ldx, strideX,
-                                     d_B + b0 * strideB, ldb, strideB, d_R + b0 * strideR, ldr, strideR, d_W ? d_W + b0 * strideR : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, ba::residual_step(BR_MAX_UNITS, BT_MAX_LAUNCH, nrhs), [&](int64_t b0, int64_t nb) {
+        return launch_residual_batched(c, trans, d_A + b0 * strideA, lda, strideA, n, nb, nrhs, d_X + b0 * strideX, ldx, strideX,
+                                       d_B + b0 * strideB, ldb, strideB, d_R + b0 * strideR, ldr, strideR, opt(d_W, b0 * strideR));
+    });
 }
 
 int mpf_gerfs_batched(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, const double *d_LU, int64_t ldlu,
@@ -228,148 +197,125 @@ int mpf_gerfs_batched(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda,
                       int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t itmax, double *d_ferr, double *d_berr,
                       int32_t *d_iters) {
     if (!c) return -1;
-    int rc = check_sizes_refine(c, "gerfs_batched", n, batch, "mpf_gerfs (and mpf_gecon)");
+    const char *who = "gerfs_batched";
+    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, "use mpf_gerfs (and mpf_gecon) on one matrix at a time");
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
-    if (batch > 1 && strideP < n) { c->err = "gerfs_batched: stride of ipiv < n"; return -1; }
     if (nrhs < 0) { c->err = "gerfs_batched: nrhs must not be negative"; return -1; }
     if (trans != 0 && trans != 1) { c->err = "gerfs_batched: trans must be 0 or 1"; return -1; }
     if (n == 0 || batch == 0 || nrhs == 0) return 0;
-    rc = check_strided(c, "gerfs_batched", "A", lda, strideA, n, n, batch);
-    if (!rc) rc = check_strided(c, "gerfs_batched", "LU", ldlu, strideLU, n, n, batch);
-    if (!rc) rc = check_strided(c, "gerfs_batched", "B", ldb, strideB, n, nrhs, batch);
-    if (!rc) rc = check_strided(c, "gerfs_batched", "X", ldx, strideX, n, nrhs, batch);
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "X", ldx, strideX, n, nrhs, batch);
     if (rc) return rc;
     if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !d_berr) { c->err = "gerfs_batched: null pointer"; return -1; }
     const int it = itmax <= 0 ? 5 : (itmax > 31 ? 31 : itmax);   // mpf_gerfs's rule
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BT_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BT_MAX_LAUNCH ? batch - b0 : BT_MAX_LAUNCH;
-        rc = launch_gerfs_batched(c, trans, d_A + b0 * strideA, lda, strideA, d_LU + b0 * strideLU, ldlu, strideLU, n, nb,
-                                  d_ipiv + b0 * strideP, strideP, nrhs, d_B + b0 * strideB, ldb, strideB, d_X + b0 * strideX, ldx, strideX, it,
-                                  d_ferr ? d_ferr + b0 * nrhs : nullptr, d_berr + b0 * nrhs, d_iters ? d_iters + b0 * nrhs : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_gerfs_batched(c, trans, d_A + b0 * strideA, lda, strideA, d_LU + b0 * strideLU, ldlu, strideLU, n, nb,
+                                    d_ipiv + b0 * strideP, strideP, nrhs, d_B + b0 * strideB, ldb, strideB, d_X + b0 * strideX, ldx, strideX, it,
+                                    opt(d_ferr, b0 * nrhs), d_berr + b0 * nrhs, opt(d_iters, b0 * nrhs));
+    });
 }
 
 // ---- blocked: one n <= 1024 per call ------------------------------------------------------------------------------------------------------
-// The checks are check_sizes' and check_strided's with the larger limit; n below option batched_blocked_min_n (and <= 128) goes to the
-// entry points above, whose bits are the same by contract.
+// The checks of the entries above with the larger limit; n below option batched_blocked_min_n (and <= 128) goes to those entries,
+// whose bits are the same by contract.
 int mpf_getrf_batched_blocked(mpf_ctx *c, double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t *d_ipiv,
                               int64_t strideP, int32_t *d_info, int32_t fused) {
     if (!c) return -1;
-    int rc = check_sizes_blocked(c, "getrf_batched_blocked", n, batch, strideP);
+    const char *who = "getrf_batched_blocked";
+    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, THEN_GETRS);
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
     if (n == 0 || batch == 0) return 0;
-    rc = check_strided(c, "getrf_batched_blocked", "A", lda, strideA, n, n, batch);
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
     if (rc) return rc;
     if (!d_A || !d_ipiv) { c->err = "getrf_batched_blocked: null pointer"; return -1; }
-    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n) return mpf_getrf_batched(c, d_A, lda, strideA, n, batch, d_ipiv, strideP, d_info, fused);
+    if (forwards_to_small(c, n)) return mpf_getrf_batched(c, d_A, lda, strideA, n, batch, d_ipiv, strideP, d_info, fused);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     int valu = 0, stages = 7;
 #ifdef MPF_PROBE
     valu = c->tune.batched_blocked_valu;
     stages = c->tune.batched_blocked_stages;
 #endif
-    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
-        rc = launch_getrf_batched_blocked(c, d_A + b0 * strideA, lda, strideA, n, nb, d_ipiv + b0 * strideP, strideP,
-                                          d_info ? d_info + b0 : nullptr, fused != 0, c->tune.batched_blocked_nb, valu, stages);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_getrf_batched_blocked(c, d_A + b0 * strideA, lda, strideA, n, nb, d_ipiv + b0 * strideP, strideP, opt(d_info, b0),
+                                            fused != 0, c->tune.batched_blocked_nb, valu, stages);
+    });
 }
 
 int mpf_getrs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                               const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB) {
     if (!c) return -1;
-    int rc = check_sizes_blocked(c, "getrs_batched_blocked", n, batch, strideP);
+    const char *who = "getrs_batched_blocked";
+    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, THEN_GETRS);
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
     if (nrhs < 0) { c->err = "getrs_batched_blocked: nrhs must not be negative"; return -1; }
     if (trans != 0 && trans != 1) { c->err = "getrs_batched_blocked: trans must be 0 or 1"; return -1; }
     if (n == 0 || batch == 0 || nrhs == 0) return 0;
-    rc = check_strided(c, "getrs_batched_blocked", "LU", ldlu, strideLU, n, n, batch);
-    if (!rc) rc = check_strided(c, "getrs_batched_blocked", "B", ldb, strideB, n, nrhs, batch);
+    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
     if (rc) return rc;
     if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs_batched_blocked: null pointer"; return -1; }
-    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
-        return mpf_getrs_batched(c, trans, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, nrhs, d_B, ldb, strideB);
+    if (forwards_to_small(c, n)) return mpf_getrs_batched(c, trans, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, nrhs, d_B, ldb, strideB);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
-        rc = launch_getrs_batched_blocked(c, trans, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, nrhs,
-                                          d_B + b0 * strideB, ldb, strideB);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_getrs_batched_blocked(c, trans, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, nrhs,
+                                            d_B + b0 * strideB, ldb, strideB);
+    });
 }
 
-// mpf_getri_batched's checks with the larger limit.  The kernels need no flag buffer: every workgroup reads its matrix's diagonal and
-// knows the first zero before its first store, whether or not d_info is given.
+// The kernels need no flag buffer: every workgroup reads its matrix's diagonal and knows the first zero before its first store,
+// whether or not d_info is given.
 int mpf_getri_batched_blocked(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                               const int32_t *d_ipiv, int64_t strideP, double *d_inv, int64_t ldinv, int64_t strideInv, int32_t *d_info) {
     if (!c) return -1;
-    int rc = check_sizes_blocked(c, "getri_batched_blocked", n, batch, strideP, "invert with mpf_getri");
+    const char *who = "getri_batched_blocked";
+    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, "factor it with mpf_factor_dev (and invert with mpf_getri)");
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
     if (n == 0 || batch == 0) return 0;
-    rc = check_strided(c, "getri_batched_blocked", "LU", ldlu, strideLU, n, n, batch);
-    if (!rc) rc = check_strided(c, "getri_batched_blocked", "inv", ldinv, strideInv, n, n, batch);
+    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "inv", ldinv, strideInv, n, n, batch);
     if (rc) return rc;
     if (!d_LU || !d_ipiv || !d_inv) { c->err = "getri_batched_blocked: null pointer"; return -1; }
-    {   // mpf_getri_batched's rule and text
-        const uintptr_t a0 = (uintptr_t)d_LU, a1 = a0 + (size_t)((batch - 1) * strideLU + (n - 1) * ldlu + n) * sizeof(double);
-        const uintptr_t b0 = (uintptr_t)d_inv, b1 = b0 + (size_t)((batch - 1) * strideInv + (n - 1) * ldinv + n) * sizeof(double);
-        if (a0 < b1 && b0 < a1) { c->err = "getri_batched_blocked: d_inv overlaps d_LU (the inverse is formed out of place)"; return -1; }
-    }
-    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
-        return mpf_getri_batched(c, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_inv, ldinv, strideInv, d_info);
+    rc = check_out_of_place(c, who, d_LU, ldlu, strideLU, n, batch, d_inv, ldinv, strideInv);
+    if (rc) return rc;
+    if (forwards_to_small(c, n)) return mpf_getri_batched(c, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_inv, ldinv, strideInv, d_info);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
-        rc = launch_getri_batched_blocked(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP,
-                                          d_inv + b0 * strideInv, ldinv, strideInv, d_info ? d_info + b0 : nullptr,
-                                          c->tune.batched_blocked_inv_ct);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_getri_batched_blocked(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP,
+                                            d_inv + b0 * strideInv, ldinv, strideInv, opt(d_info, b0), c->tune.batched_blocked_inv_ct);
+    });
 }
 
 int mpf_getdet_batched_blocked(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                                const int32_t *d_ipiv, int64_t strideP, double *d_mant, int32_t *d_expo) {
     if (!c) return -1;
-    int rc = check_sizes_blocked(c, "getdet_batched_blocked", n, batch, strideP, "take the determinant with mpf_getdet");
+    const char *who = "getdet_batched_blocked";
+    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, "factor it with mpf_factor_dev (and take the determinant with mpf_getdet)");
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
     if (n == 0 || batch == 0) return 0;
-    rc = check_strided(c, "getdet_batched_blocked", "LU", ldlu, strideLU, n, n, batch);
+    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
     if (rc) return rc;
     if (!d_LU || !d_ipiv || !d_mant || !d_expo) { c->err = "getdet_batched_blocked: null pointer"; return -1; }
-    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
-        return mpf_getdet_batched(c, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_mant, d_expo);
+    if (forwards_to_small(c, n)) return mpf_getdet_batched(c, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_mant, d_expo);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
-        rc = launch_getdet_batched_blocked(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0,
-                                           d_expo + b0);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_getdet_batched_blocked(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0,
+                                             d_expo + b0);
+    });
 }
 
 // ---- the expert layer, one n <= 1024 per call (kernels in batched_refine_blocked.hip) ---------------------------------------------------
-// The checks of the n <= 128 entries in their order with the larger limit; n below option batched_blocked_min_n (and <= 128) goes to
-// those entries, whose bits are the same by contract.
-static int check_sizes_refine_blocked(mpf_ctx *c, const char *who, int32_t n, int64_t batch) {
-    if (n < 0 || batch < 0) { c->err = std::string(who) + ": n and batch must not be negative"; return -1; }
-    if (n > BB_MAXN) {
-        c->err = std::string(who) + ": n > 1024 is not a batch-sized matrix: use mpf_lange, mpf_gecon / mpf_gerfs on one matrix at a time";
-        return -1;
-    }
-    return 0;
-}
-
 int mpf_lange_batched_blocked(mpf_ctx *c, char norm, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_out) {
     if (!c) return -1;
-    int rc = check_sizes_refine_blocked(c, "lange_batched_blocked", n, batch);
+    const char *who = "lange_batched_blocked";
+    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, ONE_AT_A_TIME);
     if (rc) return rc;
     int mode;
     if (norm == '1' || norm == 'O' || norm == 'o') mode = 0;
@@ -377,68 +323,59 @@ int mpf_lange_batched_blocked(mpf_ctx *c, char norm, const double *d_A, int64_t 
     else if (norm == 'M' || norm == 'm') mode = 2;
     else { c->err = "lange_batched_blocked: norm must be '1', 'O', 'I' or 'M'"; return -1; }
     if (n == 0 || batch == 0) return 0;
-    rc = check_strided(c, "lange_batched_blocked", "A", lda, strideA, n, n, batch);
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
     if (rc) return rc;
     if (!d_A || !d_out) { c->err = "lange_batched_blocked: null pointer"; return -1; }
-    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n) return mpf_lange_batched(c, norm, d_A, lda, strideA, n, batch, d_out);
+    if (forwards_to_small(c, n)) return mpf_lange_batched(c, norm, d_A, lda, strideA, n, batch, d_out);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
-        rc = launch_lange_batched_blocked(c, mode, d_A + b0 * strideA, lda, strideA, n, nb, d_out + b0);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_lange_batched_blocked(c, mode, d_A + b0 * strideA, lda, strideA, n, nb, d_out + b0);
+    });
 }
 
 int mpf_gecon_batched_blocked(mpf_ctx *c, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
                               const double *d_anorm, double *d_rcond, double *d_ainvnm) {
     if (!c) return -1;
-    int rc = check_sizes_refine_blocked(c, "gecon_batched_blocked", n, batch);
+    const char *who = "gecon_batched_blocked";
+    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, ONE_AT_A_TIME);
     if (rc) return rc;
     const bool one = norm == '1' || norm == 'O' || norm == 'o';
     if (!one && norm != 'I' && norm != 'i') { c->err = "gecon_batched_blocked: norm must be '1', 'O' or 'I'"; return -1; }
     if (n == 0 || batch == 0) return 0;
-    rc = check_strided(c, "gecon_batched_blocked", "LU", ldlu, strideLU, n, n, batch);
+    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
     if (rc) return rc;
     if (!d_LU || !d_anorm || !d_rcond) { c->err = "gecon_batched_blocked: null pointer"; return -1; }
-    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
-        return mpf_gecon_batched(c, norm, d_LU, ldlu, strideLU, n, batch, d_anorm, d_rcond, d_ainvnm);
+    if (forwards_to_small(c, n)) return mpf_gecon_batched(c, norm, d_LU, ldlu, strideLU, n, batch, d_anorm, d_rcond, d_ainvnm);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
-        rc = launch_gecon_batched_blocked(c, one ? 0 : 1, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_anorm + b0, d_rcond + b0,
-                                          d_ainvnm ? d_ainvnm + b0 : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_gecon_batched_blocked(c, one ? 0 : 1, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_anorm + b0, d_rcond + b0,
+                                            opt(d_ainvnm, b0));
+    });
 }
 
 int mpf_residual_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
                                  int32_t nrhs, const double *d_X, int64_t ldx, int64_t strideX, const double *d_B, int64_t ldb, int64_t strideB,
                                  double *d_R, int64_t ldr, int64_t strideR, double *d_W) {
     if (!c) return -1;
-    int rc = check_sizes_refine_blocked(c, "residual_batched_blocked", n, batch);
+    const char *who = "residual_batched_blocked";
+    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, ONE_AT_A_TIME);
     if (rc) return rc;
     if (nrhs < 0) { c->err = "residual_batched_blocked: nrhs must not be negative"; return -1; }
     if (trans != 0 && trans != 1) { c->err = "residual_batched_blocked: trans must be 0 or 1"; return -1; }
     if (n == 0 || batch == 0 || nrhs == 0) return 0;
-    rc = check_strided(c, "residual_batched_blocked", "A", lda, strideA, n, n, batch);
-    if (!rc) rc = check_strided(c, "residual_batched_blocked", "X", ldx, strideX, n, nrhs, batch);
-    if (!rc) rc = check_strided(c, "residual_batched_blocked", "B", ldb, strideB, n, nrhs, batch);
-    if (!rc) rc = check_strided(c, "residual_batched_blocked", "R", ldr, strideR, n, nrhs, batch);
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "X", ldx, strideX, n, nrhs, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "R", ldr, strideR, n, nrhs, batch);
     if (rc) return rc;
     if (!d_A || !d_X || !d_B || !d_R) { c->err = "residual_batched_blocked: null pointer"; return -1; }
-    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
+    if (forwards_to_small(c, n))
         return mpf_residual_batched(c, trans, d_A, lda, strideA, n, batch, nrhs, d_X, ldx, strideX, d_B, ldb, strideB, d_R, ldr, strideR, d_W);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t b0 = 0; b0 < batch; b0 += BB_MAX_LAUNCH) {
-        const int64_t nb = batch - b0 < BB_MAX_LAUNCH ? batch - b0 : BB_MAX_LAUNCH;
-        rc = launch_residual_batched_blocked(c, trans, d_A + b0 * strideA, lda, strideA, n, nb, nrhs, d_X + b0 * strideX, ldx, strideX,
-                                             d_B + b0 * strideB, ldb, strideB, d_R + b0 * strideR, ldr, strideR,
-                                             d_W ? d_W + b0 * strideR : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_residual_batched_blocked(c, trans, d_A + b0 * strideA, lda, strideA, n, nb, nrhs, d_X + b0 * strideX, ldx, strideX,
+                                               d_B + b0 * strideB, ldb, strideB, d_R + b0 * strideR, ldr, strideR, opt(d_W, b0 * strideR));
+    });
 }
 
 int mpf_gerfs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, const double *d_LU, int64_t ldlu,
@@ -446,39 +383,29 @@ int mpf_gerfs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_A, int6
                               const double *d_B, int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t itmax,
                               double *d_ferr, double *d_berr, int32_t *d_iters) {
     if (!c) return -1;
-    int rc = check_sizes_refine_blocked(c, "gerfs_batched_blocked", n, batch);
+    const char *who = "gerfs_batched_blocked";
+    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, ONE_AT_A_TIME);
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
-    if (batch > 1 && strideP < n) { c->err = "gerfs_batched_blocked: stride of ipiv < n"; return -1; }
     if (nrhs < 0) { c->err = "gerfs_batched_blocked: nrhs must not be negative"; return -1; }
     if (trans != 0 && trans != 1) { c->err = "gerfs_batched_blocked: trans must be 0 or 1"; return -1; }
     if (n == 0 || batch == 0 || nrhs == 0) return 0;
-    rc = check_strided(c, "gerfs_batched_blocked", "A", lda, strideA, n, n, batch);
-    if (!rc) rc = check_strided(c, "gerfs_batched_blocked", "LU", ldlu, strideLU, n, n, batch);
-    if (!rc) rc = check_strided(c, "gerfs_batched_blocked", "B", ldb, strideB, n, nrhs, batch);
-    if (!rc) rc = check_strided(c, "gerfs_batched_blocked", "X", ldx, strideX, n, nrhs, batch);
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
+    if (!rc) rc = ba::check_strided(c->err, who, "X", ldx, strideX, n, nrhs, batch);
     if (rc) return rc;
     if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !d_berr) { c->err = "gerfs_batched_blocked: null pointer"; return -1; }
-    if (n <= BATCHED_MAXN && n < c->tune.batched_blocked_min_n)
+    if (forwards_to_small(c, n))
         return mpf_gerfs_batched(c, trans, d_A, lda, strideA, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, nrhs, d_B, ldb, strideB, d_X,
                                  ldx, strideX, itmax, d_ferr, d_berr, d_iters);
     const int it = itmax <= 0 ? 5 : (itmax > 31 ? 31 : itmax);   // mpf_gerfs's rule
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    // with the bound, a chunk is also as many matrices as keep its workspace (n + 1 doubles per column, one per column and tile of
-    // 16 chains) within 256 MB; a matrix's results do not depend on the chunk
-    int64_t step = BB_MAX_LAUNCH;
-    if (d_ferr) {
-        const int64_t fit = ((int64_t)1 << 25) / ((int64_t)nrhs * (n + 1 + (n + 15) / 16));
-        step = fit < 1 ? 1 : (fit < step ? fit : step);
-    }
-    for (int64_t b0 = 0; b0 < batch; b0 += step) {
-        const int64_t nb = batch - b0 < step ? batch - b0 : step;
-        rc = launch_gerfs_batched_blocked(c, trans, d_A + b0 * strideA, lda, strideA, d_LU + b0 * strideLU, ldlu, strideLU, n, nb,
-                                          d_ipiv + b0 * strideP, strideP, nrhs, d_B + b0 * strideB, ldb, strideB, d_X + b0 * strideX, ldx,
-                                          strideX, it, d_ferr ? d_ferr + b0 * nrhs : nullptr, d_berr + b0 * nrhs,
-                                          d_iters ? d_iters + b0 * nrhs : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    return ba::chunks(batch, d_ferr ? ba::ferr_step(BB_MAX_LAUNCH, n, nrhs) : BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_gerfs_batched_blocked(c, trans, d_A + b0 * strideA, lda, strideA, d_LU + b0 * strideLU, ldlu, strideLU, n, nb,
+                                            d_ipiv + b0 * strideP, strideP, nrhs, d_B + b0 * strideB, ldb, strideB, d_X + b0 * strideX, ldx,
+                                            strideX, it, opt(d_ferr, b0 * nrhs), d_berr + b0 * nrhs, opt(d_iters, b0 * nrhs));
+    });
 }
 
 } // extern "C"

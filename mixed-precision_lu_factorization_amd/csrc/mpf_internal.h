@@ -572,7 +572,8 @@ int launch_getdet_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, in
                            double *mant, int *expo);
 // the matrices of order 0: info[b] = 0 (when info is not null), (mant[b], expo[b]) = (0.5, 1) (when mant is not null)
 int launch_vbatched_empty(mpf_ctx *c, const int32_t *idx, int64_t count, int *info, double *mant, int *expo);
-// Blocked LU of many matrices of 1 <= n <= 1024 (batched_blocked.hip; checks, chunks and forwarding in mpf_batched.cpp): at most
+// Blocked LU of many matrices of 1 <= n <= 1024 (batched_blocked.hip, bodies in batched_blocked_body.h; checks, chunks and forwarding
+// in mpf_batched.cpp on the rules of batch_args.h): at most
 // BB_MAX_LAUNCH matrices per call (the batch is a grid's second dimension).  launch_getrf_batched_blocked: the right-looking loop over
 // panels of nb = 8, 16 or 32 columns -- panel, row block, trailing update, each ONE launch for the whole batch; valu != 0: the fused
 // update on the VALU kernel; stages: bit 0 panel, 1 row block, 2 update (7 everywhere but in the probe library's per-stage timing).
@@ -605,9 +606,9 @@ int launch_gerfs_batched_blocked(mpf_ctx *c, int trans, const double *A, int64_t
                                  int64_t strideLU, int n, int64_t batch, const int *ipiv, int64_t strideP, int nrhs, const double *B,
                                  int64_t ldb, int64_t strideB, double *X, int64_t ldx, int64_t strideX, int itmax, double *ferr, double *berr,
                                  int *iters);
-// The same for matrices of different orders (vbatched_blocked.hip, bodies in batched_blocked_body.h; descriptor, groups and chunks in
-// mpf_batched.cpp): `count` <= BB_MAX_LAUNCH entries of a list ordered by n, idx[i] = the matrix of entry i, nmax = the largest order
-// among them.  launch_getrf_vbatched_blocked_step: ONE panel step of the right-looking loop at column j0 (a multiple of nb = 8, 16 or
+// The same for matrices of different orders (vbatched_blocked.hip, on the same bodies of batched_blocked_body.h; descriptor, groups
+// and chunks in mpf_batched.cpp): `count` <= BB_MAX_LAUNCH entries of a list ordered by n, idx[i] = the matrix of entry i, nmax = the
+// largest order among them.  launch_getrf_vbatched_blocked_step: ONE panel step of the right-looking loop at column j0 (a multiple of nb = 8, 16 or
 // 32, as vbatched_blocked_nb resolves the option) over the entries still active there (n > j0; vbatch_plan.h: factor_steps) -- panel,
 // row block, trailing update, each one launch sized for nmax.  The other three: one launch each, sized for nmax.
 int vbatched_blocked_nb(int nb);

@@ -2,8 +2,8 @@
 // mpf_vbatch_create_blocked (contracts in include/mpf_c.h, descriptor and host side in mpf_batched.cpp, the host plan and the per-step
 // schedule in vbatch_plan.h).
 //
-// The arithmetic is batched_blocked_body.h's: the bodies of batched_blocked.hip's fixed-size kernels, statement for statement, so a
-// matrix's bits are those of the fixed-size blocked entry on that matrix alone.  What is new here is vbatched.hip's fetch: a workgroup
+// The arithmetic is batched_blocked_body.h's: the very bodies that batched_blocked.hip's fixed-size kernels call, so a matrix's bits
+// are those of the fixed-size blocked entry on that matrix alone.  What is new here is vbatched.hip's fetch: a workgroup
 // takes entry i = blockIdx.y (the panel and the determinant: blockIdx.x) of a list ordered by n, reads the matrix's index b = idx[i],
 // then n[b], off[b], ld[b] and offv[b], and calls the body with its own work item blockIdx.x.  Grids and blocks are sized for the
 // largest matrix of the launch; a body leaves as a whole when its item lies outside its own matrix.  The factorization launches each

@@ -8,7 +8,7 @@ window (as tools/vbatched_probe.py).
   (b) uniform descriptors of n = 256 and n = 512 with batch 64 and 1024, against the fixed-size blocked entry on the same buffer: what
       the index list and the per-matrix (n, off, ld, offv) loads cost when nothing is ragged;
   (c) both routes must agree bit for bit, in (a) and in (b): asserted.
-The fixed-size entries are the baselines and are unchanged code (csrc/batched_blocked.hip).
+The fixed-size entries (csrc/batched_blocked.hip) are the baselines: the same bodies (csrc/batched_blocked_body.h) behind a strided fetch.
 Writes profiles/vbatched_blocked_probe.json.  Conditions recorded with the numbers: every mixed ratio grouped / vbatched above 1, every
 uniform ratio vbatched / fixed at most 1.26.
 Usage: python tools/vbatched_blocked_probe.py [out.json] [total MB]"""
