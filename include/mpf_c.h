@@ -685,7 +685,8 @@ int mpf_getdet(mpf_ctx *ctx, const double *d_LU, int64_t ldlu, const int32_t *d_
  * at these sizes.  No driver uses them; the inverse and the determinant from the factors are mpf_getri_batched and mpf_getdet_batched
  * below; matrices of different orders in one call: the mpf_*_vbatched entries after them; refinement, error bounds and rcond for these
  * batches: the mpf_*_batched expert entries after mpf_getdet_batched, and for one order up to 1024 the mpf_*_batched_blocked expert
- * entries after mpf_getdet_batched_blocked (there is none for the vbatched forms).
+ * entries after mpf_getdet_batched_blocked, and for a descriptor of different orders the mpf_*_vbatched expert entries after
+ * mpf_getdet_vbatched.
  *
  * Layout: A[b] = d_A + b * strideA, n x n column-major, lda >= n, strideA >= lda * n (or batch == 1);
  * ipiv[b] = d_ipiv + b * strideP, strideP >= n (or batch == 1), 1-based as LAPACK; d_info: batch int32 on the device, optional.
@@ -944,7 +945,8 @@ int mpf_gerfs_batched_blocked(mpf_ctx *ctx, int32_t trans, const double *d_A, in
  * mpf_vbatch_info / mpf_vbatch_offsets: what creation computed (any output may be NULL); offM = the matrix offsets, offV the vector ones.
  *
  * Not here: pointer arrays to separate allocations, n > 128 (mpf_vbatch_create_blocked below), a per-matrix nrhs, sizes given on the
- * device, a block-diagonal matrix-vector product with the inverses, fp16, refinement.  No driver uses these. */
+ * device, a block-diagonal matrix-vector product with the inverses, fp16.  Refinement, error bounds and rcond: the expert entries
+ * after mpf_getdet_vbatched.  No driver uses these. */
 typedef struct mpf_vbatch mpf_vbatch;
 int mpf_vbatch_create(mpf_ctx *ctx, int64_t batch, const int32_t *n /* host */, const int64_t *ld /* host, optional */,
                       const int64_t *off /* host, optional */, mpf_vbatch **out);
@@ -968,7 +970,8 @@ int mpf_vbatch_create(mpf_ctx *ctx, int64_t batch, const int32_t *n /* host */, 
  * Asynchronous on the context's stream, no workspace beyond the descriptor, nothing read back; every launch is an ordinary launch (no
  * kernel waits for another workgroup, no bounded spin, no co-residency requirement); a group with more than 32768 matrices is launched
  * in chunks.
- * Not here: pointer arrays, a per-matrix nrhs, sizes given on the device, fp16, refinement; no driver uses it. */
+ * Not here: pointer arrays, a per-matrix nrhs, sizes given on the device, fp16; no driver uses it.  Refinement, error bounds and
+ * rcond: the expert entries after mpf_getdet_vbatched. */
 int mpf_vbatch_create_blocked(mpf_ctx *ctx, int64_t batch, const int32_t *n /* host */, const int64_t *ld /* host, optional */,
                               const int64_t *off /* host, optional */, mpf_vbatch **out);
 void mpf_vbatch_destroy(mpf_vbatch *vb);
@@ -991,6 +994,40 @@ int mpf_getri_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, const double *d_LU, c
                        int32_t *d_info /* optional */);
 /* mpf_getdet_batched's (mant, expo) per matrix; n[b] == 0 gives (0.5, 1), mpf_getdet's N = 0 case. */
 int mpf_getdet_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, const double *d_LU, const int32_t *d_ipiv, double *d_mant, int32_t *d_expo);
+/* The expert layer on a descriptor of EITHER kind (csrc/vbatched_refine.hip, bodies in csrc/batched_refine_blocked_body.h): norms, exact
+ * reciprocal condition numbers, the residual step operator and the refinement with berr and an exact ferr for all matrices of the
+ * descriptor in a handful of ordinary launches.
+ * Layouts: the matrices (A, LU) in the descriptor's layout; X, B, R and W tall total_n x nrhs column-major matrices, matrix b's rows at
+ * offV[b] .., every leading dimension >= total_n (mpf_getrs_vbatched's B); the pivots at offV[b]; per-matrix outputs (d_out, d_anorm,
+ * d_rcond, d_ainvnm) at b, per-column outputs (d_ferr, d_berr, d_iters) at b * nrhs + c.
+ * Contract: for every b every output equals, bit for bit, what the fixed-size BLOCKED expert entry above (mpf_lange_batched_blocked,
+ * mpf_gecon_batched_blocked, mpf_residual_batched_blocked, mpf_gerfs_batched_blocked) returns for that matrix alone with n = n[b], and
+ * so, for n[b] <= 128, what the small expert entry returns.  The result depends on nothing but the matrix, its factors and its
+ * columns: not on the batch or the position, the orders launched beside it, ld, off or nrhs, the chunk or the kind of descriptor.  The
+ * rule, constants and stop reasons of the refinement, the itmax handling, the rcond = 0 cases and the NaN behaviour are the fixed
+ * entries', word for word; rows n[b] .. ld[b]-1 and every byte between matrices are neither read nor written, nor are rows of X, B, R,
+ * W outside 0 .. total_n-1.  d_R may be d_B.
+ * Path: every matrix of order >= 1 runs the ragged forms of the blocked expert kernels, whatever the descriptor's kind and option
+ * batched_blocked_min_n (the tree padded to 1024 is the tree padded to 128, so the small entries' bits come out for n <= 128).  The
+ * list ordered by n is cut into launch groups at the orders 64, 128, 256, 512, 1024, a group into chunks of at most 32768 matrices;
+ * grids and blocks are sized for the largest matrix of a launch.  Matrices of order 0 own no rows; their outputs are norm 0, rcond 1 and
+ * ainvnm 0 (dgecon's quick return), berr = ferr = 0 and iters = 0 for each column.
+ * Asynchronous on the context's stream, nothing read back, no kernel waits for another workgroup and nothing spins.  Workspace (the
+ * context's, grow-only): gecon one double per (matrix, tile of 16 chains); gerfs with d_ferr n[b] + 1 doubles per (matrix, column) and
+ * one per (matrix, column, tile), at most 256 MB: such a call goes in chunks of as many matrices as fit (at least one).  Nothing is
+ * proportional to n^2.
+ * Return 0, or < 0 with a message: NULL pointers, a descriptor of another context, a bad letter or trans, nrhs < 0, a leading
+ * dimension < total_n.  batch == 0, total_n == 0 and nrhs == 0 do no work on matrices.
+ * Not here: forms of the small expert kernels' 8 / 16 / 32 lanes per matrix (orders <= 32 run a workgroup each), equilibration,
+ * dlacn2 estimates, an extra-precise residual, a per-matrix nrhs, pointer arrays; no driver uses these. */
+int mpf_lange_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, char norm, const double *d_A, double *d_out /* device, batch */);
+int mpf_gecon_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, char norm, const double *d_LU, const double *d_anorm /* device, batch */,
+                       double *d_rcond /* device, batch */, double *d_ainvnm /* optional: device, batch */);
+int mpf_residual_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, int32_t trans, const double *d_A, int32_t nrhs, const double *d_X, int64_t ldx,
+                          const double *d_B, int64_t ldb, double *d_R, int64_t ldr, double *d_W /* optional, ldr */);
+int mpf_gerfs_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, int32_t trans, const double *d_A, const double *d_LU, const int32_t *d_ipiv,
+                       int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *d_ferr /* optional */,
+                       double *d_berr, int32_t *d_iters /* optional */);
 
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block

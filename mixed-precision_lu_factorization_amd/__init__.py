@@ -45,6 +45,7 @@ C_ABI_SYMBOLS = [
     "mpf_lange_batched_blocked", "mpf_gecon_batched_blocked", "mpf_residual_batched_blocked", "mpf_gerfs_batched_blocked",
     "mpf_vbatch_create", "mpf_vbatch_create_blocked", "mpf_vbatch_destroy", "mpf_vbatch_info", "mpf_vbatch_offsets",
     "mpf_getrf_vbatched", "mpf_getrs_vbatched", "mpf_getri_vbatched", "mpf_getdet_vbatched",
+    "mpf_lange_vbatched", "mpf_gecon_vbatched", "mpf_residual_vbatched", "mpf_gerfs_vbatched",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -238,6 +239,10 @@ def load_library(probe=False):
     L.mpf_getrs_vbatched.argtypes = [vp, vp, i32, vp, vp, i32, vp, i64]
     L.mpf_getri_vbatched.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mpf_getdet_vbatched.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mpf_lange_vbatched.argtypes = [vp, vp, C.c_char, vp, vp]
+    L.mpf_gecon_vbatched.argtypes = [vp, vp, C.c_char, vp, vp, vp, vp]
+    L.mpf_residual_vbatched.argtypes = [vp, vp, i32, vp, i32, vp, i64, vp, i64, vp, i64, vp]
+    L.mpf_gerfs_vbatched.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, i64, i32, vp, vp, vp]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -1595,3 +1600,103 @@ class VBatch:
         mant, expo = self.getdet(A_or_LU, ipiv)
         sign = t.where(t.isnan(mant), mant, t.sign(mant))
         return sign, t.log(t.abs(mant)) + expo.to(t.float64) * math.log(2.0)
+
+    # ---- the expert layer (include/mpf_c.h: mpf_lange_vbatched, mpf_gecon_vbatched, mpf_residual_vbatched, mpf_gerfs_vbatched) --------------
+    # Every result of matrix b is bit for bit what the *_batched_blocked method returns for that matrix alone (for n[b] <= 128 also what
+    # the small *_batched method returns), on a descriptor of either kind.
+    def _tall(self, M, what, overwrite, copy=True):
+        """(tensor, ld) of a tall (total_n, nrhs) column-major operand: M itself when it is column-major, else a column-major copy
+        (refused with overwrite=True)."""
+        ctx = self.ctx
+        assert M.dim() == 2 and M.shape[0] == self.total_n and M.dtype == ctx.torch.float64 and M.is_cuda, f"{what}: (total_n, nrhs) float64"
+        nrhs = M.shape[1]
+        colmajor = (M.shape[0] <= 1 or M.stride(0) == 1) and (nrhs <= 1 or M.stride(1) >= max(self.total_n, 1))
+        if overwrite and not colmajor:
+            raise MPFError(f"{what}: overwrite=True needs a column-major tensor (MPFContext.colmajor); this one would be copied")
+        if not colmajor or (copy and not overwrite):
+            T = ctx.colmajor(self.total_n, nrhs)
+            T.copy_(M)
+            M = T
+        return M, (M.stride(1) if nrhs > 1 else max(self.total_n, 1))
+
+    def lange(self, A, norm="1"):
+        """mpf_lange_vbatched: the '1' / 'O', 'I' or 'M' norm of every matrix of the flat tensor A, a float64 (batch,) device tensor
+        (0 for a matrix of order 0)."""
+        ctx, t = self.ctx, self.ctx.torch
+        ctx._bind()
+        out = t.zeros(self.batch, dtype=t.float64, device=ctx.device)
+        ctx._check(ctx.L.mpf_lange_vbatched(ctx.h, self.h, norm.encode()[:1], _ptr(self._flat(A, "lange")), _ptr(out)), "mpf_lange_vbatched")
+        return out
+
+    def gecon(self, LU, anorm, norm="1", want_ainvnm=False):
+        """mpf_gecon_vbatched: rcond[b] = (1 / ||(L U)^-1||) / anorm[b] from getrf's factors, the norm of the inverse exact.  anorm: a
+        float64 (batch,) device tensor (lange of the matrices, same norm).  Returns rcond, or (rcond, ainvnm) with want_ainvnm; rcond
+        is 0 for anorm 0, a zero on U's diagonal or a non-finite inverse, 1 for a matrix of order 0."""
+        ctx, t = self.ctx, self.ctx.torch
+        ctx._bind()
+        assert anorm.dtype == t.float64 and anorm.is_cuda and anorm.shape == (self.batch,)
+        anorm = anorm.contiguous()
+        rcond = t.zeros(self.batch, dtype=t.float64, device=ctx.device)
+        ainv = t.zeros(self.batch, dtype=t.float64, device=ctx.device) if want_ainvnm else None
+        rc = ctx.L.mpf_gecon_vbatched(ctx.h, self.h, norm.encode()[:1], _ptr(self._flat(LU, "gecon")), _ptr(anorm), _ptr(rcond),
+                                      _ptr(ainv) if want_ainvnm else None)
+        ctx._check(rc, "mpf_gecon_vbatched")
+        return (rcond, ainv) if want_ainvnm else rcond
+
+    def residual(self, A, X, B, trans=False, want_w=True):
+        """mpf_residual_vbatched: (R, W) with R = B - op(D) X and W = |B| + |op(D)| |X| for the block-diagonal D of the matrices in
+        the flat tensor A (W None without want_w), new column-major tensors; X and B are (total_n, nrhs), or (total_n,)."""
+        ctx = self.ctx
+        ctx._bind()
+        if B.dim() == 1:
+            R, W = self.residual(A, X.unsqueeze(1), B.unsqueeze(1), trans, want_w)
+            return R.squeeze(1), (W.squeeze(1) if want_w else None)
+        assert X.shape == B.shape
+        nrhs = B.shape[1]
+        Xm, ldx = self._tall(X, "residual X", False, copy=False)
+        Bm, ldb = self._tall(B, "residual B", False, copy=False)
+        R = ctx.colmajor(self.total_n, nrhs)
+        W = ctx.colmajor(self.total_n, nrhs) if want_w else None
+        ldr = R.stride(1) if nrhs > 1 else max(self.total_n, 1)
+        rc = ctx.L.mpf_residual_vbatched(ctx.h, self.h, int(bool(trans)), _ptr(self._flat(A, "residual")), nrhs, _ptr(Xm), ldx, _ptr(Bm), ldb,
+                                         _ptr(R), ldr, _ptr(W) if want_w else None)
+        ctx._check(rc, "mpf_residual_vbatched")
+        return R, W
+
+    def gerfs(self, A, LU, ipiv, B, X, trans=False, itmax=0, overwrite=False, want_ferr=True):
+        """mpf_gerfs_vbatched: dgerfs per matrix and column with getrf's factors.  X holds a solution (getrs's) and is refined: a new
+        column-major tensor, or X itself with overwrite=True.  Returns (X, ferr, berr, iters): float64 / int32 (batch, nrhs) device
+        tensors (ferr None without want_ferr); the columns of a matrix of order 0 give 0."""
+        ctx, t = self.ctx, self.ctx.torch
+        ctx._bind()
+        if B.dim() == 1:
+            Xr, ferr, berr, its = self.gerfs(A, LU, ipiv, B.unsqueeze(1), X.unsqueeze(1), trans, itmax, overwrite, want_ferr)
+            return Xr.squeeze(1), ferr, berr, its
+        assert X.shape == B.shape
+        nrhs = B.shape[1]
+        Bm, ldb = self._tall(B, "gerfs B", False, copy=False)
+        Xm, ldx = self._tall(X, "gerfs X", overwrite)
+        ferr = t.zeros((self.batch, nrhs), dtype=t.float64, device=ctx.device) if want_ferr else None
+        berr = t.zeros((self.batch, nrhs), dtype=t.float64, device=ctx.device)
+        its = t.zeros((self.batch, nrhs), dtype=t.int32, device=ctx.device)
+        rc = ctx.L.mpf_gerfs_vbatched(ctx.h, self.h, int(bool(trans)), _ptr(self._flat(A, "gerfs")), _ptr(self._flat(LU, "gerfs LU")),
+                                      _ptr(self._pivots(ipiv)), nrhs, _ptr(Bm), ldb, _ptr(Xm), ldx, int(itmax),
+                                      _ptr(ferr) if want_ferr else None, _ptr(berr), _ptr(its))
+        ctx._check(rc, "mpf_gerfs_vbatched")
+        return Xm, ferr, berr, its
+
+    def cond(self, A, norm="1"):
+        """rcond of every matrix in the flat tensor A: getrf on a copy, lange, gecon.  0 for a singular matrix; nothing is read back."""
+        LU, _, _ = self.getrf(A)
+        return self.gecon(LU, self.lange(A, norm), norm)
+
+    def solvex(self, A, B, trans=False, itmax=0):
+        """dgesvx's shape without equilibration for the whole descriptor: getrf on a copy, lange / gecon (the '1' norm, or 'I' with
+        trans), getrs, gerfs.  Returns (X, rcond, ferr, berr, info), all on the device; never raises on a singular matrix: info[b] is
+        its first zero pivot and rcond[b] is 0 (its X, ferr and berr are not meaningful)."""
+        norm = "I" if trans else "1"
+        LU, ipiv, info = self.getrf(A)
+        rcond = self.gecon(LU, self.lange(A, norm), norm)
+        X = self.getrs(LU, ipiv, B, trans=trans)
+        X, ferr, berr, _ = self.gerfs(A, LU, ipiv, B, X, trans=trans, itmax=itmax, overwrite=True)
+        return X, rcond, ferr, berr, info

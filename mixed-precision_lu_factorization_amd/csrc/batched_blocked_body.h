@@ -70,6 +70,19 @@ constexpr int BB_UT = 64;    // trailing update: tile of C
 constexpr int BB_IG = 8;     // inverse: rows per register group of the diagonal solve
 constexpr int BB_UG = 16;    // inverse: factor elements per load group of the update
 
+// The ragged launches' fetch (vbatched_blocked.hip, vbatched_refine.hip): entry i of a list ordered by n is matrix b = idx[i]; its order,
+// matrix offset, leading dimension and vector offset come from the descriptor's arrays
+struct bbv_entry { int b, n; long long off, ld, offv; };
+__device__ __forceinline__ bbv_entry bbv_fetch(const BtRagged &v, const int *idx, unsigned i) {
+    bbv_entry e;
+    e.b = idx[i];
+    e.n = v.n[e.b];
+    e.off = v.off[e.b];
+    e.ld = v.ld[e.b];
+    e.offv = v.offv[e.b];
+    return e;
+}
+
 // ---- panel (bb_panel_kernel) ----------------------------------------------------------------------------------------------------------
 // A: the matrix; ipiv: the matrix's pivots; info: the matrix's entry or null.  blockDim.x >= n - j0 in whole waves (<= 1024)
 template <int NB, bool FUSED>

@@ -17,6 +17,9 @@
 // prefix sums, size classes) uploaded once; each call then launches one ragged kernel of vbatched.hip per class that is not empty.
 // A descriptor from mpf_vbatch_create_blocked (orders up to 1024) also has the plan's large list: its matrices take the ragged blocked
 // kernels of vbatched_blocked.hip, launch group by launch group, the factorization panel step by panel step over the active suffix.
+//   mpf_lange_vbatched, mpf_gecon_vbatched, mpf_residual_vbatched, mpf_gerfs_vbatched   the expert layer on a descriptor of either kind:
+//                       every matrix of order >= 1 takes the ragged blocked expert kernels of vbatched_refine.hip, launch group by
+//                       launch group of the whole ordered list (vbatch_plan.h: refine_chunks)
 #include "mpf_internal.h"
 #include "batch_args.h"
 #include "vbatch_plan.h"
@@ -28,6 +31,7 @@ struct mpf_vbatch {
     vbatch::Plan plan;
     Buf<int32_t> d_n, d_list;
     Buf<int64_t> d_off, d_ld, d_offv;
+    Buf<int64_t> d_lrow, d_ltile;   // the plan's prefix sums by list position (the expert layer's workspace layout), batch + 1 each
 };
 
 namespace {
@@ -435,6 +439,10 @@ int vb_create(mpf_ctx *c, const char *who, int maxn, int min_n, int64_t batch, c
         MPF_HIP_TRY(c, hipMemcpy(vb->d_off.get(), p.off.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice));
         MPF_HIP_TRY(c, hipMemcpy(vb->d_ld.get(), p.ld.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice));
         MPF_HIP_TRY(c, hipMemcpy(vb->d_offv.get(), p.offv.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice));
+        MPF_HIP_TRY(c, vb->d_lrow.grow(batch + 1));
+        MPF_HIP_TRY(c, vb->d_ltile.grow(batch + 1));
+        MPF_HIP_TRY(c, hipMemcpy(vb->d_lrow.get(), p.lrow.data(), (size_t)(batch + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+        MPF_HIP_TRY(c, hipMemcpy(vb->d_ltile.get(), p.ltile.data(), (size_t)(batch + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     *out = vb.release();
     return 0;
@@ -520,6 +528,38 @@ int vb_large(const mpf_vbatch *vb, F f) {
             const int rc = f(vb->d_list.get() + at, nb, (int)ns.back(), ns.data());
             if (rc) return rc;
         }
+    return 0;
+}
+// The expert layer's launch groups over every matrix of order >= 1, list[zeros .. batch) (vbatch_plan.h: refine_chunks; limit > 0: the
+// refinement's workspace cut): f(device list + first, count, nmax, the chunk's workspace frame, its rows and tiles)
+constexpr int64_t RBV_WORK_LIMIT = (int64_t)1 << 25;   // doubles (256 MB): batch_args::ferr_step's
+struct RbvNeed { int64_t rows = 0, tiles = 0, count = 0; };
+std::vector<vbatch::Chunk> vb_refine_chunks(const mpf_vbatch *vb, int64_t nrhs, int64_t limit, RbvNeed *need) {
+    const vbatch::Plan &p = vb->plan;
+    std::vector<vbatch::Chunk> ch = vbatch::refine_chunks(p.ln.data() + p.zeros, p.batch - p.zeros, BB_MAX_LAUNCH, nrhs, limit);
+    for (vbatch::Chunk &k : ch) {
+        k.first += p.zeros;                                          // (a list position from here on)
+        if (!need) continue;
+        const size_t a = (size_t)k.first, e = (size_t)(k.first + k.count);
+        need->rows = std::max(need->rows, p.lrow[e] - p.lrow[a]);
+        need->tiles = std::max(need->tiles, p.ltile[e] - p.ltile[a]);
+        need->count = std::max(need->count, k.count);
+    }
+    return ch;
+}
+RbvWork vb_work(mpf_ctx *c, const mpf_vbatch *vb, const vbatch::Chunk &k) {
+    const vbatch::Plan &p = vb->plan;
+    return RbvWork{vb->d_lrow.get() + k.first, vb->d_ltile.get() + k.first, p.lrow[(size_t)k.first], p.ltile[(size_t)k.first],
+                   c->rb_part.get(), c->rb_g.get(), c->rb_xm.get()};
+}
+// the order-0 matrices' outputs
+int vb_refine_empty(mpf_ctx *c, const mpf_vbatch *vb, int nrhs, double *norm, double *rcond, double *ainvnm, double *berr, double *ferr,
+                    int32_t *iters) {
+    for (int64_t i0 = 0; i0 < vb->plan.zeros; i0 += BT_MAX_LAUNCH) {
+        const int64_t nb = vb->plan.zeros - i0 < BT_MAX_LAUNCH ? vb->plan.zeros - i0 : BT_MAX_LAUNCH;
+        const int rc = launch_refine_vbatched_empty(c, vb->d_list.get() + i0, nb, nrhs, norm, rcond, ainvnm, berr, ferr, iters);
+        if (rc) return rc;
+    }
     return 0;
 }
 BtRagged vb_arrays(const mpf_vbatch *vb) { return BtRagged{vb->d_n.get(), vb->d_off.get(), vb->d_ld.get(), vb->d_offv.get()}; }
@@ -620,6 +660,111 @@ int mpf_getdet_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_LU, co
     return vb_large(vb, [&](const int32_t *idx, int64_t count, int, const int32_t *) {
         return launch_getdet_vbatched_blocked(c, v, idx, count, d_LU, d_ipiv, d_mant, d_expo);
     });
+}
+
+// ---- the expert layer on a descriptor of either kind (kernels in vbatched_refine.hip) -----------------------------------------------------
+// Every matrix of order >= 1 takes the ragged blocked expert kernels, whose bits for n <= 128 are the small expert entries' by contract:
+// the descriptor's classes and batched_blocked_min_n play no part.
+int mpf_lange_vbatched(mpf_ctx *c, const mpf_vbatch *vb, char norm, const double *d_A, double *d_out) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "lange_vbatched");
+    if (rc) return rc;
+    int mode;
+    if (norm == '1' || norm == 'O' || norm == 'o') mode = 0;
+    else if (norm == 'I' || norm == 'i') mode = 1;
+    else if (norm == 'M' || norm == 'm') mode = 2;
+    else { c->err = "lange_vbatched: norm must be '1', 'O', 'I' or 'M'"; return -1; }
+    if (vb->plan.batch == 0) return 0;
+    if (!d_out || (vb->plan.total_n > 0 && !d_A)) { c->err = "lange_vbatched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    rc = vb_refine_empty(c, vb, 0, d_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    const BtRagged v = vb_arrays(vb);
+    for (const vbatch::Chunk &k : vb_refine_chunks(vb, 0, 0, nullptr)) {
+        rc = launch_lange_vbatched(c, v, vb->d_list.get() + k.first, k.count, k.nmax, mode, d_A, d_out);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_gecon_vbatched(mpf_ctx *c, const mpf_vbatch *vb, char norm, const double *d_LU, const double *d_anorm, double *d_rcond,
+                       double *d_ainvnm) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "gecon_vbatched");
+    if (rc) return rc;
+    const bool one = norm == '1' || norm == 'O' || norm == 'o';
+    if (!one && norm != 'I' && norm != 'i') { c->err = "gecon_vbatched: norm must be '1', 'O' or 'I'"; return -1; }
+    if (vb->plan.batch == 0) return 0;
+    if (!d_rcond || (vb->plan.total_n > 0 && (!d_LU || !d_anorm))) { c->err = "gecon_vbatched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    rc = vb_refine_empty(c, vb, 0, nullptr, d_rcond, d_ainvnm, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    RbvNeed need;
+    const std::vector<vbatch::Chunk> chunks = vb_refine_chunks(vb, 0, 0, &need);
+    MPF_HIP_TRY(c, c->rb_part.grow(need.tiles));                    // (once, before the first launch that uses it)
+    const BtRagged v = vb_arrays(vb);
+    for (const vbatch::Chunk &k : chunks) {
+        rc = launch_gecon_vbatched(c, v, vb->d_list.get() + k.first, vb_work(c, vb, k), k.count, k.nmax, one ? 0 : 1, d_LU, d_anorm, d_rcond,
+                                   d_ainvnm);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_residual_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const double *d_A, int32_t nrhs, const double *d_X, int64_t ldx,
+                          const double *d_B, int64_t ldb, double *d_R, int64_t ldr, double *d_W) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "residual_vbatched");
+    if (rc) return rc;
+    if (nrhs < 0) { c->err = "residual_vbatched: nrhs must not be negative"; return -1; }
+    if (trans != 0 && trans != 1) { c->err = "residual_vbatched: trans must be 0 or 1"; return -1; }
+    if (vb->plan.batch == 0 || vb->plan.total_n == 0 || nrhs == 0) return 0;
+    if (ldx < vb->plan.total_n) { c->err = "residual_vbatched: leading dimension of X < total_n"; return -1; }
+    if (ldb < vb->plan.total_n) { c->err = "residual_vbatched: leading dimension of B < total_n"; return -1; }
+    if (ldr < vb->plan.total_n) { c->err = "residual_vbatched: leading dimension of R < total_n"; return -1; }
+    if (!d_A || !d_X || !d_B || !d_R) { c->err = "residual_vbatched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const BtRagged v = vb_arrays(vb);
+    for (const vbatch::Chunk &k : vb_refine_chunks(vb, 0, 0, nullptr)) {
+        rc = launch_residual_vbatched(c, v, vb->d_list.get() + k.first, k.count, k.nmax, trans, d_A, nrhs, d_X, ldx, d_B, ldb, d_R, ldr, d_W);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_gerfs_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const double *d_A, const double *d_LU, const int32_t *d_ipiv,
+                       int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *d_ferr, double *d_berr,
+                       int32_t *d_iters) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "gerfs_vbatched");
+    if (rc) return rc;
+    if (nrhs < 0) { c->err = "gerfs_vbatched: nrhs must not be negative"; return -1; }
+    if (trans != 0 && trans != 1) { c->err = "gerfs_vbatched: trans must be 0 or 1"; return -1; }
+    if (vb->plan.batch == 0 || nrhs == 0) return 0;
+    if (!d_berr) { c->err = "gerfs_vbatched: null pointer"; return -1; }
+    if (vb->plan.total_n > 0) {
+        if (ldb < vb->plan.total_n) { c->err = "gerfs_vbatched: leading dimension of B < total_n"; return -1; }
+        if (ldx < vb->plan.total_n) { c->err = "gerfs_vbatched: leading dimension of X < total_n"; return -1; }
+        if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X) { c->err = "gerfs_vbatched: null pointer"; return -1; }
+    }
+    const int it = itmax <= 0 ? 5 : (itmax > 31 ? 31 : itmax);   // mpf_gerfs's rule
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    rc = vb_refine_empty(c, vb, nrhs, nullptr, nullptr, nullptr, d_berr, d_ferr, d_iters);
+    if (rc) return rc;
+    RbvNeed need;
+    const std::vector<vbatch::Chunk> chunks = vb_refine_chunks(vb, nrhs, d_ferr ? RBV_WORK_LIMIT : 0, &need);
+    if (d_ferr) {                                                   // (once, before the first launch that uses them)
+        MPF_HIP_TRY(c, c->rb_g.grow(need.rows * nrhs));
+        MPF_HIP_TRY(c, c->rb_xm.grow(need.count * nrhs));
+        MPF_HIP_TRY(c, c->rb_part.grow(need.tiles * nrhs));
+    }
+    const BtRagged v = vb_arrays(vb);
+    for (const vbatch::Chunk &k : chunks) {
+        rc = launch_gerfs_vbatched(c, v, vb->d_list.get() + k.first, vb_work(c, vb, k), k.count, k.nmax, trans, d_A, d_LU, d_ipiv, nrhs, d_B,
+                                   ldb, d_X, ldx, it, d_ferr, d_berr, d_iters);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 } // extern "C"

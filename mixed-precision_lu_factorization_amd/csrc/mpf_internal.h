@@ -225,7 +225,7 @@ struct mpf_ctx {
     // inverse and determinant (mpf_getri.cpp, getri.hip): ceil(N / 256) x 256 x 256 doubles -- L's block inverses transposed, then the
     // 256-row panel of the interchange pass; mpf_getdet's chunk results
     Buf<double> getri_buf;
-    // blocked batched expert layer (batched_refine_blocked.hip): g per (matrix, column, row) and max |x| per (matrix, column) between
+    // blocked batched expert layer (batched_refine_blocked.hip, vbatched_refine.hip): g per (matrix, column, row) and max |x| per (matrix, column) between
     // the refinement and its bound; the tile maxima of the reduced chains per (matrix[, column], tile)
     Buf<double> rb_g, rb_xm, rb_part;
     // factored 32x32 diagonal tiles of the fp64 panel, parked here until every workgroup of the sub-panel launches has
@@ -620,6 +620,23 @@ int launch_getri_vbatched_blocked(mpf_ctx *c, const BtRagged &v, const int32_t *
                                   const int *ipiv, double *inv, int *info, int ct);
 int launch_getdet_vbatched_blocked(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, const double *LU, const int *ipiv,
                                    double *mant, int *expo);
+// The expert layer for matrices of different orders (vbatched_refine.hip, on the bodies of batched_refine_blocked_body.h that
+// batched_refine_blocked.hip calls too; launch groups: vbatch_plan.h refine_chunks): `count` <= BB_MAX_LAUNCH entries of a list ordered
+// by n, every order >= 1, nmax the largest.  RbvWork: where the launch's chunk keeps its workspace -- row / tile point at the chunk's first
+// entry of the descriptor's prefix sums (orders and tiles of 16 chains of the entries before a list position), row0 / tile0 are their
+// values there; part: one double per tile (gecon) or nrhs per tile (ferr), g: nrhs per row, xm: nrhs per entry of the chunk.
+// launch_refine_vbatched_empty: the order-0 matrices' outputs, whichever are not null (norm 0, rcond 1, ainvnm 0, berr = ferr = iters = 0)
+struct RbvWork { const int64_t *row, *tile; int64_t row0, tile0; double *part, *g, *xm; };
+int launch_lange_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int nmax, int mode, const double *A, double *out);
+int launch_gecon_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, const RbvWork &w, int64_t count, int nmax, int inf, const double *LU,
+                          const double *anorm, double *rcond, double *ainvnm);
+int launch_residual_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int nmax, int trans, const double *A, int nrhs,
+                             const double *X, int64_t ldx, const double *B, int64_t ldb, double *R, int64_t ldr, double *W);
+int launch_gerfs_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, const RbvWork &w, int64_t count, int nmax, int trans, const double *A,
+                          const double *LU, const int *ipiv, int nrhs, const double *B, int64_t ldb, double *X, int64_t ldx, int itmax,
+                          double *ferr, double *berr, int *iters);
+int launch_refine_vbatched_empty(mpf_ctx *c, const int32_t *idx, int64_t count, int nrhs, double *norm, double *rcond, double *ainvnm,
+                                 double *berr, double *ferr, int *iters);
 // mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
 int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 

@@ -3,7 +3,8 @@
 // (tests/vbatch_plan_driver.cpp, under AddressSanitizer and UBSan); tests/vbatched_model.py restates it in numpy.
 // mpf_vbatch_create_blocked uses the same function with the larger limit and a forwarding threshold: the matrices that the fixed-size
 // blocked entries would hand to the small kernels stay in the classes, the others form the large list and its launch groups
-// (tests/vbatch_plan_blocked_driver.cpp, tests/vbatched_blocked_model.py).
+// (tests/vbatch_plan_blocked_driver.cpp, tests/vbatched_blocked_model.py).  The expert layer cuts the whole ordered list into launch
+// groups of its own (refine_chunks; tests/vbatch_plan_refine_driver.cpp, tests/vbatched_refine_model.py).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -51,7 +52,45 @@ struct Plan {
     int64_t large_start = 0, large_count = 0;
     int64_t gstart[NGROUP] = {}, gcount[NGROUP] = {};
     int gnmax[NGROUP] = {};                  // the largest order in each group (0: the group is empty)
+    // For the expert layer (refine_chunks below), by list position: ln[i] = the order of entry i, and the sums over the entries before
+    // i of their orders (lrow) and of their tiles of REFINE_CT chains (ltile), batch + 1 entries each.  A chunk [a, a + count) of the
+    // list lays its workspace out by lrow[i] - lrow[a] and ltile[i] - ltile[a].
+    std::vector<int32_t> ln;
+    std::vector<int64_t> lrow, ltile;
 };
+
+// The launch groups of the expert layer (mpf_lange_vbatched, mpf_gecon_vbatched, mpf_residual_vbatched, mpf_gerfs_vbatched): they take
+// every matrix of order >= 1 of either kind of descriptor, list[zeros .. batch), which is in ascending order of n ACROSS the classes
+// and the large list -- plan() fills `list` by one counting sort by n, and the classes and groups are ranges of it.  A launch's block is
+// sized for its largest matrix, so the range is cut at the tops 64, 128, 256, 512, 1024: a block is at most twice what the group's
+// smallest matrix needs and never below one wave.
+constexpr int NRTOP = 5;
+constexpr int REFINE_TOP[NRTOP] = {64, 128, 256, 512, 1024};
+constexpr int REFINE_CT = 16;                 // chains per workgroup of the reduced chains: a matrix has ceil(n / 16) tiles
+struct Chunk { int64_t first, count; int nmax; };
+// ns[i] = the order of entry i, ascending, 1 <= ns[i] <= 1024.  A chunk holds at most max_launch entries of one group.  limit > 0 (the
+// refinement with its bound): a chunk's workspace -- batch_args::ferr_step's count, nrhs (n + 1 + tiles) doubles per matrix, summed over
+// the chunk's own matrices -- also stays within `limit` doubles, with at least one matrix per chunk.  The chunks are consecutive and
+// cover the list; a matrix's results do not depend on its chunk.
+inline std::vector<Chunk> refine_chunks(const int32_t *ns, int64_t count, int64_t max_launch, int64_t nrhs = 0, int64_t limit = 0) {
+    std::vector<Chunk> out;
+    if (max_launch < 1) max_launch = 1;
+    int64_t i = 0;
+    while (i < count) {
+        int g = 0;
+        while (g < NRTOP - 1 && REFINE_TOP[g] < ns[i]) ++g;
+        int64_t j = i, work = 0;
+        while (j < count && j - i < max_launch && ns[j] <= REFINE_TOP[g]) {
+            const int64_t w = nrhs * ((int64_t)ns[j] + 1 + (ns[j] + REFINE_CT - 1) / REFINE_CT);
+            if (limit > 0 && j > i && work + w > limit) break;
+            work += w;
+            ++j;
+        }
+        out.push_back(Chunk{i, j - i, (int)ns[j - 1]});
+        i = j;
+    }
+    return out;
+}
 
 // One panel step of the blocked factorization of `count` list entries ordered by n: the matrices still active at column j0 (n > j0) are
 // a suffix of the entries; a step launches only over entries first .. count-1, sized for `rows` = the largest remaining row count.
@@ -156,6 +195,16 @@ inline int plan(int64_t batch, const int32_t *n, const int64_t *ld, const int64_
     }
     p.list.resize((size_t)batch);
     for (int64_t b = 0; b < batch; ++b) p.list[(size_t)by_n[(size_t)n[b]]++] = (int32_t)b;
+    // (one counting sort by n: `list` as a whole is in ascending order of n, the order-0 matrices first)
+    p.ln.resize((size_t)batch);
+    p.lrow.assign((size_t)batch + 1, 0);
+    p.ltile.assign((size_t)batch + 1, 0);
+    for (int64_t i = 0; i < batch; ++i) {
+        const int32_t v = n[p.list[(size_t)i]];
+        p.ln[(size_t)i] = v;
+        p.lrow[(size_t)i + 1] = p.lrow[(size_t)i] + v;
+        p.ltile[(size_t)i + 1] = p.ltile[(size_t)i] + (v + REFINE_CT - 1) / REFINE_CT;
+    }
     return 0;
 }
 

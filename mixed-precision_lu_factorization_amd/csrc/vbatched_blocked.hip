@@ -13,17 +13,7 @@
 
 namespace {
 
-struct bbv_entry { int b, n; long long off, ld, offv; };
-__device__ __forceinline__ bbv_entry bbv_fetch(const BtRagged &v, const int *idx, unsigned i) {
-    bbv_entry e;
-    e.b = idx[i];
-    e.n = v.n[e.b];
-    e.off = v.off[e.b];
-    e.ld = v.ld[e.b];
-    e.offv = v.offv[e.b];
-    return e;
-}
-
+// (bbv_fetch: batched_blocked_body.h, shared with vbatched_refine.hip)
 // blockDim.x = the launch's largest row count n - j0 rounded up to whole waves (<= 1024); blockIdx.x = list entry
 template <int NB, bool FUSED>
 __global__ __launch_bounds__(1024) void bbv_panel_kernel(double *A, BtRagged v, const int *idx, int j0, int *ipiv, int *info) {
