@@ -1029,6 +1029,76 @@ int mpf_gerfs_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, int32_t trans, const 
                        int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *d_ferr /* optional */,
                        double *d_berr, int32_t *d_iters /* optional */);
 
+/* ---- equilibration of the batched layouts (csrc/batched_equil.hip) ---------------------------------------------------------
+ * mpf_geequ's power-of-two factors, dlaqge's scaling and the diagonal scaling of right-hand sides for the three batched layouts: a
+ * strided batch of one order n <= 128 (mpf_*_batched), of one order n <= 1024 (mpf_*_batched_blocked) and a descriptor of either kind
+ * (mpf_*_vbatched).  Layout rules, argument checks, error style and asynchrony are mpf_getrs_batched's, mpf_getrs_batched_blocked's and
+ * mpf_getrs_vbatched's: ordinary launches on the context's stream, nothing read back, every result a device array, rows n .. ld-1 and
+ * the bytes between matrices neither read nor written, n == 0 or batch == 0 returns 0 with no work.  The small entries refuse n > 128,
+ * the blocked ones n > 1024 (a matrix that large: mpf_geequ / mpf_gesvx, mpf_factor_dev); a blocked entry hands n below option
+ * batched_blocked_min_n to the small kernels; batches longer than one launch go in chunks.
+ * Every product below is a product with a power of two and every extreme is a maximum or minimum, so a matrix's results are the same
+ * bits on every path: they depend on the matrix and `rule` alone, not on batch, position, ld, stride, off, the orders launched beside it,
+ * the kernel form, batched_blocked_min_n or the kind of descriptor.  tests/batched_equil_model.py restates all of it in numpy.
+ *
+ * mpf_geequ_*: per matrix mpf_geequ's definitions -- r_i = 2^-floor(log2 max_j |a_ij|), c_j = 2^-floor(log2 max_i |a_ij| r_i) (the
+ * rounded product), exponents clamped to [-1022, 1022]; with rmax / rmin the largest / smallest row maximum and smlnum = DBL_MIN,
+ * rowcnd = max(rmin, smlnum) / min(rmax, 1 / smlnum), colcnd the same of the scaled column maxima, amax = the largest |a_ij|.
+ * d_r and d_c hold n doubles per matrix -- strided layouts at b n, descriptors at offV[b]; d_rowcnd, d_colcnd, d_amax (double) and
+ * d_info (int32) one per matrix; all six are required.  d_info[b]:
+ *   0           a clean matrix: everything is set.
+ *   i + 1       row i is the first zero row: amax is set, rowcnd is 0, r is set (1 for a zero row); c and colcnd are not written.
+ *   n + j + 1   column j is the first zero column of the row-scaled matrix: r, rowcnd and amax are set; c and colcnd are not written.
+ *   2 n + 1     the matrix holds a NaN or +-Inf: amax is that NaN or Inf (a NaN wherever one is present); the check comes before any
+ *               scale is formed, and r, c, rowcnd and colcnd are not written.
+ * A matrix of order 0 (descriptors): rowcnd = colcnd = 1, amax = 0, info = 0 (dgeequ's quick return).
+ *
+ * mpf_laqge_*: d_out[b] = Dr A[b] Dc by `rule`, decided per matrix on the device: 0 never (a copy); 1 dlaqge's rule as mpf_gesvx
+ * states it -- rows if rowcnd < 0.1 or amax outside [small, 1 / small] with small = DBL_MIN / DBL_EPSILON, columns if colcnd < 0.1; 2
+ * always both; any other rule returns -1.  A matrix with d_info[b] != 0 is never scaled under any rule (its rowcnd / colcnd are not
+ * looked at).  d_out may be d_A (in place: a matrix that is not scaled is then not touched); otherwise it has d_A's layout (lda,
+ * strideA / the descriptor) and must not overlap d_A.  Each element is (r_i a_ij) c_j, two rounded products in that order; a side that
+ * is not scaled contributes no product.  d_equed[b] (int32, required): 0 none, 1 rows, 2 columns, 3 both (mpf_gesvx_stats.equed's
+ * values).  d_spread (optional, 2 doubles per matrix): [2 b] = max_i r_i / min_i r_i if the rows were scaled, else 1; [2 b + 1] the
+ * same of c -- exact powers of two (Inf past 2^1023), what a driver multiplies ferr by.  Order 0: equed 0, spread 1.
+ *
+ * mpf_lascl2_*: V[b] = diag(s[b]) V[b] in place on the matrices with d_equed == NULL or d_equed[b] & bit; a matrix whose bit is clear
+ * is not touched.  V is n x nrhs per matrix laid out as mpf_getrs_batched's B (ldv, strideV), for a descriptor the tall total_n x nrhs
+ * matrix of mpf_getrs_vbatched with s at offV[b].  A driver needs multiplications only: B' = Dr B and X = Dc X' for trans = 0,
+ * B' = Dc B and X = Dr X' for trans = 1.
+ *
+ * Paths: n <= 32 runs 8 / 16 / 32 lanes of a wave per matrix, 33 .. 128 a workgroup per matrix, both reading A once; the blocked
+ * entries spread a matrix over ceil(n / 64) workgroups for the row maxima and ceil(n / 16) for the scaled column maxima, with one small
+ * launch after each (four launches, A read twice); a descriptor runs the ragged forms of those four for every order >= 1, launch
+ * group by launch group of its ordered list (the expert layer's groups).  Workspace (the context's, grow-only): two words per row of a
+ * chunk for the blocked and descriptor forms.  No kernel waits for another workgroup.
+ * Return 0, or < 0 with a message: NULL pointers, negative sizes, n over the limit, a leading dimension or stride too small, a bad
+ * rule, d_out overlapping d_A, a descriptor of another context.
+ * Not here: scaling fused into the loads of getrf / getrs; a C driver (the Python gesvx_batched composes these entries with the
+ * existing ones, refining on the equilibrated system); the 8 / 16 / 32-lane forms for the small matrices of a descriptor; mpf_geequ and
+ * the large-matrix drivers are unchanged. */
+int mpf_geequ_batched(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_r, double *d_c,
+                      double *d_rowcnd, double *d_colcnd, double *d_amax, int32_t *d_info);
+int mpf_laqge_batched(mpf_ctx *ctx, int32_t rule, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                      const double *d_r, const double *d_c, const double *d_rowcnd, const double *d_colcnd, const double *d_amax,
+                      const int32_t *d_info, double *d_out, int32_t *d_equed, double *d_spread /* optional: 2 per matrix */);
+int mpf_lascl2_batched(mpf_ctx *ctx, const double *d_s, int32_t n, int64_t batch, int32_t nrhs, double *d_V, int64_t ldv, int64_t strideV,
+                       const int32_t *d_equed /* optional */, int32_t bit);
+int mpf_geequ_batched_blocked(mpf_ctx *ctx, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_r,
+                              double *d_c, double *d_rowcnd, double *d_colcnd, double *d_amax, int32_t *d_info);
+int mpf_laqge_batched_blocked(mpf_ctx *ctx, int32_t rule, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                              const double *d_r, const double *d_c, const double *d_rowcnd, const double *d_colcnd, const double *d_amax,
+                              const int32_t *d_info, double *d_out, int32_t *d_equed, double *d_spread /* optional */);
+int mpf_lascl2_batched_blocked(mpf_ctx *ctx, const double *d_s, int32_t n, int64_t batch, int32_t nrhs, double *d_V, int64_t ldv,
+                               int64_t strideV, const int32_t *d_equed /* optional */, int32_t bit);
+int mpf_geequ_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, const double *d_A, double *d_r, double *d_c, double *d_rowcnd, double *d_colcnd,
+                       double *d_amax, int32_t *d_info);
+int mpf_laqge_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, int32_t rule, const double *d_A, const double *d_r, const double *d_c,
+                       const double *d_rowcnd, const double *d_colcnd, const double *d_amax, const int32_t *d_info, double *d_out,
+                       int32_t *d_equed, double *d_spread /* optional */);
+int mpf_lascl2_vbatched(mpf_ctx *ctx, const mpf_vbatch *vb, const double *d_s, int32_t nrhs, double *d_V, int64_t ldv,
+                        const int32_t *d_equed /* optional */, int32_t bit);
+
 /* ---- multi-GPU (build extension; the reference is single-device, MPF.cu:77) ------------------------------------
  * One process per GPU.  1-D block-cyclic columns: global column block b (nb columns) lives on rank b % world as local block
  * b / world; d_Aloc is the rank's N x (local columns) column-major matrix (ldloc >= N), d_ipiv the full pivot vector (N int32,

@@ -46,6 +46,9 @@ C_ABI_SYMBOLS = [
     "mpf_vbatch_create", "mpf_vbatch_create_blocked", "mpf_vbatch_destroy", "mpf_vbatch_info", "mpf_vbatch_offsets",
     "mpf_getrf_vbatched", "mpf_getrs_vbatched", "mpf_getri_vbatched", "mpf_getdet_vbatched",
     "mpf_lange_vbatched", "mpf_gecon_vbatched", "mpf_residual_vbatched", "mpf_gerfs_vbatched",
+    "mpf_geequ_batched", "mpf_laqge_batched", "mpf_lascl2_batched",
+    "mpf_geequ_batched_blocked", "mpf_laqge_batched_blocked", "mpf_lascl2_batched_blocked",
+    "mpf_geequ_vbatched", "mpf_laqge_vbatched", "mpf_lascl2_vbatched",
 ]
 PROBE_ONLY_SYMBOLS = ["mpf_microbench", "mpf_debug_mfma4", "mpf_debug_gate", "mpf_debug_hgemm_again"]   # include/mpf_probe.h
 CXX_SYMBOL_MPF = "_Z3MPFPdiiPi"  # void MPF(double*, int, int, int*)  (reference MPF.h:3)
@@ -243,6 +246,15 @@ def load_library(probe=False):
     L.mpf_gecon_vbatched.argtypes = [vp, vp, C.c_char, vp, vp, vp, vp]
     L.mpf_residual_vbatched.argtypes = [vp, vp, i32, vp, i32, vp, i64, vp, i64, vp, i64, vp]
     L.mpf_gerfs_vbatched.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, i64, i32, vp, vp, vp]
+    L.mpf_geequ_batched.argtypes = [vp, vp, i64, i64, i32, i64, vp, vp, vp, vp, vp, vp]
+    L.mpf_laqge_batched.argtypes = [vp, i32, vp, i64, i64, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mpf_lascl2_batched.argtypes = [vp, vp, i32, i64, i32, vp, i64, i64, vp, i32]
+    L.mpf_geequ_batched_blocked.argtypes = L.mpf_geequ_batched.argtypes
+    L.mpf_laqge_batched_blocked.argtypes = L.mpf_laqge_batched.argtypes
+    L.mpf_lascl2_batched_blocked.argtypes = L.mpf_lascl2_batched.argtypes
+    L.mpf_geequ_vbatched.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mpf_laqge_vbatched.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mpf_lascl2_vbatched.argtypes = [vp, vp, vp, i32, vp, i64, vp, i32]
     L.mpf_matgen_dev.argtypes = [vp, vp, i64, i64, i64]
     L.mpf_matgen_cols_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64]
     L.mpf_matgen_state.argtypes = [i64, C.POINTER(C.c_uint32)]
@@ -1245,7 +1257,7 @@ class MPFContext:
         return getattr(self, "gecon_batched" + suffix)(LU, getattr(self, "lange_batched" + suffix)(A, norm), norm)
 
     def solvex_batched(self, A, B, trans=False, itmax=0):
-        """dgesvx's shape without equilibration for a batch, n <= 128: getrf_batched on a copy, lange_batched / gecon_batched (the
+        """dgesvx's shape without equilibration (gesvx_batched adds it) for a batch, n <= 128: getrf_batched on a copy, lange_batched / gecon_batched (the
         '1' norm, or 'I' with trans), getrs_batched, gerfs_batched.  Returns (X, rcond, ferr, berr, info), all on the device; never
         raises on a singular matrix: info[b] is its first zero pivot and rcond[b] is 0 (its X, ferr and berr are not meaningful)."""
         return self._solvex_batched(A, B, trans, itmax, "")
@@ -1405,10 +1417,116 @@ class MPFContext:
         return self._cond_batched(A, norm, "_blocked")
 
     def solvex_batched_blocked(self, A, B, trans=False, itmax=0):
-        """solvex_batched for n <= 1024 from the blocked entries.  Returns (X, rcond, ferr, berr, info), all on the device; never
+        """solvex_batched for n <= 1024 from the blocked entries (gesvx_batched_blocked adds equilibration).  Returns (X, rcond, ferr, berr, info), all on the device; never
         raises on a singular matrix: info[b] is its first zero pivot and rcond[b] is 0."""
         return self._solvex_batched(A, B, trans, itmax, "_blocked")
 
+
+    # ---- equilibration of those batches (include/mpf_c.h: mpf_geequ_batched, mpf_laqge_batched, mpf_lascl2_batched) --------------------------
+    def geequ_batched(self, A):
+        """mpf_geequ_batched: mpf_geequ's power-of-two row and column factors of every matrix of the (batch, n, n) tensor A, n <= 128.
+        Returns (r, c, rowcnd, colcnd, amax, info): float64 (batch, n) and (batch,) device tensors and int32 info -- 0, i + 1 for the
+        first zero row, n + j + 1 for the first zero scaled column, 2 n + 1 for a NaN or Inf in the matrix (what the contract leaves
+        unset stays zero here)."""
+        return self._geequ_batched(A, "geequ_batched")
+
+    def _geequ_batched(self, A, entry):
+        self._bind()
+        t = self.torch
+        assert A.dim() == 3 and A.shape[1] == A.shape[2], "A: (batch, n, n)"
+        batch, n = A.shape[0], A.shape[1]
+        Am, lda, sa = self._batch_arg(A, entry, False, copy=False)
+        r, c = (t.zeros((batch, n), dtype=t.float64, device=self.device) for _ in range(2))
+        rowcnd, colcnd, amax = (t.zeros(batch, dtype=t.float64, device=self.device) for _ in range(3))
+        info = t.zeros(batch, dtype=t.int32, device=self.device)
+        rc = getattr(self.L, "mpf_" + entry)(self.h, _ptr(Am), lda, sa, n, batch, _ptr(r), _ptr(c), _ptr(rowcnd), _ptr(colcnd), _ptr(amax),
+                                             _ptr(info))
+        self._check(rc, "mpf_" + entry)
+        return r, c, rowcnd, colcnd, amax, info
+
+    def laqge_batched(self, A, r, c, rowcnd, colcnd, amax, info, rule=1, overwrite=False):
+        """mpf_laqge_batched: As[b] = Dr A[b] Dc with geequ_batched's results, by rule 0 (never), 1 (dlaqge's rule as mpf_gesvx
+        states it) or 2 (always both), decided per matrix on the device; a matrix with info != 0 is never scaled.  Returns (As,
+        equed, spread): a column-major batch (A itself with overwrite=True), int32 (batch,) with 0 none / 1 rows / 2 columns / 3
+        both, and float64 (batch, 2) with max r / min r and max c / min c of the sides that were scaled (1 otherwise).  Without
+        overwrite As is a new tensor of A's column-major layout (a packed one when A's had to be copied), formed out of place."""
+        return self._laqge_batched(A, r, c, rowcnd, colcnd, amax, info, rule, overwrite, "laqge_batched")
+
+    def _laqge_batched(self, A, r, c, rowcnd, colcnd, amax, info, rule, overwrite, entry):
+        self._bind()
+        t = self.torch
+        assert A.dim() == 3 and A.shape[1] == A.shape[2], "A: (batch, n, n)"
+        batch, n = A.shape[0], A.shape[1]
+        Am, lda, sa = self._batch_arg(A, entry, overwrite, copy=False)
+        As = Am if overwrite else t.empty_strided(Am.shape, Am.stride(), dtype=t.float64, device=self.device)
+        for v, shape in ((r, (batch, n)), (c, (batch, n)), (rowcnd, (batch,)), (colcnd, (batch,)), (amax, (batch,))):
+            assert v.dtype == t.float64 and v.is_cuda and v.shape == shape and v.is_contiguous()
+        assert info.dtype == t.int32 and info.is_cuda and info.shape == (batch,) and info.is_contiguous()
+        equed = t.zeros(batch, dtype=t.int32, device=self.device)
+        spread = t.ones((batch, 2), dtype=t.float64, device=self.device)
+        rc = getattr(self.L, "mpf_" + entry)(self.h, int(rule), _ptr(Am), lda, sa, n, batch, _ptr(r), _ptr(c), _ptr(rowcnd), _ptr(colcnd),
+                                             _ptr(amax), _ptr(info), _ptr(As), _ptr(equed), _ptr(spread))
+        self._check(rc, "mpf_" + entry)
+        return As, equed, spread
+
+    def lascl2_batched(self, s, V, equed=None, bit=0, overwrite=False):
+        """mpf_lascl2_batched: V[b] = diag(s[b]) V[b] for the matrices with equed[b] & bit (all of them when equed is None); V is
+        (batch, n, nrhs) or (batch, n), s float64 (batch, n).  Returns a new column-major tensor, or V itself with overwrite=True."""
+        return self._lascl2_batched(s, V, equed, bit, overwrite, "lascl2_batched")
+
+    def _lascl2_batched(self, s, V, equed, bit, overwrite, entry):
+        self._bind()
+        t = self.torch
+        if V.dim() == 2:
+            return self._lascl2_batched(s, V.unsqueeze(2), equed, bit, overwrite, entry).squeeze(2)
+        assert V.dim() == 3 and s.dtype == t.float64 and s.is_cuda and s.shape == V.shape[:2] and s.is_contiguous(), "s: (batch, n), V: (batch, n, nrhs)"
+        batch, n, nrhs = V.shape
+        Vm, ldv, sv = self._batch_arg(V, entry, overwrite)
+        if equed is not None:
+            assert equed.dtype == t.int32 and equed.is_cuda and equed.shape == (batch,) and equed.is_contiguous()
+        rc = getattr(self.L, "mpf_" + entry)(self.h, _ptr(s), n, batch, nrhs, _ptr(Vm), ldv, sv, _ptr(equed) if equed is not None else None,
+                                             int(bit))
+        self._check(rc, "mpf_" + entry)
+        return Vm
+
+    def gesvx_batched(self, A, B, trans=False, itmax=0, equilibrate=1):
+        """dgesvx for a batch, n <= 128, composed of the batched entries in dgesvx's order: geequ_batched, laqge_batched into a copy
+        (equilibrate: its rule -- 0 never, 1 dlaqge's, 2 always), getrf_batched, lange_batched / gecon_batched of the equilibrated
+        matrix, lascl2_batched on a copy of B, getrs_batched, gerfs_batched on the equilibrated system, lascl2_batched on X, and ferr
+        times the spread of the scaling on X's side.  Returns (X, rcond, ferr, berr, info, equed, r, c), all on the device; rcond and
+        info are the equilibrated matrix's; never raises on a singular or flagged matrix.  equilibrate=0: solvex_batched's bits."""
+        return self._gesvx_batched(A, B, trans, itmax, equilibrate, "")
+
+    def _gesvx_batched(self, A, B, trans, itmax, equilibrate, suffix):
+        f = lambda name: getattr(self, name + "_batched" + suffix)   # noqa: E731
+        norm = "I" if trans else "1"
+        r, c, rowcnd, colcnd, amax, einfo = f("geequ")(A)
+        As, equed, spread = f("laqge")(A, r, c, rowcnd, colcnd, amax, einfo, rule=equilibrate)
+        LU, ipiv, info = f("getrf")(As)
+        rcond = f("gecon")(LU, f("lange")(As, norm), norm)
+        Bs = f("lascl2")(c if trans else r, B, equed, 2 if trans else 1)
+        X = f("getrs")(LU, ipiv, Bs, trans=trans)
+        X, ferr, berr, _ = f("gerfs")(As, LU, ipiv, Bs, X, trans=trans, itmax=itmax, overwrite=True)
+        X = f("lascl2")(r if trans else c, X, equed, 1 if trans else 2, overwrite=True)
+        ferr = ferr * spread[:, 0 if trans else 1].unsqueeze(1)
+        return X, rcond, ferr, berr, info, equed, r, c
+
+    def geequ_batched_blocked(self, A):
+        """mpf_geequ_batched_blocked: geequ_batched for n <= 1024 -- the same arguments, results and bits (a matrix spread over
+        several workgroups, four launches)."""
+        return self._geequ_batched(A, "geequ_batched_blocked")
+
+    def laqge_batched_blocked(self, A, r, c, rowcnd, colcnd, amax, info, rule=1, overwrite=False):
+        """mpf_laqge_batched_blocked: laqge_batched for n <= 1024."""
+        return self._laqge_batched(A, r, c, rowcnd, colcnd, amax, info, rule, overwrite, "laqge_batched_blocked")
+
+    def lascl2_batched_blocked(self, s, V, equed=None, bit=0, overwrite=False):
+        """mpf_lascl2_batched_blocked: lascl2_batched for n <= 1024."""
+        return self._lascl2_batched(s, V, equed, bit, overwrite, "lascl2_batched_blocked")
+
+    def gesvx_batched_blocked(self, A, B, trans=False, itmax=0, equilibrate=1):
+        """gesvx_batched for n <= 1024 from the blocked entries; equilibrate=0: solvex_batched_blocked's bits."""
+        return self._gesvx_batched(A, B, trans, itmax, equilibrate, "_blocked")
 
     # ---- the same for matrices of different orders (include/mpf_c.h: mpf_vbatch_create, mpf_getrf_vbatched, ...) --------------------------
     def vbatch(self, n, ld=None, off=None):
@@ -1691,7 +1809,7 @@ class VBatch:
         return self.gecon(LU, self.lange(A, norm), norm)
 
     def solvex(self, A, B, trans=False, itmax=0):
-        """dgesvx's shape without equilibration for the whole descriptor: getrf on a copy, lange / gecon (the '1' norm, or 'I' with
+        """dgesvx's shape without equilibration (VBatch.gesvx adds it) for the whole descriptor: getrf on a copy, lange / gecon (the '1' norm, or 'I' with
         trans), getrs, gerfs.  Returns (X, rcond, ferr, berr, info), all on the device; never raises on a singular matrix: info[b] is
         its first zero pivot and rcond[b] is 0 (its X, ferr and berr are not meaningful)."""
         norm = "I" if trans else "1"
@@ -1700,3 +1818,70 @@ class VBatch:
         X = self.getrs(LU, ipiv, B, trans=trans)
         X, ferr, berr, _ = self.gerfs(A, LU, ipiv, B, X, trans=trans, itmax=itmax, overwrite=True)
         return X, rcond, ferr, berr, info
+
+    # ---- equilibration (include/mpf_c.h: mpf_geequ_vbatched, mpf_laqge_vbatched, mpf_lascl2_vbatched) ------------------------------------------
+    def _vec(self, s, what):
+        t = self.ctx.torch
+        assert s.dim() == 1 and s.dtype == t.float64 and s.is_cuda and s.is_contiguous() and s.numel() >= self.total_n, \
+            f"{what}: a float64 device tensor of total_n = {self.total_n} elements"
+        return s
+
+    def geequ(self, A):
+        """mpf_geequ_vbatched: (r, c, rowcnd, colcnd, amax, info) of every matrix of the flat tensor A -- r and c float64 (total_n,),
+        matrix b's at offv[b]; the others (batch,).  A matrix of order 0 gives rowcnd = colcnd = 1, amax = 0, info = 0."""
+        ctx, t = self.ctx, self.ctx.torch
+        ctx._bind()
+        r, c = (t.zeros(max(self.total_n, 1), dtype=t.float64, device=ctx.device) for _ in range(2))
+        rowcnd, colcnd, amax = (t.zeros(self.batch, dtype=t.float64, device=ctx.device) for _ in range(3))
+        info = self._info(None)
+        rc = ctx.L.mpf_geequ_vbatched(ctx.h, self.h, _ptr(self._flat(A, "geequ")), _ptr(r), _ptr(c), _ptr(rowcnd), _ptr(colcnd), _ptr(amax),
+                                      _ptr(info))
+        ctx._check(rc, "mpf_geequ_vbatched")
+        return r[:self.total_n], c[:self.total_n], rowcnd, colcnd, amax, info
+
+    def laqge(self, A, r, c, rowcnd, colcnd, amax, info, rule=1, overwrite=False):
+        """mpf_laqge_vbatched: (As, equed, spread) as MPFContext.laqge_batched returns them, As flat in this layout (A itself with
+        overwrite=True, else a new tensor formed out of place, zero between the matrices)."""
+        ctx, t = self.ctx, self.ctx.torch
+        ctx._bind()
+        Am = self._flat(A, "laqge")
+        As = Am if overwrite else t.zeros_like(Am)
+        equed = t.zeros(self.batch, dtype=t.int32, device=ctx.device)
+        spread = t.ones((self.batch, 2), dtype=t.float64, device=ctx.device)
+        for v in (rowcnd, colcnd, amax):
+            assert v.dtype == t.float64 and v.is_cuda and v.shape == (self.batch,) and v.is_contiguous()
+        rc = ctx.L.mpf_laqge_vbatched(ctx.h, self.h, int(rule), _ptr(Am), _ptr(self._vec(r, "laqge r")), _ptr(self._vec(c, "laqge c")),
+                                      _ptr(rowcnd), _ptr(colcnd), _ptr(amax), _ptr(self._info(info)), _ptr(As), _ptr(equed), _ptr(spread))
+        ctx._check(rc, "mpf_laqge_vbatched")
+        return As, equed, spread
+
+    def lascl2(self, s, V, equed=None, bit=0, overwrite=False):
+        """mpf_lascl2_vbatched: V = diag(s) V on the rows of the matrices with equed[b] & bit (all when equed is None); V is
+        (total_n,) or a (total_n, nrhs) tensor, s float64 (total_n,).  Returns a new column-major tensor, or V itself with overwrite."""
+        ctx, t = self.ctx, self.ctx.torch
+        ctx._bind()
+        if V.dim() == 1:
+            assert V.is_contiguous()
+            return self.lascl2(s, V.unsqueeze(1), equed, bit, overwrite).squeeze(1)
+        Vm, ldv = self._tall(V, "lascl2 V", overwrite)
+        if equed is not None:
+            assert equed.dtype == t.int32 and equed.is_cuda and equed.shape == (self.batch,) and equed.is_contiguous()
+        rc = ctx.L.mpf_lascl2_vbatched(ctx.h, self.h, _ptr(self._vec(s, "lascl2 s")), Vm.shape[1], _ptr(Vm), ldv,
+                                       _ptr(equed) if equed is not None else None, int(bit))
+        ctx._check(rc, "mpf_lascl2_vbatched")
+        return Vm
+
+    def gesvx(self, A, B, trans=False, itmax=0, equilibrate=1):
+        """MPFContext.gesvx_batched for the whole descriptor: (X, rcond, ferr, berr, info, equed, r, c), all on the device;
+        equilibrate=0: solvex's bits."""
+        norm = "I" if trans else "1"
+        r, c, rowcnd, colcnd, amax, einfo = self.geequ(A)
+        As, equed, spread = self.laqge(A, r, c, rowcnd, colcnd, amax, einfo, rule=equilibrate)
+        LU, ipiv, info = self.getrf(As)
+        rcond = self.gecon(LU, self.lange(As, norm), norm)
+        Bs = self.lascl2(c if trans else r, B, equed, 2 if trans else 1)
+        X = self.getrs(LU, ipiv, Bs, trans=trans)
+        X, ferr, berr, _ = self.gerfs(As, LU, ipiv, Bs, X, trans=trans, itmax=itmax, overwrite=True)
+        X = self.lascl2(r if trans else c, X, equed, 1 if trans else 2, overwrite=True)
+        ferr = ferr * spread[:, 0 if trans else 1].unsqueeze(1)
+        return X, rcond, ferr, berr, info, equed, r, c

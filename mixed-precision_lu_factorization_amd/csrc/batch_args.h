@@ -57,6 +57,12 @@ inline int64_t residual_step(int64_t max_units, int64_t max_launch, int32_t nrhs
     const int64_t step = max_units / nrhs;
     return step > max_launch ? max_launch : step;
 }
+// the elementwise kernels of the equilibration (one thread per element, 32-bit element numbers): as many matrices of `per` >= 1
+// elements each as stay below 2^31 elements and within max_launch matrices, at least one (the caller keeps per < 2^31)
+inline int64_t elements_step(int64_t max_launch, int64_t per) {
+    const int64_t fit = (((int64_t)1 << 31) - 1) / per;
+    return fit < 1 ? 1 : (fit < max_launch ? fit : max_launch);
+}
 // the blocked refinement with the bound: also as many matrices as keep a chunk's workspace (n + 1 doubles per column, one per column
 // and tile of 16 chains) within 256 MB, at least one; a matrix's results do not depend on the chunk
 inline int64_t ferr_step(int64_t max_launch, int32_t n, int32_t nrhs) {

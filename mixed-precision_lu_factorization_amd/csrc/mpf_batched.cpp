@@ -414,6 +414,127 @@ int mpf_gerfs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_A, int6
 
 } // extern "C"
 
+// ---- equilibration of the strided batches (kernels in batched_equil.hip) ------------------------------------------------------------------
+// One body per operator for the small and the blocked entry: the limit, the name and whether the call takes the small kernels differ.
+namespace {
+const char *const ONE_GEEQU = "equilibrate it with mpf_geequ (or mpf_gesvx) and factor it with mpf_factor_dev";
+
+int geequ_strided(mpf_ctx *c, const char *who, int32_t limit, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                  double *d_r, double *d_c, double *d_rowcnd, double *d_colcnd, double *d_amax, int32_t *d_info) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, ONE_GEEQU);
+    if (rc) return rc;
+    if (n == 0 || batch == 0) return 0;
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
+    if (rc) return rc;
+    if (!d_A || !d_r || !d_c || !d_rowcnd || !d_colcnd || !d_amax || !d_info) { c->err = std::string(who) + ": null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    if (limit == ba::SMALL_MAXN || forwards_to_small(c, n))
+        return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+            return launch_geequ_batched(c, d_A + b0 * strideA, lda, strideA, n, nb, d_r + b0 * n, d_c + b0 * n, d_rowcnd + b0, d_colcnd + b0,
+                                        d_amax + b0, d_info + b0);
+        });
+    const int64_t step = batch < BB_MAX_LAUNCH ? batch : BB_MAX_LAUNCH;
+    MPF_HIP_TRY(c, c->rb_g.grow(step * n));                         // (once, before the first launch that uses them)
+    MPF_HIP_TRY(c, c->rb_part.grow(step * n));
+    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_geequ_batched_blocked(c, d_A + b0 * strideA, lda, strideA, n, nb, d_r + b0 * n, d_c + b0 * n, d_rowcnd + b0,
+                                            d_colcnd + b0, d_amax + b0, d_info + b0, c->rb_g.get(), c->rb_part.get());
+    });
+}
+
+int laqge_strided(mpf_ctx *c, const char *who, int32_t limit, int32_t rule, const double *d_A, int64_t lda, int64_t strideA, int32_t n,
+                  int64_t batch, const double *d_r, const double *d_c, const double *d_rowcnd, const double *d_colcnd, const double *d_amax,
+                  const int32_t *d_info, double *d_out, int32_t *d_equed, double *d_spread) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, ONE_GEEQU);
+    if (rc) return rc;
+    if (rule < 0 || rule > 2) { c->err = std::string(who) + ": rule must be 0, 1 or 2"; return -1; }
+    if (n == 0 || batch == 0) return 0;
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
+    if (rc) return rc;
+    if (!d_A || !d_r || !d_c || !d_rowcnd || !d_colcnd || !d_amax || !d_info || !d_out || !d_equed) { c->err = std::string(who) + ": null pointer"; return -1; }
+    const int64_t ext = ba::extent(n, batch, lda, strideA);
+    if (d_out != d_A && ba::ranges_overlap((uintptr_t)d_A, ext, (uintptr_t)d_out, ext)) {
+        c->err = std::string(who) + ": d_out overlaps d_A (in place is d_out == d_A)";
+        return -1;
+    }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    rc = ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_laqge_decide(c, rule, n, nb, nullptr, nullptr, d_r + b0 * n, d_c + b0 * n, d_rowcnd + b0, d_colcnd + b0, d_amax + b0,
+                                   d_info + b0, d_equed + b0, opt(d_spread, 2 * b0));
+    });
+    if (rc) return rc;
+    if (limit == ba::SMALL_MAXN || forwards_to_small(c, n))
+        return ba::chunks(batch, ba::elements_step(BT_MAX_LAUNCH, (int64_t)n * n), [&](int64_t b0, int64_t nb) {
+            return launch_laqge_batched(c, d_A + b0 * strideA, lda, strideA, n, nb, d_r + b0 * n, d_c + b0 * n, d_equed + b0, d_out + b0 * strideA);
+        });
+    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch_laqge_batched_blocked(c, d_A + b0 * strideA, lda, strideA, n, nb, d_r + b0 * n, d_c + b0 * n, d_equed + b0,
+                                            d_out + b0 * strideA);
+    });
+}
+
+// elementwise whatever n: one kernel for both entries
+int lascl2_strided(mpf_ctx *c, const char *who, int32_t limit, const double *d_s, int32_t n, int64_t batch, int32_t nrhs, double *d_V,
+                   int64_t ldv, int64_t strideV, const int32_t *d_equed, int32_t bit) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, ONE_GEEQU);
+    if (rc) return rc;
+    if (nrhs < 0) { c->err = std::string(who) + ": nrhs must not be negative"; return -1; }
+    if (n == 0 || batch == 0 || nrhs == 0) return 0;
+    rc = ba::check_strided(c->err, who, "V", ldv, strideV, n, nrhs, batch);
+    if (rc) return rc;
+    if (!d_s || !d_V) { c->err = std::string(who) + ": null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const int32_t kc = (int32_t)ba::elements_step(nrhs, n);        // columns per launch: n kc < 2^31
+    for (int32_t k0 = 0; k0 < nrhs; k0 += kc) {
+        const int32_t nk = nrhs - k0 < kc ? nrhs - k0 : kc;
+        rc = ba::chunks(batch, ba::elements_step(BT_MAX_LAUNCH, (int64_t)n * nk), [&](int64_t b0, int64_t nb) {
+            return launch_lascl2_batched(c, d_s + b0 * n, n, nb, nk, d_V + b0 * strideV + (int64_t)k0 * ldv, ldv, strideV, opt(d_equed, b0), bit);
+        });
+        if (rc) return rc;
+    }
+    return 0;
+}
+} // namespace
+
+extern "C" {
+
+int mpf_geequ_batched(mpf_ctx *c, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_r, double *d_c,
+                      double *d_rowcnd, double *d_colcnd, double *d_amax, int32_t *d_info) {
+    if (!c) return -1;
+    return geequ_strided(c, "geequ_batched", ba::SMALL_MAXN, d_A, lda, strideA, n, batch, d_r, d_c, d_rowcnd, d_colcnd, d_amax, d_info);
+}
+int mpf_geequ_batched_blocked(mpf_ctx *c, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_r, double *d_c,
+                              double *d_rowcnd, double *d_colcnd, double *d_amax, int32_t *d_info) {
+    if (!c) return -1;
+    return geequ_strided(c, "geequ_batched_blocked", ba::BLOCKED_MAXN, d_A, lda, strideA, n, batch, d_r, d_c, d_rowcnd, d_colcnd, d_amax, d_info);
+}
+int mpf_laqge_batched(mpf_ctx *c, int32_t rule, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, const double *d_r,
+                      const double *d_c, const double *d_rowcnd, const double *d_colcnd, const double *d_amax, const int32_t *d_info,
+                      double *d_out, int32_t *d_equed, double *d_spread) {
+    if (!c) return -1;
+    return laqge_strided(c, "laqge_batched", ba::SMALL_MAXN, rule, d_A, lda, strideA, n, batch, d_r, d_c, d_rowcnd, d_colcnd, d_amax, d_info,
+                         d_out, d_equed, d_spread);
+}
+int mpf_laqge_batched_blocked(mpf_ctx *c, int32_t rule, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                              const double *d_r, const double *d_c, const double *d_rowcnd, const double *d_colcnd, const double *d_amax,
+                              const int32_t *d_info, double *d_out, int32_t *d_equed, double *d_spread) {
+    if (!c) return -1;
+    return laqge_strided(c, "laqge_batched_blocked", ba::BLOCKED_MAXN, rule, d_A, lda, strideA, n, batch, d_r, d_c, d_rowcnd, d_colcnd, d_amax,
+                         d_info, d_out, d_equed, d_spread);
+}
+int mpf_lascl2_batched(mpf_ctx *c, const double *d_s, int32_t n, int64_t batch, int32_t nrhs, double *d_V, int64_t ldv, int64_t strideV,
+                       const int32_t *d_equed, int32_t bit) {
+    if (!c) return -1;
+    return lascl2_strided(c, "lascl2_batched", ba::SMALL_MAXN, d_s, n, batch, nrhs, d_V, ldv, strideV, d_equed, bit);
+}
+int mpf_lascl2_batched_blocked(mpf_ctx *c, const double *d_s, int32_t n, int64_t batch, int32_t nrhs, double *d_V, int64_t ldv, int64_t strideV,
+                               const int32_t *d_equed, int32_t bit) {
+    if (!c) return -1;
+    return lascl2_strided(c, "lascl2_batched_blocked", ba::BLOCKED_MAXN, d_s, n, batch, nrhs, d_V, ldv, strideV, d_equed, bit);
+}
+
+} // extern "C"
+
 // ---- variable sizes -------------------------------------------------------------------------------------------------------------------
 namespace {
 // both creators: the plan with the limit and forwarding threshold in force, then the upload
@@ -764,6 +885,86 @@ int mpf_gerfs_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const do
                                    ldb, d_X, ldx, it, d_ferr, d_berr, d_iters);
         if (rc) return rc;
     }
+    return 0;
+}
+
+// ---- equilibration on a descriptor of either kind (kernels in batched_equil.hip) ------------------------------------------------------------
+// Every matrix of order >= 1 takes the ragged kernels, launch group by launch group of the whole ordered list (refine_chunks), the
+// maxima of a chunk in the context's workspace by list position; the decision of laqge runs over the whole list, orders 0 included.
+int mpf_geequ_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_A, double *d_r, double *d_c, double *d_rowcnd, double *d_colcnd,
+                       double *d_amax, int32_t *d_info) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "geequ_vbatched");
+    if (rc) return rc;
+    if (vb->plan.batch == 0) return 0;
+    if (!d_rowcnd || !d_colcnd || !d_amax || !d_info || (vb->plan.total_n > 0 && (!d_A || !d_r || !d_c))) { c->err = "geequ_vbatched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    for (int64_t i0 = 0; i0 < vb->plan.zeros; i0 += BT_MAX_LAUNCH) {
+        const int64_t nb = vb->plan.zeros - i0 < BT_MAX_LAUNCH ? vb->plan.zeros - i0 : BT_MAX_LAUNCH;
+        rc = launch_geequ_vbatched_empty(c, vb->d_list.get() + i0, nb, d_rowcnd, d_colcnd, d_amax, d_info);
+        if (rc) return rc;
+    }
+    RbvNeed need;
+    const std::vector<vbatch::Chunk> chunks = vb_refine_chunks(vb, 0, 0, &need);
+    MPF_HIP_TRY(c, c->rb_g.grow(need.rows));                        // (once, before the first launch that uses them)
+    MPF_HIP_TRY(c, c->rb_part.grow(need.rows));
+    const BtRagged v = vb_arrays(vb);
+    for (const vbatch::Chunk &k : chunks) {
+        rc = launch_geequ_vbatched(c, v, vb->d_list.get() + k.first, vb->d_lrow.get() + k.first, vb->plan.lrow[(size_t)k.first], k.count, k.nmax, d_A,
+                                   d_r, d_c, d_rowcnd, d_colcnd, d_amax, d_info, c->rb_g.get(), c->rb_part.get());
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_laqge_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t rule, const double *d_A, const double *d_r, const double *d_c,
+                       const double *d_rowcnd, const double *d_colcnd, const double *d_amax, const int32_t *d_info, double *d_out,
+                       int32_t *d_equed, double *d_spread) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "laqge_vbatched");
+    if (rc) return rc;
+    if (rule < 0 || rule > 2) { c->err = "laqge_vbatched: rule must be 0, 1 or 2"; return -1; }
+    if (vb->plan.batch == 0) return 0;
+    if (!d_rowcnd || !d_colcnd || !d_amax || !d_info || !d_equed || (vb->plan.total_n > 0 && (!d_A || !d_r || !d_c || !d_out))) {
+        c->err = "laqge_vbatched: null pointer";
+        return -1;
+    }
+    if (vb->plan.total_n > 0 && d_out != d_A && ba::ranges_overlap((uintptr_t)d_A, vb->plan.extent, (uintptr_t)d_out, vb->plan.extent)) {
+        c->err = "laqge_vbatched: d_out overlaps d_A (in place is d_out == d_A)";
+        return -1;
+    }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const BtRagged v = vb_arrays(vb);
+    for (int64_t i0 = 0; i0 < vb->plan.batch; i0 += BT_MAX_LAUNCH) {
+        const int64_t nb = vb->plan.batch - i0 < BT_MAX_LAUNCH ? vb->plan.batch - i0 : BT_MAX_LAUNCH;
+        rc = launch_laqge_decide(c, rule, 0, nb, vb->d_list.get() + i0, &v, d_r, d_c, d_rowcnd, d_colcnd, d_amax, d_info, d_equed, d_spread);
+        if (rc) return rc;
+    }
+    for (const vbatch::Chunk &k : vb_refine_chunks(vb, 0, 0, nullptr)) {
+        rc = launch_laqge_vbatched(c, v, vb->d_list.get() + k.first, k.count, k.nmax, d_A, d_r, d_c, d_equed, d_out);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpf_lascl2_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_s, int32_t nrhs, double *d_V, int64_t ldv, const int32_t *d_equed,
+                        int32_t bit) {
+    if (!c) return -1;
+    int rc = vb_enter(c, vb, "lascl2_vbatched");
+    if (rc) return rc;
+    if (nrhs < 0) { c->err = "lascl2_vbatched: nrhs must not be negative"; return -1; }
+    if (vb->plan.batch == 0 || vb->plan.total_n == 0 || nrhs == 0) return 0;
+    if (ldv < vb->plan.total_n) { c->err = "lascl2_vbatched: leading dimension of V < total_n"; return -1; }
+    if (!d_s || !d_V) { c->err = "lascl2_vbatched: null pointer"; return -1; }
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    const BtRagged v = vb_arrays(vb);
+    constexpr int32_t KC = 1 << 16;                                 // columns per launch (a grid dimension of four columns each)
+    for (int32_t k0 = 0; k0 < nrhs; k0 += KC)
+        for (const vbatch::Chunk &k : vb_refine_chunks(vb, 0, 0, nullptr)) {
+            rc = launch_lascl2_vbatched(c, v, vb->d_list.get() + k.first, k.count, k.nmax, d_s, nrhs - k0 < KC ? nrhs - k0 : KC,
+                                        d_V + (int64_t)k0 * ldv, ldv, d_equed, bit);
+            if (rc) return rc;
+        }
     return 0;
 }
 

@@ -637,6 +637,31 @@ int launch_gerfs_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, con
                           double *ferr, double *berr, int *iters);
 int launch_refine_vbatched_empty(mpf_ctx *c, const int32_t *idx, int64_t count, int nrhs, double *norm, double *rcond, double *ainvnm,
                                  double *berr, double *ferr, int *iters);
+// Equilibration of those batches (batched_equil.hip; checks and chunks in mpf_batched.cpp).  launch_geequ_batched: 1 <= n <= 128, at most
+// BT_MAX_LAUNCH matrices, A read once.  launch_geequ_batched_blocked / launch_geequ_vbatched: any order up to 1024, at most BB_MAX_LAUNCH
+// matrices or list entries (every order >= 1), four launches; rk, ck: one double-sized word per row of the launch each (ragged: entry i's
+// at row[i] - row0, the descriptor's prefix sums as in RbvWork).  launch_laqge_decide: equed and, when not null, spread of `count` matrices
+// (idx null: matrices 0 .. count-1 of order n; else list entries of any order, v the descriptor's arrays).  launch_laqge_batched and
+// launch_lascl2_batched: one thread per element, fewer than 2^31 elements per call.  out may be A itself.
+int launch_geequ_batched(mpf_ctx *c, const double *A, int64_t lda, int64_t stride, int n, int64_t batch, double *r, double *cs, double *rowcnd,
+                         double *colcnd, double *amax, int *info);
+int launch_geequ_batched_blocked(mpf_ctx *c, const double *A, int64_t lda, int64_t stride, int n, int64_t batch, double *r, double *cs,
+                                 double *rowcnd, double *colcnd, double *amax, int *info, double *rk, double *ck);
+int launch_geequ_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, const int64_t *row, int64_t row0, int64_t count, int nmax,
+                          const double *A, double *r, double *cs, double *rowcnd, double *colcnd, double *amax, int *info, double *rk, double *ck);
+int launch_geequ_vbatched_empty(mpf_ctx *c, const int32_t *idx, int64_t count, double *rowcnd, double *colcnd, double *amax, int *info);
+int launch_laqge_decide(mpf_ctx *c, int rule, int n, int64_t count, const int32_t *idx, const BtRagged *v, const double *r, const double *cs,
+                        const double *rowcnd, const double *colcnd, const double *amax, const int *info, int *equed, double *spread);
+int launch_laqge_batched(mpf_ctx *c, const double *A, int64_t lda, int64_t stride, int n, int64_t batch, const double *r, const double *cs,
+                         const int *equed, double *out);
+int launch_laqge_batched_blocked(mpf_ctx *c, const double *A, int64_t lda, int64_t stride, int n, int64_t batch, const double *r, const double *cs,
+                                 const int *equed, double *out);
+int launch_laqge_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int nmax, const double *A, const double *r,
+                          const double *cs, const int *equed, double *out);
+int launch_lascl2_batched(mpf_ctx *c, const double *s, int n, int64_t batch, int nrhs, double *V, int64_t ldv, int64_t stride, const int *equed,
+                          int bit);
+int launch_lascl2_vbatched(mpf_ctx *c, const BtRagged &v, const int32_t *idx, int64_t count, int nmax, const double *s, int nrhs, double *V,
+                           int64_t ldv, const int *equed, int bit);
 // mpf_block.cpp: the body of mpf_solve_gmres_ir_block, as the cores above (no scales); restart and max_outer clamped (gmres_clamp)
 int blk_gmres_core(const BlkSys &s, const BlkRhs &r, int32_t max_outer, int32_t restart, double tol, mpf_gmres_stats *st);
 
