@@ -1,25 +1,20 @@
-// LU of many small matrices (no reference counterpart; LAPACK dgetrf / dgetrs per matrix of a strided batch):
-//   mpf_getrf_batched   mpf_dgetf2_piv's pivots and bits for every n x n matrix of the batch, n <= 128
-//   mpf_getrs_batched   dgetrs with those factors, in place on the right-hand sides
-//   mpf_getri_batched   the inverse from those factors, out of place: the solve's bits on an identity that is never formed
-//   mpf_getdet_batched  the determinant from those factors as mant 2^expo, mpf_getdet's order per matrix
-//   mpf_lange_batched, mpf_gecon_batched, mpf_residual_batched, mpf_gerfs_batched   the expert layer on those batches: a norm and an
-//                       exact reciprocal condition number per matrix, the residual step operator, dgerfs's refinement with berr and
-//                       an exact ferr per matrix and column (kernels in batched_refine.hip)
-// The argument checks, the chunks of a batch longer than one grid and the error text (the rules themselves: batch_args.h); kernels and
-// form choice in batched.hip; the contracts are in include/mpf_c.h.
-//   mpf_getrf_batched_blocked, mpf_getrs_batched_blocked   the first two for one n <= 1024: the same bits from a right-looking blocked
-//                       loop (batched_blocked.hip), three launches per panel step for the whole batch
-//   mpf_getri_batched_blocked, mpf_getdet_batched_blocked   the other two for one n <= 1024: one launch each, no workspace
-//   mpf_lange_batched_blocked, mpf_gecon_batched_blocked, mpf_residual_batched_blocked, mpf_gerfs_batched_blocked   the expert layer for
-//                       one n <= 1024 (batched_refine_blocked.hip): the small layer's arguments, rules and, for n <= 128, bits
-// The same four for matrices of different orders (mpf_*_vbatched) on a descriptor, mpf_vbatch: the host plan of vbatch_plan.h (checks,
-// prefix sums, size classes) uploaded once; each call then launches one ragged kernel of vbatched.hip per class that is not empty.
-// A descriptor from mpf_vbatch_create_blocked (orders up to 1024) also has the plan's large list: its matrices take the ragged blocked
-// kernels of vbatched_blocked.hip, launch group by launch group, the factorization panel step by panel step over the active suffix.
-//   mpf_lange_vbatched, mpf_gecon_vbatched, mpf_residual_vbatched, mpf_gerfs_vbatched   the expert layer on a descriptor of either kind:
-//                       every matrix of order >= 1 takes the ragged blocked expert kernels of vbatched_refine.hip, launch group by
-//                       launch group of the whole ordered list (vbatch_plan.h: refine_chunks)
+// The host side of the batched layer (no reference counterpart; LAPACK per matrix of a batch; contracts in include/mpf_c.h).
+// Strided batches, one order per call: every operator has ONE host body, <operator>_strided, for its two entries mpf_<operator>_batched
+// (n <= 128; batched.hip, batched_refine.hip) and mpf_<operator>_batched_blocked (n <= 1024; batched_blocked.hip,
+// batched_refine_blocked.hip; equilibration for both: batched_equil.hip).  An entry is a !c test and one call that passes its name, its
+// family's limit and the text that says where a larger matrix goes (the three equilibration bodies take no such text: their six entries
+// share ONE_GEEQU).  A body reads: the checks in the contract's order (sizes, pivot stride, nrhs / trans / norm, `return 0` on the empty
+// cases, strided operands, null pointers, getri's out-of-place test; rules and texts are batch_args.h's), hipSetDevice, then one launch
+// per chunk -- the small launcher and chunk step for a small entry and for a blocked one below option batched_blocked_min_n (the same
+// bits by contract), the blocked ones otherwise.  Operators: getrf, getrs, getri, getdet; the expert layer lange, gecon, residual, gerfs;
+// the equilibration geequ, laqge, lascl2.
+// Matrices of different orders (mpf_*_vbatched) on a descriptor, mpf_vbatch: the host plan of vbatch_plan.h uploaded once.  Three walks
+// over three different lists stay apart, each cut with batch_args::chunks: vb_classes (orders <= 128 of the factor, solve, inverse and
+// determinant entries: one ragged kernel of vbatched.hip per class that is not empty), vb_large (a blocked descriptor's large list:
+// vbatched_blocked.hip, launch group by launch group, the factorization panel step by panel step over the active suffix) and
+// vb_refine_chunks (expert layer and equilibration on either kind: every order >= 1, vbatched_refine.hip / batched_equil.hip, launch
+// groups of the whole ordered list; vbatch_plan.h: refine_chunks).  The matrices of order 0 get their outputs from kernels of their own
+// (vb_zeros).
 #include "mpf_internal.h"
 #include "batch_args.h"
 #include "vbatch_plan.h"
@@ -39,386 +34,209 @@ namespace ba = batch_args;
 
 // where check_sizes' message sends a matrix that is too large for the family
 const char *const THEN_GETRS = "factor it with mpf_factor_dev (and solve with mpf_getrs)";
+const char *const THEN_GETRI = "factor it with mpf_factor_dev (and invert with mpf_getri)";
+const char *const THEN_GETDET = "factor it with mpf_factor_dev (and take the determinant with mpf_getdet)";
+const char *const ONE_LANGE = "use mpf_lange (and mpf_gecon / mpf_gerfs) on one matrix at a time";
+const char *const ONE_GECON = "use mpf_gecon (and mpf_gerfs) on one matrix at a time";
+const char *const ONE_GERFS = "use mpf_gerfs (and mpf_gecon) on one matrix at a time";
 const char *const ONE_AT_A_TIME = "use mpf_lange, mpf_gecon / mpf_gerfs on one matrix at a time";
+const char *const ONE_GEEQU = "equilibrate it with mpf_geequ (or mpf_gesvx) and factor it with mpf_factor_dev";
 
 bool forwards_to_small(const mpf_ctx *c, int32_t n) { return ba::forwards_to_small(n, c->tune.batched_blocked_min_n); }
+// whether a body launches the small kernels: every call of a small entry, and a blocked entry's that forwards
+bool takes_small(const mpf_ctx *c, int32_t limit, int32_t n) { return limit == ba::SMALL_MAXN || forwards_to_small(c, n); }
+int null_pointer(mpf_ctx *c, const char *who) { c->err = std::string(who) + ": null pointer"; return -1; }
 // an optional per-matrix output of a chunk
 template <class T>
 T *opt(T *p, int64_t at) { return p ? p + at : nullptr; }
 // getri's rule: the factors are still being read while the result is stored (mpf_getri's rule, on the address ranges of the two batches)
-int check_out_of_place(mpf_ctx *c, const char *who, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
-                       const double *d_inv, int64_t ldinv, int64_t strideInv) {
-    if (!ba::ranges_overlap((uintptr_t)d_LU, ba::extent(n, batch, ldlu, strideLU), (uintptr_t)d_inv, ba::extent(n, batch, ldinv, strideInv))) return 0;
+int check_out_of_place(mpf_ctx *c, const char *who, const double *d_LU, int64_t na, const double *d_inv, int64_t nb) {
+    if (!ba::ranges_overlap((uintptr_t)d_LU, na, (uintptr_t)d_inv, nb)) return 0;
     c->err = std::string(who) + ": d_inv overlaps d_LU (the inverse is formed out of place)";
     return -1;
 }
-} // namespace
-
-// Every entry below reads: the checks in the contract's order, for a blocked entry the forward to the small one, then one launch per
-// chunk of the batch.
-extern "C" {
-
-int mpf_getrf_batched(mpf_ctx *c, double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t *d_ipiv, int64_t strideP,
-                      int32_t *d_info, int32_t fused) {
-    if (!c) return -1;
-    const char *who = "getrf_batched";
-    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, THEN_GETRS);
-    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
-    if (rc) return rc;
-    if (n == 0 || batch == 0) return 0;
-    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
-    if (rc) return rc;
-    if (!d_A || !d_ipiv) { c->err = "getrf_batched: null pointer"; return -1; }
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_getrf_batched(c, d_A + b0 * strideA, lda, strideA, n, nb, d_ipiv + b0 * strideP, strideP, opt(d_info, b0), fused != 0);
-    });
-}
-
-int mpf_getrs_batched(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
-                      const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB) {
-    if (!c) return -1;
-    const char *who = "getrs_batched";
-    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, THEN_GETRS);
-    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
-    if (rc) return rc;
-    if (nrhs < 0) { c->err = "getrs_batched: nrhs must not be negative"; return -1; }
-    if (trans != 0 && trans != 1) { c->err = "getrs_batched: trans must be 0 or 1"; return -1; }
-    if (n == 0 || batch == 0 || nrhs == 0) return 0;
-    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
-    if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
-    if (rc) return rc;
-    if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs_batched: null pointer"; return -1; }
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_getrs_batched(c, trans, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, nrhs,
-                                    d_B + b0 * strideB, ldb, strideB);
-    });
-}
-
-int mpf_getri_batched(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv,
-                      int64_t strideP, double *d_inv, int64_t ldinv, int64_t strideInv, int32_t *d_info) {
-    if (!c) return -1;
-    const char *who = "getri_batched";
-    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, THEN_GETRS);
-    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
-    if (rc) return rc;
-    if (n == 0 || batch == 0) return 0;
-    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
-    if (!rc) rc = ba::check_strided(c->err, who, "inv", ldinv, strideInv, n, n, batch);
-    if (rc) return rc;
-    if (!d_LU || !d_ipiv || !d_inv) { c->err = "getri_batched: null pointer"; return -1; }
-    rc = check_out_of_place(c, who, d_LU, ldlu, strideLU, n, batch, d_inv, ldinv, strideInv);
-    if (rc) return rc;
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_getri_batched(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_inv + b0 * strideInv,
-                                    ldinv, strideInv, opt(d_info, b0));
-    });
-}
-
-int mpf_getdet_batched(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv,
-                       int64_t strideP, double *d_mant, int32_t *d_expo) {
-    if (!c) return -1;
-    const char *who = "getdet_batched";
-    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, THEN_GETRS);
-    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
-    if (rc) return rc;
-    if (n == 0 || batch == 0) return 0;
-    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
-    if (rc) return rc;
-    if (!d_LU || !d_ipiv || !d_mant || !d_expo) { c->err = "getdet_batched: null pointer"; return -1; }
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_getdet_batched(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0, d_expo + b0);
-    });
-}
-
-// ---- the expert layer, n <= 128 (kernels in batched_refine.hip) ---------------------------------------------------------------------------
-int mpf_lange_batched(mpf_ctx *c, char norm, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_out) {
-    if (!c) return -1;
-    const char *who = "lange_batched";
-    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, "use mpf_lange (and mpf_gecon / mpf_gerfs) on one matrix at a time");
-    if (rc) return rc;
-    int mode;
-    if (norm == '1' || norm == 'O' || norm == 'o') mode = 0;
-    else if (norm == 'I' || norm == 'i') mode = 1;
-    else if (norm == 'M' || norm == 'm') mode = 2;
-    else { c->err = "lange_batched: norm must be '1', 'O', 'I' or 'M'"; return -1; }
-    if (n == 0 || batch == 0) return 0;
-    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
-    if (rc) return rc;
-    if (!d_A || !d_out) { c->err = "lange_batched: null pointer"; return -1; }
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_lange_batched(c, mode, d_A + b0 * strideA, lda, strideA, n, nb, d_out + b0);
-    });
-}
-
-int mpf_gecon_batched(mpf_ctx *c, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
-                      const double *d_anorm, double *d_rcond, double *d_ainvnm) {
-    if (!c) return -1;
-    const char *who = "gecon_batched";
-    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, "use mpf_gecon (and mpf_gerfs) on one matrix at a time");
-    if (rc) return rc;
-    const bool one = norm == '1' || norm == 'O' || norm == 'o';
-    if (!one && norm != 'I' && norm != 'i') { c->err = "gecon_batched: norm must be '1', 'O' or 'I'"; return -1; }
-    if (n == 0 || batch == 0) return 0;
-    rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
-    if (rc) return rc;
-    if (!d_LU || !d_anorm || !d_rcond) { c->err = "gecon_batched: null pointer"; return -1; }
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_gecon_batched(c, one ? 0 : 1, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_anorm + b0, d_rcond + b0, opt(d_ainvnm, b0));
-    });
-}
-
-int mpf_residual_batched(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t nrhs,
-                         const double *d_X, int64_t ldx, int64_t strideX, const double *d_B, int64_t ldb, int64_t strideB, double *d_R,
-                         int64_t ldr, int64_t strideR, double *d_W) {
-    if (!c) return -1;
-    const char *who = "residual_batched";
-    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, "use mpf_gerfs (and mpf_gecon) on one matrix at a time");
-    if (rc) return rc;
-    if (nrhs < 0) { c->err = "residual_batched: nrhs must not be negative"; return -1; }
-    if (trans != 0 && trans != 1) { c->err = "residual_batched: trans must be 0 or 1"; return -1; }
-    if (n == 0 || batch == 0 || nrhs == 0) return 0;
-    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
-    if (!rc) rc = ba::check_strided(c->err, who, "X", ldx, strideX, n, nrhs, batch);
-    if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
-    if (!rc) rc = ba::check_strided(c->err, who, "R", ldr, strideR, n, nrhs, batch);
-    if (rc) return rc;
-    if (!d_A || !d_X || !d_B || !d_R) { c->err = "residual_batched: null pointer"; return -1; }
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, ba::residual_step(BR_MAX_UNITS, BT_MAX_LAUNCH, nrhs), [&](int64_t b0, int64_t nb) {
-        return launch_residual_batched(c, trans, d_A + b0 * strideA, lda, strideA, n, nb, nrhs, d_X + b0 * strideX, ldx, strideX,
-                                       d_B + b0 * strideB, ldb, strideB, d_R + b0 * strideR, ldr, strideR, opt(d_W, b0 * strideR));
-    });
-}
-
-int mpf_gerfs_batched(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, const double *d_LU, int64_t ldlu,
-                      int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, const double *d_B,
-                      int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t itmax, double *d_ferr, double *d_berr,
-                      int32_t *d_iters) {
-    if (!c) return -1;
-    const char *who = "gerfs_batched";
-    int rc = ba::check_sizes(c->err, who, ba::SMALL_MAXN, n, batch, "use mpf_gerfs (and mpf_gecon) on one matrix at a time");
-    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
-    if (rc) return rc;
-    if (nrhs < 0) { c->err = "gerfs_batched: nrhs must not be negative"; return -1; }
-    if (trans != 0 && trans != 1) { c->err = "gerfs_batched: trans must be 0 or 1"; return -1; }
-    if (n == 0 || batch == 0 || nrhs == 0) return 0;
-    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
-    if (!rc) rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
-    if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
-    if (!rc) rc = ba::check_strided(c->err, who, "X", ldx, strideX, n, nrhs, batch);
-    if (rc) return rc;
-    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !d_berr) { c->err = "gerfs_batched: null pointer"; return -1; }
-    const int it = itmax <= 0 ? 5 : (itmax > 31 ? 31 : itmax);   // mpf_gerfs's rule
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_gerfs_batched(c, trans, d_A + b0 * strideA, lda, strideA, d_LU + b0 * strideLU, ldlu, strideLU, n, nb,
-                                    d_ipiv + b0 * strideP, strideP, nrhs, d_B + b0 * strideB, ldb, strideB, d_X + b0 * strideX, ldx, strideX, it,
-                                    opt(d_ferr, b0 * nrhs), d_berr + b0 * nrhs, opt(d_iters, b0 * nrhs));
-    });
-}
-
-// ---- blocked: one n <= 1024 per call ------------------------------------------------------------------------------------------------------
-// The checks of the entries above with the larger limit; n below option batched_blocked_min_n (and <= 128) goes to those entries,
-// whose bits are the same by contract.
-int mpf_getrf_batched_blocked(mpf_ctx *c, double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t *d_ipiv,
-                              int64_t strideP, int32_t *d_info, int32_t fused) {
-    if (!c) return -1;
-    const char *who = "getrf_batched_blocked";
-    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, THEN_GETRS);
-    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
-    if (rc) return rc;
-    if (n == 0 || batch == 0) return 0;
-    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
-    if (rc) return rc;
-    if (!d_A || !d_ipiv) { c->err = "getrf_batched_blocked: null pointer"; return -1; }
-    if (forwards_to_small(c, n)) return mpf_getrf_batched(c, d_A, lda, strideA, n, batch, d_ipiv, strideP, d_info, fused);
-    MPF_HIP_TRY(c, hipSetDevice(c->device));
-    int valu = 0, stages = 7;
+// the blocked factorization's update form and pipeline depth: switches of the probe library only
+struct FactorForm { int valu, stages; };
+FactorForm factor_form(const mpf_ctx *c) {
 #ifdef MPF_PROBE
-    valu = c->tune.batched_blocked_valu;
-    stages = c->tune.batched_blocked_stages;
+    return {c->tune.batched_blocked_valu, c->tune.batched_blocked_stages};
+#else
+    return {0, 7};
 #endif
+}
+
+// ---- strided batches: one body per operator ------------------------------------------------------------------------------------------------
+int getrf_strided(mpf_ctx *c, const char *who, int32_t limit, const char *tail, double *d_A, int64_t lda, int64_t strideA, int32_t n,
+                  int64_t batch, int32_t *d_ipiv, int64_t strideP, int32_t *d_info, int32_t fused) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, tail);
+    if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
+    if (rc) return rc;
+    if (n == 0 || batch == 0) return 0;
+    rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
+    if (rc) return rc;
+    if (!d_A || !d_ipiv) return null_pointer(c, who);
+    MPF_HIP_TRY(c, hipSetDevice(c->device));
+    if (takes_small(c, limit, n))
+        return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+            return launch_getrf_batched(c, d_A + b0 * strideA, lda, strideA, n, nb, d_ipiv + b0 * strideP, strideP, opt(d_info, b0), fused != 0);
+        });
+    const FactorForm f = factor_form(c);
     return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
         return launch_getrf_batched_blocked(c, d_A + b0 * strideA, lda, strideA, n, nb, d_ipiv + b0 * strideP, strideP, opt(d_info, b0),
-                                            fused != 0, c->tune.batched_blocked_nb, valu, stages);
+                                            fused != 0, c->tune.batched_blocked_nb, f.valu, f.stages);
     });
 }
 
-int mpf_getrs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
-                              const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB) {
-    if (!c) return -1;
-    const char *who = "getrs_batched_blocked";
-    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, THEN_GETRS);
+int getrs_strided(mpf_ctx *c, const char *who, int32_t limit, const char *tail, int32_t trans, const double *d_LU, int64_t ldlu,
+                  int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb,
+                  int64_t strideB) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, tail);
     if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
+    if (!rc) rc = ba::check_nrhs_trans(c->err, who, nrhs, trans);
     if (rc) return rc;
-    if (nrhs < 0) { c->err = "getrs_batched_blocked: nrhs must not be negative"; return -1; }
-    if (trans != 0 && trans != 1) { c->err = "getrs_batched_blocked: trans must be 0 or 1"; return -1; }
     if (n == 0 || batch == 0 || nrhs == 0) return 0;
     rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
     if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
     if (rc) return rc;
-    if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs_batched_blocked: null pointer"; return -1; }
-    if (forwards_to_small(c, n)) return mpf_getrs_batched(c, trans, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, nrhs, d_B, ldb, strideB);
+    if (!d_LU || !d_ipiv || !d_B) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_getrs_batched_blocked(c, trans, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, nrhs,
-                                            d_B + b0 * strideB, ldb, strideB);
+    const bool small = takes_small(c, limit, n);
+    const auto launch = small ? launch_getrs_batched : launch_getrs_batched_blocked;
+    return ba::chunks(batch, small ? BT_MAX_LAUNCH : BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch(c, trans, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, nrhs, d_B + b0 * strideB, ldb, strideB);
     });
 }
 
-// The kernels need no flag buffer: every workgroup reads its matrix's diagonal and knows the first zero before its first store,
+// The blocked kernels need no flag buffer: every workgroup reads its matrix's diagonal and knows the first zero before its first store,
 // whether or not d_info is given.
-int mpf_getri_batched_blocked(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
-                              const int32_t *d_ipiv, int64_t strideP, double *d_inv, int64_t ldinv, int64_t strideInv, int32_t *d_info) {
-    if (!c) return -1;
-    const char *who = "getri_batched_blocked";
-    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, "factor it with mpf_factor_dev (and invert with mpf_getri)");
+int getri_strided(mpf_ctx *c, const char *who, int32_t limit, const char *tail, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n,
+                  int64_t batch, const int32_t *d_ipiv, int64_t strideP, double *d_inv, int64_t ldinv, int64_t strideInv, int32_t *d_info) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, tail);
     if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
     if (n == 0 || batch == 0) return 0;
     rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
     if (!rc) rc = ba::check_strided(c->err, who, "inv", ldinv, strideInv, n, n, batch);
     if (rc) return rc;
-    if (!d_LU || !d_ipiv || !d_inv) { c->err = "getri_batched_blocked: null pointer"; return -1; }
-    rc = check_out_of_place(c, who, d_LU, ldlu, strideLU, n, batch, d_inv, ldinv, strideInv);
+    if (!d_LU || !d_ipiv || !d_inv) return null_pointer(c, who);
+    rc = check_out_of_place(c, who, d_LU, ba::extent(n, batch, ldlu, strideLU), d_inv, ba::extent(n, batch, ldinv, strideInv));
     if (rc) return rc;
-    if (forwards_to_small(c, n)) return mpf_getri_batched(c, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_inv, ldinv, strideInv, d_info);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
+    if (takes_small(c, limit, n))
+        return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+            return launch_getri_batched(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_inv + b0 * strideInv,
+                                        ldinv, strideInv, opt(d_info, b0));
+        });
     return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
         return launch_getri_batched_blocked(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP,
                                             d_inv + b0 * strideInv, ldinv, strideInv, opt(d_info, b0), c->tune.batched_blocked_inv_ct);
     });
 }
 
-int mpf_getdet_batched_blocked(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
-                               const int32_t *d_ipiv, int64_t strideP, double *d_mant, int32_t *d_expo) {
-    if (!c) return -1;
-    const char *who = "getdet_batched_blocked";
-    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, "factor it with mpf_factor_dev (and take the determinant with mpf_getdet)");
+int getdet_strided(mpf_ctx *c, const char *who, int32_t limit, const char *tail, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n,
+                   int64_t batch, const int32_t *d_ipiv, int64_t strideP, double *d_mant, int32_t *d_expo) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, tail);
     if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
     if (rc) return rc;
     if (n == 0 || batch == 0) return 0;
     rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
     if (rc) return rc;
-    if (!d_LU || !d_ipiv || !d_mant || !d_expo) { c->err = "getdet_batched_blocked: null pointer"; return -1; }
-    if (forwards_to_small(c, n)) return mpf_getdet_batched(c, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_mant, d_expo);
+    if (!d_LU || !d_ipiv || !d_mant || !d_expo) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_getdet_batched_blocked(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0,
-                                             d_expo + b0);
+    const bool small = takes_small(c, limit, n);
+    const auto launch = small ? launch_getdet_batched : launch_getdet_batched_blocked;
+    return ba::chunks(batch, small ? BT_MAX_LAUNCH : BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch(c, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, d_mant + b0, d_expo + b0);
     });
 }
 
-// ---- the expert layer, one n <= 1024 per call (kernels in batched_refine_blocked.hip) ---------------------------------------------------
-int mpf_lange_batched_blocked(mpf_ctx *c, char norm, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_out) {
-    if (!c) return -1;
-    const char *who = "lange_batched_blocked";
-    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, ONE_AT_A_TIME);
+// the expert layer
+int lange_strided(mpf_ctx *c, const char *who, int32_t limit, const char *tail, char norm, const double *d_A, int64_t lda, int64_t strideA,
+                  int32_t n, int64_t batch, double *d_out) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, tail);
     if (rc) return rc;
-    int mode;
-    if (norm == '1' || norm == 'O' || norm == 'o') mode = 0;
-    else if (norm == 'I' || norm == 'i') mode = 1;
-    else if (norm == 'M' || norm == 'm') mode = 2;
-    else { c->err = "lange_batched_blocked: norm must be '1', 'O', 'I' or 'M'"; return -1; }
+    const int mode = ba::lange_mode(c->err, who, norm);
+    if (mode < 0) return -1;
     if (n == 0 || batch == 0) return 0;
     rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
     if (rc) return rc;
-    if (!d_A || !d_out) { c->err = "lange_batched_blocked: null pointer"; return -1; }
-    if (forwards_to_small(c, n)) return mpf_lange_batched(c, norm, d_A, lda, strideA, n, batch, d_out);
+    if (!d_A || !d_out) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_lange_batched_blocked(c, mode, d_A + b0 * strideA, lda, strideA, n, nb, d_out + b0);
+    const bool small = takes_small(c, limit, n);
+    const auto launch = small ? launch_lange_batched : launch_lange_batched_blocked;
+    return ba::chunks(batch, small ? BT_MAX_LAUNCH : BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch(c, mode, d_A + b0 * strideA, lda, strideA, n, nb, d_out + b0);
     });
 }
 
-int mpf_gecon_batched_blocked(mpf_ctx *c, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
-                              const double *d_anorm, double *d_rcond, double *d_ainvnm) {
-    if (!c) return -1;
-    const char *who = "gecon_batched_blocked";
-    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, ONE_AT_A_TIME);
+int gecon_strided(mpf_ctx *c, const char *who, int32_t limit, const char *tail, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU,
+                  int32_t n, int64_t batch, const double *d_anorm, double *d_rcond, double *d_ainvnm) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, tail);
     if (rc) return rc;
-    const bool one = norm == '1' || norm == 'O' || norm == 'o';
-    if (!one && norm != 'I' && norm != 'i') { c->err = "gecon_batched_blocked: norm must be '1', 'O' or 'I'"; return -1; }
+    const int inf = ba::gecon_mode(c->err, who, norm);
+    if (inf < 0) return -1;
     if (n == 0 || batch == 0) return 0;
     rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
     if (rc) return rc;
-    if (!d_LU || !d_anorm || !d_rcond) { c->err = "gecon_batched_blocked: null pointer"; return -1; }
-    if (forwards_to_small(c, n)) return mpf_gecon_batched(c, norm, d_LU, ldlu, strideLU, n, batch, d_anorm, d_rcond, d_ainvnm);
+    if (!d_LU || !d_anorm || !d_rcond) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_gecon_batched_blocked(c, one ? 0 : 1, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_anorm + b0, d_rcond + b0,
-                                            opt(d_ainvnm, b0));
+    const bool small = takes_small(c, limit, n);
+    const auto launch = small ? launch_gecon_batched : launch_gecon_batched_blocked;
+    return ba::chunks(batch, small ? BT_MAX_LAUNCH : BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch(c, inf, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_anorm + b0, d_rcond + b0, opt(d_ainvnm, b0));
     });
 }
 
-int mpf_residual_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
-                                 int32_t nrhs, const double *d_X, int64_t ldx, int64_t strideX, const double *d_B, int64_t ldb, int64_t strideB,
-                                 double *d_R, int64_t ldr, int64_t strideR, double *d_W) {
-    if (!c) return -1;
-    const char *who = "residual_batched_blocked";
-    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, ONE_AT_A_TIME);
+int residual_strided(mpf_ctx *c, const char *who, int32_t limit, const char *tail, int32_t trans, const double *d_A, int64_t lda,
+                     int64_t strideA, int32_t n, int64_t batch, int32_t nrhs, const double *d_X, int64_t ldx, int64_t strideX, const double *d_B,
+                     int64_t ldb, int64_t strideB, double *d_R, int64_t ldr, int64_t strideR, double *d_W) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, tail);
+    if (!rc) rc = ba::check_nrhs_trans(c->err, who, nrhs, trans);
     if (rc) return rc;
-    if (nrhs < 0) { c->err = "residual_batched_blocked: nrhs must not be negative"; return -1; }
-    if (trans != 0 && trans != 1) { c->err = "residual_batched_blocked: trans must be 0 or 1"; return -1; }
     if (n == 0 || batch == 0 || nrhs == 0) return 0;
     rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
     if (!rc) rc = ba::check_strided(c->err, who, "X", ldx, strideX, n, nrhs, batch);
     if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
     if (!rc) rc = ba::check_strided(c->err, who, "R", ldr, strideR, n, nrhs, batch);
     if (rc) return rc;
-    if (!d_A || !d_X || !d_B || !d_R) { c->err = "residual_batched_blocked: null pointer"; return -1; }
-    if (forwards_to_small(c, n))
-        return mpf_residual_batched(c, trans, d_A, lda, strideA, n, batch, nrhs, d_X, ldx, strideX, d_B, ldb, strideB, d_R, ldr, strideR, d_W);
+    if (!d_A || !d_X || !d_B || !d_R) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_residual_batched_blocked(c, trans, d_A + b0 * strideA, lda, strideA, n, nb, nrhs, d_X + b0 * strideX, ldx, strideX,
-                                               d_B + b0 * strideB, ldb, strideB, d_R + b0 * strideR, ldr, strideR, opt(d_W, b0 * strideR));
+    const bool small = takes_small(c, limit, n);
+    const auto launch = small ? launch_residual_batched : launch_residual_batched_blocked;
+    return ba::chunks(batch, small ? ba::residual_step(BR_MAX_UNITS, BT_MAX_LAUNCH, nrhs) : BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
+        return launch(c, trans, d_A + b0 * strideA, lda, strideA, n, nb, nrhs, d_X + b0 * strideX, ldx, strideX, d_B + b0 * strideB, ldb, strideB,
+                      d_R + b0 * strideR, ldr, strideR, opt(d_W, b0 * strideR));
     });
 }
 
-int mpf_gerfs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, const double *d_LU, int64_t ldlu,
-                              int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv, int64_t strideP, int32_t nrhs,
-                              const double *d_B, int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t itmax,
-                              double *d_ferr, double *d_berr, int32_t *d_iters) {
-    if (!c) return -1;
-    const char *who = "gerfs_batched_blocked";
-    int rc = ba::check_sizes(c->err, who, ba::BLOCKED_MAXN, n, batch, ONE_AT_A_TIME);
+int gerfs_strided(mpf_ctx *c, const char *who, int32_t limit, const char *tail, int32_t trans, const double *d_A, int64_t lda, int64_t strideA,
+                  const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv, int64_t strideP,
+                  int32_t nrhs, const double *d_B, int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t itmax,
+                  double *d_ferr, double *d_berr, int32_t *d_iters) {
+    int rc = ba::check_sizes(c->err, who, limit, n, batch, tail);
     if (!rc) rc = ba::check_pivot_stride(c->err, who, n, batch, strideP);
+    if (!rc) rc = ba::check_nrhs_trans(c->err, who, nrhs, trans);
     if (rc) return rc;
-    if (nrhs < 0) { c->err = "gerfs_batched_blocked: nrhs must not be negative"; return -1; }
-    if (trans != 0 && trans != 1) { c->err = "gerfs_batched_blocked: trans must be 0 or 1"; return -1; }
     if (n == 0 || batch == 0 || nrhs == 0) return 0;
     rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
     if (!rc) rc = ba::check_strided(c->err, who, "LU", ldlu, strideLU, n, n, batch);
     if (!rc) rc = ba::check_strided(c->err, who, "B", ldb, strideB, n, nrhs, batch);
     if (!rc) rc = ba::check_strided(c->err, who, "X", ldx, strideX, n, nrhs, batch);
     if (rc) return rc;
-    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !d_berr) { c->err = "gerfs_batched_blocked: null pointer"; return -1; }
-    if (forwards_to_small(c, n))
-        return mpf_gerfs_batched(c, trans, d_A, lda, strideA, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, nrhs, d_B, ldb, strideB, d_X,
-                                 ldx, strideX, itmax, d_ferr, d_berr, d_iters);
-    const int it = itmax <= 0 ? 5 : (itmax > 31 ? 31 : itmax);   // mpf_gerfs's rule
+    if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X || !d_berr) return null_pointer(c, who);
+    const int it = ba::clamp_itmax(itmax);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    return ba::chunks(batch, d_ferr ? ba::ferr_step(BB_MAX_LAUNCH, n, nrhs) : BB_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
-        return launch_gerfs_batched_blocked(c, trans, d_A + b0 * strideA, lda, strideA, d_LU + b0 * strideLU, ldlu, strideLU, n, nb,
-                                            d_ipiv + b0 * strideP, strideP, nrhs, d_B + b0 * strideB, ldb, strideB, d_X + b0 * strideX, ldx,
-                                            strideX, it, opt(d_ferr, b0 * nrhs), d_berr + b0 * nrhs, opt(d_iters, b0 * nrhs));
+    const bool small = takes_small(c, limit, n);
+    const auto launch = small ? launch_gerfs_batched : launch_gerfs_batched_blocked;
+    const int64_t step = small ? BT_MAX_LAUNCH : (d_ferr ? ba::ferr_step(BB_MAX_LAUNCH, n, nrhs) : BB_MAX_LAUNCH);
+    return ba::chunks(batch, step, [&](int64_t b0, int64_t nb) {
+        return launch(c, trans, d_A + b0 * strideA, lda, strideA, d_LU + b0 * strideLU, ldlu, strideLU, n, nb, d_ipiv + b0 * strideP, strideP, nrhs,
+                      d_B + b0 * strideB, ldb, strideB, d_X + b0 * strideX, ldx, strideX, it, opt(d_ferr, b0 * nrhs),
+                      d_berr + b0 * nrhs, opt(d_iters, b0 * nrhs));
     });
 }
 
-} // extern "C"
-
-// ---- equilibration of the strided batches (kernels in batched_equil.hip) ------------------------------------------------------------------
-// One body per operator for the small and the blocked entry: the limit, the name and whether the call takes the small kernels differ.
-namespace {
-const char *const ONE_GEEQU = "equilibrate it with mpf_geequ (or mpf_gesvx) and factor it with mpf_factor_dev";
-
+// equilibration
 int geequ_strided(mpf_ctx *c, const char *who, int32_t limit, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
                   double *d_r, double *d_c, double *d_rowcnd, double *d_colcnd, double *d_amax, int32_t *d_info) {
     int rc = ba::check_sizes(c->err, who, limit, n, batch, ONE_GEEQU);
@@ -426,9 +244,9 @@ int geequ_strided(mpf_ctx *c, const char *who, int32_t limit, const double *d_A,
     if (n == 0 || batch == 0) return 0;
     rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
     if (rc) return rc;
-    if (!d_A || !d_r || !d_c || !d_rowcnd || !d_colcnd || !d_amax || !d_info) { c->err = std::string(who) + ": null pointer"; return -1; }
+    if (!d_A || !d_r || !d_c || !d_rowcnd || !d_colcnd || !d_amax || !d_info) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    if (limit == ba::SMALL_MAXN || forwards_to_small(c, n))
+    if (takes_small(c, limit, n))
         return ba::chunks(batch, BT_MAX_LAUNCH, [&](int64_t b0, int64_t nb) {
             return launch_geequ_batched(c, d_A + b0 * strideA, lda, strideA, n, nb, d_r + b0 * n, d_c + b0 * n, d_rowcnd + b0, d_colcnd + b0,
                                         d_amax + b0, d_info + b0);
@@ -451,7 +269,7 @@ int laqge_strided(mpf_ctx *c, const char *who, int32_t limit, int32_t rule, cons
     if (n == 0 || batch == 0) return 0;
     rc = ba::check_strided(c->err, who, "A", lda, strideA, n, n, batch);
     if (rc) return rc;
-    if (!d_A || !d_r || !d_c || !d_rowcnd || !d_colcnd || !d_amax || !d_info || !d_out || !d_equed) { c->err = std::string(who) + ": null pointer"; return -1; }
+    if (!d_A || !d_r || !d_c || !d_rowcnd || !d_colcnd || !d_amax || !d_info || !d_out || !d_equed) return null_pointer(c, who);
     const int64_t ext = ba::extent(n, batch, lda, strideA);
     if (d_out != d_A && ba::ranges_overlap((uintptr_t)d_A, ext, (uintptr_t)d_out, ext)) {
         c->err = std::string(who) + ": d_out overlaps d_A (in place is d_out == d_A)";
@@ -463,7 +281,7 @@ int laqge_strided(mpf_ctx *c, const char *who, int32_t limit, int32_t rule, cons
                                    d_info + b0, d_equed + b0, opt(d_spread, 2 * b0));
     });
     if (rc) return rc;
-    if (limit == ba::SMALL_MAXN || forwards_to_small(c, n))
+    if (takes_small(c, limit, n))
         return ba::chunks(batch, ba::elements_step(BT_MAX_LAUNCH, (int64_t)n * n), [&](int64_t b0, int64_t nb) {
             return launch_laqge_batched(c, d_A + b0 * strideA, lda, strideA, n, nb, d_r + b0 * n, d_c + b0 * n, d_equed + b0, d_out + b0 * strideA);
         });
@@ -482,7 +300,7 @@ int lascl2_strided(mpf_ctx *c, const char *who, int32_t limit, const double *d_s
     if (n == 0 || batch == 0 || nrhs == 0) return 0;
     rc = ba::check_strided(c->err, who, "V", ldv, strideV, n, nrhs, batch);
     if (rc) return rc;
-    if (!d_s || !d_V) { c->err = std::string(who) + ": null pointer"; return -1; }
+    if (!d_s || !d_V) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     const int32_t kc = (int32_t)ba::elements_step(nrhs, n);        // columns per launch: n kc < 2^31
     for (int32_t k0 = 0; k0 < nrhs; k0 += kc) {
@@ -496,8 +314,102 @@ int lascl2_strided(mpf_ctx *c, const char *who, int32_t limit, const double *d_s
 }
 } // namespace
 
+// ---- the entries of the strided batches: the name, the limit, where a larger matrix goes -------------------------------------------------
 extern "C" {
 
+int mpf_getrf_batched(mpf_ctx *c, double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t *d_ipiv, int64_t strideP,
+                      int32_t *d_info, int32_t fused) {
+    if (!c) return -1;
+    return getrf_strided(c, "getrf_batched", ba::SMALL_MAXN, THEN_GETRS, d_A, lda, strideA, n, batch, d_ipiv, strideP, d_info, fused);
+}
+int mpf_getrf_batched_blocked(mpf_ctx *c, double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t *d_ipiv,
+                              int64_t strideP, int32_t *d_info, int32_t fused) {
+    if (!c) return -1;
+    return getrf_strided(c, "getrf_batched_blocked", ba::BLOCKED_MAXN, THEN_GETRS, d_A, lda, strideA, n, batch, d_ipiv, strideP, d_info, fused);
+}
+int mpf_getrs_batched(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                      const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB) {
+    if (!c) return -1;
+    return getrs_strided(c, "getrs_batched", ba::SMALL_MAXN, THEN_GETRS, trans, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, nrhs, d_B, ldb,
+                         strideB);
+}
+int mpf_getrs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                              const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, double *d_B, int64_t ldb, int64_t strideB) {
+    if (!c) return -1;
+    return getrs_strided(c, "getrs_batched_blocked", ba::BLOCKED_MAXN, THEN_GETRS, trans, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, nrhs,
+                         d_B, ldb, strideB);
+}
+int mpf_getri_batched(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv,
+                      int64_t strideP, double *d_inv, int64_t ldinv, int64_t strideInv, int32_t *d_info) {
+    if (!c) return -1;
+    return getri_strided(c, "getri_batched", ba::SMALL_MAXN, THEN_GETRS, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_inv, ldinv, strideInv,
+                         d_info);
+}
+int mpf_getri_batched_blocked(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                              const int32_t *d_ipiv, int64_t strideP, double *d_inv, int64_t ldinv, int64_t strideInv, int32_t *d_info) {
+    if (!c) return -1;
+    return getri_strided(c, "getri_batched_blocked", ba::BLOCKED_MAXN, THEN_GETRI, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_inv, ldinv,
+                         strideInv, d_info);
+}
+int mpf_getdet_batched(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv,
+                       int64_t strideP, double *d_mant, int32_t *d_expo) {
+    if (!c) return -1;
+    return getdet_strided(c, "getdet_batched", ba::SMALL_MAXN, THEN_GETRS, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_mant, d_expo);
+}
+int mpf_getdet_batched_blocked(mpf_ctx *c, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                               const int32_t *d_ipiv, int64_t strideP, double *d_mant, int32_t *d_expo) {
+    if (!c) return -1;
+    return getdet_strided(c, "getdet_batched_blocked", ba::BLOCKED_MAXN, THEN_GETDET, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP, d_mant, d_expo);
+}
+int mpf_lange_batched(mpf_ctx *c, char norm, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_out) {
+    if (!c) return -1;
+    return lange_strided(c, "lange_batched", ba::SMALL_MAXN, ONE_LANGE, norm, d_A, lda, strideA, n, batch, d_out);
+}
+int mpf_lange_batched_blocked(mpf_ctx *c, char norm, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_out) {
+    if (!c) return -1;
+    return lange_strided(c, "lange_batched_blocked", ba::BLOCKED_MAXN, ONE_AT_A_TIME, norm, d_A, lda, strideA, n, batch, d_out);
+}
+int mpf_gecon_batched(mpf_ctx *c, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                      const double *d_anorm, double *d_rcond, double *d_ainvnm) {
+    if (!c) return -1;
+    return gecon_strided(c, "gecon_batched", ba::SMALL_MAXN, ONE_GECON, norm, d_LU, ldlu, strideLU, n, batch, d_anorm, d_rcond, d_ainvnm);
+}
+int mpf_gecon_batched_blocked(mpf_ctx *c, char norm, const double *d_LU, int64_t ldlu, int64_t strideLU, int32_t n, int64_t batch,
+                              const double *d_anorm, double *d_rcond, double *d_ainvnm) {
+    if (!c) return -1;
+    return gecon_strided(c, "gecon_batched_blocked", ba::BLOCKED_MAXN, ONE_AT_A_TIME, norm, d_LU, ldlu, strideLU, n, batch, d_anorm, d_rcond,
+                         d_ainvnm);
+}
+int mpf_residual_batched(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, int32_t nrhs,
+                         const double *d_X, int64_t ldx, int64_t strideX, const double *d_B, int64_t ldb, int64_t strideB, double *d_R,
+                         int64_t ldr, int64_t strideR, double *d_W) {
+    if (!c) return -1;
+    return residual_strided(c, "residual_batched", ba::SMALL_MAXN, ONE_GERFS, trans, d_A, lda, strideA, n, batch, nrhs, d_X, ldx, strideX, d_B, ldb,
+                            strideB, d_R, ldr, strideR, d_W);
+}
+int mpf_residual_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch,
+                                 int32_t nrhs, const double *d_X, int64_t ldx, int64_t strideX, const double *d_B, int64_t ldb, int64_t strideB,
+                                 double *d_R, int64_t ldr, int64_t strideR, double *d_W) {
+    if (!c) return -1;
+    return residual_strided(c, "residual_batched_blocked", ba::BLOCKED_MAXN, ONE_AT_A_TIME, trans, d_A, lda, strideA, n, batch, nrhs, d_X, ldx,
+                            strideX, d_B, ldb, strideB, d_R, ldr, strideR, d_W);
+}
+int mpf_gerfs_batched(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, const double *d_LU, int64_t ldlu,
+                      int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv, int64_t strideP, int32_t nrhs, const double *d_B,
+                      int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t itmax, double *d_ferr, double *d_berr,
+                      int32_t *d_iters) {
+    if (!c) return -1;
+    return gerfs_strided(c, "gerfs_batched", ba::SMALL_MAXN, ONE_GERFS, trans, d_A, lda, strideA, d_LU, ldlu, strideLU, n, batch, d_ipiv, strideP,
+                         nrhs, d_B, ldb, strideB, d_X, ldx, strideX, itmax, d_ferr, d_berr, d_iters);
+}
+int mpf_gerfs_batched_blocked(mpf_ctx *c, int32_t trans, const double *d_A, int64_t lda, int64_t strideA, const double *d_LU, int64_t ldlu,
+                              int64_t strideLU, int32_t n, int64_t batch, const int32_t *d_ipiv, int64_t strideP, int32_t nrhs,
+                              const double *d_B, int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t itmax,
+                              double *d_ferr, double *d_berr, int32_t *d_iters) {
+    if (!c) return -1;
+    return gerfs_strided(c, "gerfs_batched_blocked", ba::BLOCKED_MAXN, ONE_AT_A_TIME, trans, d_A, lda, strideA, d_LU, ldlu, strideLU, n, batch,
+                         d_ipiv, strideP, nrhs, d_B, ldb, strideB, d_X, ldx, strideX, itmax, d_ferr, d_berr, d_iters);
+}
 int mpf_geequ_batched(mpf_ctx *c, const double *d_A, int64_t lda, int64_t strideA, int32_t n, int64_t batch, double *d_r, double *d_c,
                       double *d_rowcnd, double *d_colcnd, double *d_amax, int32_t *d_info) {
     if (!c) return -1;
@@ -611,44 +523,59 @@ int mpf_vbatch_offsets(const mpf_vbatch *vb, int64_t *offM, int64_t *offV) {
 namespace {
 // what every vbatched entry point asks first
 int vb_enter(mpf_ctx *c, const mpf_vbatch *vb, const char *who) {
+    if (!c) return -1;
     if (!vb) { c->err = std::string(who) + ": null pointer (descriptor)"; return -1; }
     if (vb->ctx != c) { c->err = std::string(who) + ": the descriptor belongs to another context"; return -1; }
     return 0;
+}
+// a tall operand (right-hand sides, solutions) has a row for every row of every matrix
+int vb_check_ld(mpf_ctx *c, const mpf_vbatch *vb, const char *who, const char *what, int64_t ld) {
+    if (ld >= vb->plan.total_n) return 0;
+    c->err = std::string(who) + ": leading dimension of " + what + " < total_n";
+    return -1;
 }
 // f(list + i0, count, top, nmax) for every chunk of every class that is not empty
 template <class F>
 int vb_classes(const mpf_vbatch *vb, F f) {
     const vbatch::Plan &p = vb->plan;
-    for (int k = 0; k < vbatch::NCLASS; ++k)
-        for (int64_t i0 = 0; i0 < p.count[k]; i0 += BT_MAX_LAUNCH) {
-            const int64_t nb = p.count[k] - i0 < BT_MAX_LAUNCH ? p.count[k] - i0 : BT_MAX_LAUNCH;
-            const int rc = f(vb->d_list.get() + p.start[k] + i0, nb, vbatch::CLASS_TOP[k], p.nmax[k]);
-            if (rc) return rc;
-        }
-    return 0;
-}
-// the matrices of order 0: info = 0, determinant (0.5, 1)
-int vb_empty(mpf_ctx *c, const mpf_vbatch *vb, int32_t *info, double *mant, int32_t *expo) {
-    for (int64_t i0 = 0; i0 < vb->plan.zeros; i0 += BT_MAX_LAUNCH) {
-        const int64_t nb = vb->plan.zeros - i0 < BT_MAX_LAUNCH ? vb->plan.zeros - i0 : BT_MAX_LAUNCH;
-        const int rc = launch_vbatched_empty(c, vb->d_list.get() + i0, nb, info, mant, expo);
+    for (int k = 0; k < vbatch::NCLASS; ++k) {
+        const int rc = ba::chunks(p.count[k], BT_MAX_LAUNCH, [&](int64_t i0, int64_t nb) {
+            return f(vb->d_list.get() + p.start[k] + i0, nb, vbatch::CLASS_TOP[k], p.nmax[k]);
+        });
         if (rc) return rc;
     }
     return 0;
+}
+// f(device list + first, count) for every chunk of the matrices of order 0, list[0 .. zeros)
+template <class F>
+int vb_zeros(const mpf_vbatch *vb, F f) {
+    return ba::chunks(vb->plan.zeros, BT_MAX_LAUNCH, [&](int64_t i0, int64_t nb) { return f(vb->d_list.get() + i0, nb); });
+}
+// their outputs from the factor layer: info = 0, determinant (0.5, 1)
+int vb_empty(mpf_ctx *c, const mpf_vbatch *vb, int32_t *info, double *mant, int32_t *expo) {
+    return vb_zeros(vb, [&](const int32_t *idx, int64_t nb) { return launch_vbatched_empty(c, idx, nb, info, mant, expo); });
+}
+// ... and from the expert layer
+int vb_refine_empty(mpf_ctx *c, const mpf_vbatch *vb, int nrhs, double *norm, double *rcond, double *ainvnm, double *berr, double *ferr,
+                    int32_t *iters) {
+    return vb_zeros(vb, [&](const int32_t *idx, int64_t nb) {
+        return launch_refine_vbatched_empty(c, idx, nb, nrhs, norm, rcond, ainvnm, berr, ferr, iters);
+    });
 }
 // f(device list + first, count, nmax, host orders of those entries) for every chunk of every launch group of the large list
 template <class F>
 int vb_large(const mpf_vbatch *vb, F f) {
     const vbatch::Plan &p = vb->plan;
     std::vector<int32_t> ns;
-    for (int g = 0; g < vbatch::NGROUP; ++g)
-        for (int64_t i0 = 0; i0 < p.gcount[g]; i0 += BB_MAX_LAUNCH) {
-            const int64_t nb = p.gcount[g] - i0 < BB_MAX_LAUNCH ? p.gcount[g] - i0 : BB_MAX_LAUNCH, at = p.gstart[g] + i0;
+    for (int g = 0; g < vbatch::NGROUP; ++g) {
+        const int rc = ba::chunks(p.gcount[g], BB_MAX_LAUNCH, [&](int64_t i0, int64_t nb) {
+            const int64_t at = p.gstart[g] + i0;
             ns.resize((size_t)nb);
             for (int64_t i = 0; i < nb; ++i) ns[(size_t)i] = p.n[(size_t)p.list[(size_t)(at + i)]];
-            const int rc = f(vb->d_list.get() + at, nb, (int)ns.back(), ns.data());
-            if (rc) return rc;
-        }
+            return f(vb->d_list.get() + at, nb, (int)ns.back(), ns.data());
+        });
+        if (rc) return rc;
+    }
     return 0;
 }
 // The expert layer's launch groups over every matrix of order >= 1, list[zeros .. batch) (vbatch_plan.h: refine_chunks; limit > 0: the
@@ -673,27 +600,17 @@ RbvWork vb_work(mpf_ctx *c, const mpf_vbatch *vb, const vbatch::Chunk &k) {
     return RbvWork{vb->d_lrow.get() + k.first, vb->d_ltile.get() + k.first, p.lrow[(size_t)k.first], p.ltile[(size_t)k.first],
                    c->rb_part.get(), c->rb_g.get(), c->rb_xm.get()};
 }
-// the order-0 matrices' outputs
-int vb_refine_empty(mpf_ctx *c, const mpf_vbatch *vb, int nrhs, double *norm, double *rcond, double *ainvnm, double *berr, double *ferr,
-                    int32_t *iters) {
-    for (int64_t i0 = 0; i0 < vb->plan.zeros; i0 += BT_MAX_LAUNCH) {
-        const int64_t nb = vb->plan.zeros - i0 < BT_MAX_LAUNCH ? vb->plan.zeros - i0 : BT_MAX_LAUNCH;
-        const int rc = launch_refine_vbatched_empty(c, vb->d_list.get() + i0, nb, nrhs, norm, rcond, ainvnm, berr, ferr, iters);
-        if (rc) return rc;
-    }
-    return 0;
-}
 BtRagged vb_arrays(const mpf_vbatch *vb) { return BtRagged{vb->d_n.get(), vb->d_off.get(), vb->d_ld.get(), vb->d_offv.get()}; }
 } // namespace
 
 extern "C" {
 
 int mpf_getrf_vbatched(mpf_ctx *c, const mpf_vbatch *vb, double *d_A, int32_t *d_ipiv, int32_t *d_info, int32_t fused) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "getrf_vbatched");
+    const char *who = "getrf_vbatched";
+    int rc = vb_enter(c, vb, who);
     if (rc) return rc;
     if (vb->plan.batch == 0) return 0;
-    if (vb->plan.total_n > 0 && (!d_A || !d_ipiv)) { c->err = "getrf_vbatched: null pointer"; return -1; }
+    if (vb->plan.total_n > 0 && (!d_A || !d_ipiv)) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     rc = vb_empty(c, vb, d_info, nullptr, nullptr);
     if (rc) return rc;
@@ -702,16 +619,12 @@ int mpf_getrf_vbatched(mpf_ctx *c, const mpf_vbatch *vb, double *d_A, int32_t *d
         return launch_getrf_vbatched(c, v, idx, count, top, nmax, d_A, d_ipiv, d_info, fused != 0);
     });
     if (rc || vb->plan.large_count == 0) return rc;
-    int valu = 0, stages = 7;
-#ifdef MPF_PROBE
-    valu = c->tune.batched_blocked_valu;
-    stages = c->tune.batched_blocked_stages;
-#endif
+    const FactorForm f = factor_form(c);
     const int nb = vbatched_blocked_nb(c->tune.batched_blocked_nb);
     return vb_large(vb, [&](const int32_t *idx, int64_t count, int nmax, const int32_t *ns) {
         for (const vbatch::Step &s : vbatch::factor_steps(ns, count, nb)) {   // nmax - s.j0 == s.rows
             const int e = launch_getrf_vbatched_blocked_step(c, v, idx + s.first, count - s.first, nmax, s.j0, nb, d_A, d_ipiv, d_info,
-                                                             fused != 0, valu, stages);
+                                                             fused != 0, f.valu, f.stages);
             if (e) return e;
         }
         return 0;
@@ -720,14 +633,14 @@ int mpf_getrf_vbatched(mpf_ctx *c, const mpf_vbatch *vb, double *d_A, int32_t *d
 
 int mpf_getrs_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const double *d_LU, const int32_t *d_ipiv, int32_t nrhs, double *d_B,
                        int64_t ldb) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "getrs_vbatched");
+    const char *who = "getrs_vbatched";
+    int rc = vb_enter(c, vb, who);
+    if (!rc) rc = ba::check_nrhs_trans(c->err, who, nrhs, trans);
     if (rc) return rc;
-    if (nrhs < 0) { c->err = "getrs_vbatched: nrhs must not be negative"; return -1; }
-    if (trans != 0 && trans != 1) { c->err = "getrs_vbatched: trans must be 0 or 1"; return -1; }
     if (vb->plan.batch == 0 || vb->plan.total_n == 0 || nrhs == 0) return 0;
-    if (ldb < vb->plan.total_n) { c->err = "getrs_vbatched: leading dimension of B < total_n"; return -1; }
-    if (!d_LU || !d_ipiv || !d_B) { c->err = "getrs_vbatched: null pointer"; return -1; }
+    rc = vb_check_ld(c, vb, who, "B", ldb);
+    if (rc) return rc;
+    if (!d_LU || !d_ipiv || !d_B) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     const BtRagged v = vb_arrays(vb);
     rc = vb_classes(vb, [&](const int32_t *idx, int64_t count, int top, int nmax) {
@@ -740,16 +653,15 @@ int mpf_getrs_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const do
 }
 
 int mpf_getri_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_LU, const int32_t *d_ipiv, double *d_inv, int32_t *d_info) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "getri_vbatched");
+    const char *who = "getri_vbatched";
+    int rc = vb_enter(c, vb, who);
     if (rc) return rc;
     if (vb->plan.batch == 0) return 0;
     if (vb->plan.total_n > 0) {
-        if (!d_LU || !d_ipiv || !d_inv) { c->err = "getri_vbatched: null pointer"; return -1; }
-        // the factors are still being read while the result is stored (mpf_getri_batched's rule, on the two operands' extents)
-        const uintptr_t a0 = (uintptr_t)d_LU, a1 = a0 + (size_t)vb->plan.extent * sizeof(double);
-        const uintptr_t b0 = (uintptr_t)d_inv, b1 = b0 + (size_t)vb->plan.extent * sizeof(double);
-        if (a0 < b1 && b0 < a1) { c->err = "getri_vbatched: d_inv overlaps d_LU (the inverse is formed out of place)"; return -1; }
+        if (!d_LU || !d_ipiv || !d_inv) return null_pointer(c, who);
+        // mpf_getri_batched's rule, on the two operands' extents
+        rc = check_out_of_place(c, who, d_LU, vb->plan.extent, d_inv, vb->plan.extent);
+        if (rc) return rc;
     }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     rc = vb_empty(c, vb, d_info, nullptr, nullptr);
@@ -765,11 +677,11 @@ int mpf_getri_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_LU, con
 }
 
 int mpf_getdet_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_LU, const int32_t *d_ipiv, double *d_mant, int32_t *d_expo) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "getdet_vbatched");
+    const char *who = "getdet_vbatched";
+    int rc = vb_enter(c, vb, who);
     if (rc) return rc;
     if (vb->plan.batch == 0) return 0;
-    if (!d_mant || !d_expo || (vb->plan.total_n > 0 && (!d_LU || !d_ipiv))) { c->err = "getdet_vbatched: null pointer"; return -1; }
+    if (!d_mant || !d_expo || (vb->plan.total_n > 0 && (!d_LU || !d_ipiv))) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     rc = vb_empty(c, vb, nullptr, d_mant, d_expo);
     if (rc) return rc;
@@ -787,16 +699,13 @@ int mpf_getdet_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_LU, co
 // Every matrix of order >= 1 takes the ragged blocked expert kernels, whose bits for n <= 128 are the small expert entries' by contract:
 // the descriptor's classes and batched_blocked_min_n play no part.
 int mpf_lange_vbatched(mpf_ctx *c, const mpf_vbatch *vb, char norm, const double *d_A, double *d_out) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "lange_vbatched");
+    const char *who = "lange_vbatched";
+    int rc = vb_enter(c, vb, who);
     if (rc) return rc;
-    int mode;
-    if (norm == '1' || norm == 'O' || norm == 'o') mode = 0;
-    else if (norm == 'I' || norm == 'i') mode = 1;
-    else if (norm == 'M' || norm == 'm') mode = 2;
-    else { c->err = "lange_vbatched: norm must be '1', 'O', 'I' or 'M'"; return -1; }
+    const int mode = ba::lange_mode(c->err, who, norm);
+    if (mode < 0) return -1;
     if (vb->plan.batch == 0) return 0;
-    if (!d_out || (vb->plan.total_n > 0 && !d_A)) { c->err = "lange_vbatched: null pointer"; return -1; }
+    if (!d_out || (vb->plan.total_n > 0 && !d_A)) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     rc = vb_refine_empty(c, vb, 0, d_out, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
@@ -810,13 +719,13 @@ int mpf_lange_vbatched(mpf_ctx *c, const mpf_vbatch *vb, char norm, const double
 
 int mpf_gecon_vbatched(mpf_ctx *c, const mpf_vbatch *vb, char norm, const double *d_LU, const double *d_anorm, double *d_rcond,
                        double *d_ainvnm) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "gecon_vbatched");
+    const char *who = "gecon_vbatched";
+    int rc = vb_enter(c, vb, who);
     if (rc) return rc;
-    const bool one = norm == '1' || norm == 'O' || norm == 'o';
-    if (!one && norm != 'I' && norm != 'i') { c->err = "gecon_vbatched: norm must be '1', 'O' or 'I'"; return -1; }
+    const int inf = ba::gecon_mode(c->err, who, norm);
+    if (inf < 0) return -1;
     if (vb->plan.batch == 0) return 0;
-    if (!d_rcond || (vb->plan.total_n > 0 && (!d_LU || !d_anorm))) { c->err = "gecon_vbatched: null pointer"; return -1; }
+    if (!d_rcond || (vb->plan.total_n > 0 && (!d_LU || !d_anorm))) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     rc = vb_refine_empty(c, vb, 0, nullptr, d_rcond, d_ainvnm, nullptr, nullptr, nullptr);
     if (rc) return rc;
@@ -825,8 +734,7 @@ int mpf_gecon_vbatched(mpf_ctx *c, const mpf_vbatch *vb, char norm, const double
     MPF_HIP_TRY(c, c->rb_part.grow(need.tiles));                    // (once, before the first launch that uses it)
     const BtRagged v = vb_arrays(vb);
     for (const vbatch::Chunk &k : chunks) {
-        rc = launch_gecon_vbatched(c, v, vb->d_list.get() + k.first, vb_work(c, vb, k), k.count, k.nmax, one ? 0 : 1, d_LU, d_anorm, d_rcond,
-                                   d_ainvnm);
+        rc = launch_gecon_vbatched(c, v, vb->d_list.get() + k.first, vb_work(c, vb, k), k.count, k.nmax, inf, d_LU, d_anorm, d_rcond, d_ainvnm);
         if (rc) return rc;
     }
     return 0;
@@ -834,16 +742,16 @@ int mpf_gecon_vbatched(mpf_ctx *c, const mpf_vbatch *vb, char norm, const double
 
 int mpf_residual_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const double *d_A, int32_t nrhs, const double *d_X, int64_t ldx,
                           const double *d_B, int64_t ldb, double *d_R, int64_t ldr, double *d_W) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "residual_vbatched");
+    const char *who = "residual_vbatched";
+    int rc = vb_enter(c, vb, who);
+    if (!rc) rc = ba::check_nrhs_trans(c->err, who, nrhs, trans);
     if (rc) return rc;
-    if (nrhs < 0) { c->err = "residual_vbatched: nrhs must not be negative"; return -1; }
-    if (trans != 0 && trans != 1) { c->err = "residual_vbatched: trans must be 0 or 1"; return -1; }
     if (vb->plan.batch == 0 || vb->plan.total_n == 0 || nrhs == 0) return 0;
-    if (ldx < vb->plan.total_n) { c->err = "residual_vbatched: leading dimension of X < total_n"; return -1; }
-    if (ldb < vb->plan.total_n) { c->err = "residual_vbatched: leading dimension of B < total_n"; return -1; }
-    if (ldr < vb->plan.total_n) { c->err = "residual_vbatched: leading dimension of R < total_n"; return -1; }
-    if (!d_A || !d_X || !d_B || !d_R) { c->err = "residual_vbatched: null pointer"; return -1; }
+    rc = vb_check_ld(c, vb, who, "X", ldx);
+    if (!rc) rc = vb_check_ld(c, vb, who, "B", ldb);
+    if (!rc) rc = vb_check_ld(c, vb, who, "R", ldr);
+    if (rc) return rc;
+    if (!d_A || !d_X || !d_B || !d_R) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     const BtRagged v = vb_arrays(vb);
     for (const vbatch::Chunk &k : vb_refine_chunks(vb, 0, 0, nullptr)) {
@@ -856,19 +764,19 @@ int mpf_residual_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const
 int mpf_gerfs_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const double *d_A, const double *d_LU, const int32_t *d_ipiv,
                        int32_t nrhs, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t itmax, double *d_ferr, double *d_berr,
                        int32_t *d_iters) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "gerfs_vbatched");
+    const char *who = "gerfs_vbatched";
+    int rc = vb_enter(c, vb, who);
+    if (!rc) rc = ba::check_nrhs_trans(c->err, who, nrhs, trans);
     if (rc) return rc;
-    if (nrhs < 0) { c->err = "gerfs_vbatched: nrhs must not be negative"; return -1; }
-    if (trans != 0 && trans != 1) { c->err = "gerfs_vbatched: trans must be 0 or 1"; return -1; }
     if (vb->plan.batch == 0 || nrhs == 0) return 0;
-    if (!d_berr) { c->err = "gerfs_vbatched: null pointer"; return -1; }
+    if (!d_berr) return null_pointer(c, who);
     if (vb->plan.total_n > 0) {
-        if (ldb < vb->plan.total_n) { c->err = "gerfs_vbatched: leading dimension of B < total_n"; return -1; }
-        if (ldx < vb->plan.total_n) { c->err = "gerfs_vbatched: leading dimension of X < total_n"; return -1; }
-        if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X) { c->err = "gerfs_vbatched: null pointer"; return -1; }
+        rc = vb_check_ld(c, vb, who, "B", ldb);
+        if (!rc) rc = vb_check_ld(c, vb, who, "X", ldx);
+        if (rc) return rc;
+        if (!d_A || !d_LU || !d_ipiv || !d_B || !d_X) return null_pointer(c, who);
     }
-    const int it = itmax <= 0 ? 5 : (itmax > 31 ? 31 : itmax);   // mpf_gerfs's rule
+    const int it = ba::clamp_itmax(itmax);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     rc = vb_refine_empty(c, vb, nrhs, nullptr, nullptr, nullptr, d_berr, d_ferr, d_iters);
     if (rc) return rc;
@@ -893,17 +801,14 @@ int mpf_gerfs_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t trans, const do
 // maxima of a chunk in the context's workspace by list position; the decision of laqge runs over the whole list, orders 0 included.
 int mpf_geequ_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_A, double *d_r, double *d_c, double *d_rowcnd, double *d_colcnd,
                        double *d_amax, int32_t *d_info) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "geequ_vbatched");
+    const char *who = "geequ_vbatched";
+    int rc = vb_enter(c, vb, who);
     if (rc) return rc;
     if (vb->plan.batch == 0) return 0;
-    if (!d_rowcnd || !d_colcnd || !d_amax || !d_info || (vb->plan.total_n > 0 && (!d_A || !d_r || !d_c))) { c->err = "geequ_vbatched: null pointer"; return -1; }
+    if (!d_rowcnd || !d_colcnd || !d_amax || !d_info || (vb->plan.total_n > 0 && (!d_A || !d_r || !d_c))) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
-    for (int64_t i0 = 0; i0 < vb->plan.zeros; i0 += BT_MAX_LAUNCH) {
-        const int64_t nb = vb->plan.zeros - i0 < BT_MAX_LAUNCH ? vb->plan.zeros - i0 : BT_MAX_LAUNCH;
-        rc = launch_geequ_vbatched_empty(c, vb->d_list.get() + i0, nb, d_rowcnd, d_colcnd, d_amax, d_info);
-        if (rc) return rc;
-    }
+    rc = vb_zeros(vb, [&](const int32_t *idx, int64_t nb) { return launch_geequ_vbatched_empty(c, idx, nb, d_rowcnd, d_colcnd, d_amax, d_info); });
+    if (rc) return rc;
     RbvNeed need;
     const std::vector<vbatch::Chunk> chunks = vb_refine_chunks(vb, 0, 0, &need);
     MPF_HIP_TRY(c, c->rb_g.grow(need.rows));                        // (once, before the first launch that uses them)
@@ -920,26 +825,23 @@ int mpf_geequ_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_A, doub
 int mpf_laqge_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t rule, const double *d_A, const double *d_r, const double *d_c,
                        const double *d_rowcnd, const double *d_colcnd, const double *d_amax, const int32_t *d_info, double *d_out,
                        int32_t *d_equed, double *d_spread) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "laqge_vbatched");
+    const char *who = "laqge_vbatched";
+    int rc = vb_enter(c, vb, who);
     if (rc) return rc;
     if (rule < 0 || rule > 2) { c->err = "laqge_vbatched: rule must be 0, 1 or 2"; return -1; }
     if (vb->plan.batch == 0) return 0;
-    if (!d_rowcnd || !d_colcnd || !d_amax || !d_info || !d_equed || (vb->plan.total_n > 0 && (!d_A || !d_r || !d_c || !d_out))) {
-        c->err = "laqge_vbatched: null pointer";
-        return -1;
-    }
+    if (!d_rowcnd || !d_colcnd || !d_amax || !d_info || !d_equed || (vb->plan.total_n > 0 && (!d_A || !d_r || !d_c || !d_out)))
+        return null_pointer(c, who);
     if (vb->plan.total_n > 0 && d_out != d_A && ba::ranges_overlap((uintptr_t)d_A, vb->plan.extent, (uintptr_t)d_out, vb->plan.extent)) {
         c->err = "laqge_vbatched: d_out overlaps d_A (in place is d_out == d_A)";
         return -1;
     }
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     const BtRagged v = vb_arrays(vb);
-    for (int64_t i0 = 0; i0 < vb->plan.batch; i0 += BT_MAX_LAUNCH) {
-        const int64_t nb = vb->plan.batch - i0 < BT_MAX_LAUNCH ? vb->plan.batch - i0 : BT_MAX_LAUNCH;
-        rc = launch_laqge_decide(c, rule, 0, nb, vb->d_list.get() + i0, &v, d_r, d_c, d_rowcnd, d_colcnd, d_amax, d_info, d_equed, d_spread);
-        if (rc) return rc;
-    }
+    rc = ba::chunks(vb->plan.batch, BT_MAX_LAUNCH, [&](int64_t i0, int64_t nb) {
+        return launch_laqge_decide(c, rule, 0, nb, vb->d_list.get() + i0, &v, d_r, d_c, d_rowcnd, d_colcnd, d_amax, d_info, d_equed, d_spread);
+    });
+    if (rc) return rc;
     for (const vbatch::Chunk &k : vb_refine_chunks(vb, 0, 0, nullptr)) {
         rc = launch_laqge_vbatched(c, v, vb->d_list.get() + k.first, k.count, k.nmax, d_A, d_r, d_c, d_equed, d_out);
         if (rc) return rc;
@@ -949,13 +851,14 @@ int mpf_laqge_vbatched(mpf_ctx *c, const mpf_vbatch *vb, int32_t rule, const dou
 
 int mpf_lascl2_vbatched(mpf_ctx *c, const mpf_vbatch *vb, const double *d_s, int32_t nrhs, double *d_V, int64_t ldv, const int32_t *d_equed,
                         int32_t bit) {
-    if (!c) return -1;
-    int rc = vb_enter(c, vb, "lascl2_vbatched");
+    const char *who = "lascl2_vbatched";
+    int rc = vb_enter(c, vb, who);
     if (rc) return rc;
     if (nrhs < 0) { c->err = "lascl2_vbatched: nrhs must not be negative"; return -1; }
     if (vb->plan.batch == 0 || vb->plan.total_n == 0 || nrhs == 0) return 0;
-    if (ldv < vb->plan.total_n) { c->err = "lascl2_vbatched: leading dimension of V < total_n"; return -1; }
-    if (!d_s || !d_V) { c->err = "lascl2_vbatched: null pointer"; return -1; }
+    rc = vb_check_ld(c, vb, who, "V", ldv);
+    if (rc) return rc;
+    if (!d_s || !d_V) return null_pointer(c, who);
     MPF_HIP_TRY(c, hipSetDevice(c->device));
     const BtRagged v = vb_arrays(vb);
     constexpr int32_t KC = 1 << 16;                                 // columns per launch (a grid dimension of four columns each)

@@ -9,6 +9,9 @@
 //   chunks_fail batch step at                     the same when the chunk that starts at `at` returns 7, then " rc <what chunks returned>"
 //   residual_step max_units max_launch nrhs       the step
 //   ferr_step max_launch n nrhs                   the step
+//   lange_mode who letter, gecon_mode who letter  the mode or "error <text>"
+//   nrhs_trans who nrhs trans                     "ok" or "error <text>"
+//   itmax itmax                                   the clamped limit
 #include "../mixed-precision_lu_factorization_amd/csrc/batch_args.h"
 #include <iostream>
 #include <sstream>
@@ -59,6 +62,16 @@ int main() {
         } else if (cmd == "ferr_step") {
             in >> a >> b >> c;
             std::cout << ba::ferr_step(a, (int32_t)b, (int32_t)c) << '\n';
+        } else if (cmd == "lange_mode" || cmd == "gecon_mode") {
+            in >> who >> what;
+            const int mode = cmd == "lange_mode" ? ba::lange_mode(err, who.c_str(), what.at(0)) : ba::gecon_mode(err, who.c_str(), what.at(0));
+            std::cout << (mode < 0 ? "error " + err : std::to_string(mode)) << '\n';
+        } else if (cmd == "nrhs_trans") {
+            in >> who >> a >> b;
+            answer(ba::check_nrhs_trans(err, who.c_str(), (int32_t)a, (int32_t)b), err);
+        } else if (cmd == "itmax") {
+            in >> a;
+            std::cout << ba::clamp_itmax((int32_t)a) << '\n';
         } else {
             return 2;
         }

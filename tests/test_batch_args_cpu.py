@@ -1,5 +1,5 @@
 """CPU checks of csrc/batch_args.h (the argument rules of the strided batched entry points: size check, strided-operand check, getri's
-out-of-place test, the forwarding predicate, the chunks of a long batch): a stand-alone driver (tests/batch_args_driver.cpp, built here
+out-of-place test, the forwarding predicate, the chunks of a long batch, the norm letters, the nrhs / trans refusal, the itmax clamp): a stand-alone driver (tests/batch_args_driver.cpp, built here
 with AddressSanitizer and UBSan and run directly) against a literal table.  The texts are the ones the entry points have always
 returned; the GPU argument tests (test_gpu_batched*.py) see them through the library."""
 import os
@@ -103,6 +103,30 @@ TABLE = [
     (f"ferr_step {BB_MAX_LAUNCH} 1024 {1 << 25}", "1"),
     ("chunks 30813 30812", "0:30812 30812:1"),
     ("chunks 1000 481", "0:481 481:481 962:38"),
+    # the norm letters, either case: lange 0 / 1 / 2, gecon 0 / 1 ('M' is no norm of the inverse)
+    ("lange_mode lange_batched 1", "0"), ("lange_mode lange_batched O", "0"), ("lange_mode lange_batched o", "0"),
+    ("lange_mode lange_batched_blocked I", "1"), ("lange_mode lange_batched_blocked i", "1"),
+    ("lange_mode lange_vbatched M", "2"), ("lange_mode lange_vbatched m", "2"),
+    ("lange_mode lange_batched F", "error lange_batched: norm must be '1', 'O', 'I' or 'M'"),
+    ("lange_mode lange_batched_blocked 2", "error lange_batched_blocked: norm must be '1', 'O', 'I' or 'M'"),
+    ("lange_mode lange_vbatched X", "error lange_vbatched: norm must be '1', 'O', 'I' or 'M'"),
+    ("gecon_mode gecon_batched 1", "0"), ("gecon_mode gecon_batched O", "0"), ("gecon_mode gecon_batched o", "0"),
+    ("gecon_mode gecon_batched_blocked I", "1"), ("gecon_mode gecon_vbatched i", "1"),
+    ("gecon_mode gecon_batched M", "error gecon_batched: norm must be '1', 'O' or 'I'"),
+    ("gecon_mode gecon_batched_blocked m", "error gecon_batched_blocked: norm must be '1', 'O' or 'I'"),
+    ("gecon_mode gecon_vbatched 0", "error gecon_vbatched: norm must be '1', 'O' or 'I'"),
+    # nrhs before trans; nrhs == 0 is no refusal (the entry returns 0 after it)
+    ("nrhs_trans getrs_batched 1 0", "ok"), ("nrhs_trans getrs_batched 1 1", "ok"), ("nrhs_trans getrs_batched 0 0", "ok"),
+    ("nrhs_trans getrs_batched 0 1", "ok"),
+    ("nrhs_trans getrs_batched 1 -1", "error getrs_batched: trans must be 0 or 1"),
+    ("nrhs_trans residual_batched_blocked 1 2", "error residual_batched_blocked: trans must be 0 or 1"),
+    ("nrhs_trans gerfs_vbatched 0 2", "error gerfs_vbatched: trans must be 0 or 1"),
+    ("nrhs_trans gerfs_batched -1 0", "error gerfs_batched: nrhs must not be negative"),
+    ("nrhs_trans getrs_vbatched -1 1", "error getrs_vbatched: nrhs must not be negative"),
+    ("nrhs_trans getrs_batched_blocked -1 2", "error getrs_batched_blocked: nrhs must not be negative"),
+    ("nrhs_trans residual_vbatched -1 -1", "error residual_vbatched: nrhs must not be negative"),
+    # the iteration limit: 5 by default, at most 31
+    ("itmax -3", "5"), ("itmax 0", "5"), ("itmax 1", "1"), ("itmax 31", "31"), ("itmax 32", "31"),
 ]
 
 
